@@ -16,7 +16,13 @@ Workloads (synthetic, zipkin-tracegen shape: maxDepth 6, ~24 records / ~12 logic
      at every N). Every rank hashes the finalized table (SHA-256 of m0..m4 + present); the digests
      must agree across ranks and with the G = 1 digest in tests/golden/c3_digest.json.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run (no --full) sets up, warms up, times --steps steps and prints the line. --full adds the
+legs that take runs of their own: serial steps that time K1 alone (the roofline's achieved / frac),
+the CPU baseline and the oracle parity leg, the comparison of the pipelined table sets, the
+shuffled-vs-clustered comparison and the C3 digest checks; a failing check fails the run.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
        python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -40,6 +46,18 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="c2/c3: besides the timed steps, run every leg that takes runs of its own: the serial "
+                         "steps that time K1 alone (roofline.achieved / frac), the CPU baseline and the oracle "
+                         "parity leg (--cpu-sample), the bit-for-bit comparison of the pipelined table sets, the "
+                         "shuffled-vs-clustered comparison, the C3 digest checks. Without it the run sets up, "
+                         "warms up, times --steps steps and prints the line (those fields are null). The other "
+                         "workloads (c1, c4, c5, ingest) always carry their own baseline and parity legs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float64): c1/c2/c3 the finalized table m0..m4 + present, c4 every service's top-K "
+                         "(keys as two 32-bit halves, estimates, counts), c5 the HLL registers and histogram "
+                         "bins. The inputs depend only on the arguments, so two builds compare output for output")
     ap.add_argument("--records", type=int, default=None,
                     help="c2: span records per GPU (default 1e8); c3: records of the whole global set (default 1e9)")
     ap.add_argument("--services", type=int, default=500)
@@ -98,6 +116,8 @@ def parse():
     ap.add_argument("--items", type=int, default=1_000_000_000,
                     help="c4: binary annotations per step (BASELINE configs[3]: 1e9, 12 GB in HBM)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.workload is None:
         a.workload = "c3" if int(os.environ.get("WORLD_SIZE", "1")) > 1 else "c2"
     if a.records is None:  # c3 and c5 run configs[2] / configs[4] at their stated 1e9 spans
@@ -106,7 +126,28 @@ def parse():
         a.pipeline = 3 if a.workload in ("c2", "c3") else 0 if a.workload == "c4" else 1
     if a.comm is None:
         a.comm = "zk" if os.environ.get("ZK_BENCH_BACKEND", "nccl") == "nccl" else "torch"
+    if a.dump_outputs and a.workload == "ingest":
+        ap.error("--dump-outputs: the ingest workload's decoded columns are not dumped")
     return a
+
+
+DUMP_BUDGET = 64_000_000  # bytes of --dump-outputs files in all
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: numpy array} as dirname/<name>.npy in float64 (every value here is an integer
+    below 2^53 or already a float64, so nothing is rounded). An array over its share of DUMP_BUDGET
+    is cut to a fixed sample of its elements (numpy default_rng(0), in index order)."""
+    import numpy as np
+
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    share = (DUMP_BUDGET - 4096 * len(arrays)) // (8 * len(arrays))  # elements per array, headers aside
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        if v.size > share:
+            v = v.ravel()[np.sort(np.random.default_rng(0).choice(v.size, share, replace=False))]
+        np.save(d / f"{name}.npy", v.astype(np.float64))
 
 
 def init_dist():
@@ -313,22 +354,32 @@ def main():
 
     if debug:
         sums0 = (csum(cols), csum(clustered_cols))
-    # warmup: serial steps first (their K1 launches give the isolated K1 duration), then two
-    # pipelined steps so that the second set's buffers exist before the timed region
-    # (at least ISOLATED + 1 serial steps: untimed, outside the timed region, so that the isolated K1
-    # figure averages several warm launches whatever --warmup is)
-    ISOLATED = 8
-    tmf = None
-    for i in range(max(a.warmup, ISOLATED + 1)):
-        step_serial()
-        if i == 0:  # the first launch is cold: the isolated figure averages the later ones
-            tmf = dict(ctx.timing())
-    torch.cuda.synchronize()
-    tmw = ctx.timing()
-    k1_isolated_ms = (tmw["join_ms_total"] - tmf["join_ms_total"]) / (tmw["join_calls"] - tmf["join_calls"])
-    isolated_launches = tmw["join_calls"] - tmf["join_calls"]
-    if pipeline:
-        for _ in range(len(sets)):
+    k1_isolated_ms = isolated_launches = None
+    if a.full:
+        # warmup: serial steps first (their K1 launches give the isolated K1 duration), then two
+        # pipelined steps so that the second set's buffers exist before the timed region
+        # (at least ISOLATED + 1 serial steps: untimed, outside the timed region, so that the isolated K1
+        # figure averages several warm launches whatever --warmup is)
+        ISOLATED = 8
+        tmf = None
+        warmed = max(a.warmup, ISOLATED + 1) + (len(sets) if pipeline else 0)
+        for i in range(max(a.warmup, ISOLATED + 1)):
+            step_serial()
+            if i == 0:  # the first launch is cold: the isolated figure averages the later ones
+                tmf = dict(ctx.timing())
+        torch.cuda.synchronize()
+        tmw = ctx.timing()
+        k1_isolated_ms = (tmw["join_ms_total"] - tmf["join_ms_total"]) / (tmw["join_calls"] - tmf["join_calls"])
+        isolated_launches = tmw["join_calls"] - tmf["join_calls"]
+        if pipeline:
+            for _ in range(len(sets)):
+                step()
+            drain()
+    else:
+        # a plain run warms the steps it times: --warmup of them, and at least one per table set so
+        # that every set's buffers exist before the timed region
+        warmed = max(a.warmup, len(sets) if pipeline else 1)
+        for _ in range(warmed):
             step()
         drain()
     torch.cuda.synchronize()
@@ -367,19 +418,23 @@ def main():
     join_calls = tm1["join_calls"] - tm0["join_calls"]
     join_avg_ms = (tm1["join_ms_total"] - tm0["join_ms_total"]) / max(1, join_calls)
     st = ctx.stats()
+    if a.dump_outputs and rank == 0:
+        # the table the last timed step finalized (the set that took the last batch)
+        last = sets[(state["k"] - 1) % len(sets)][3] if pipeline else out
+        dump_outputs(a.dump_outputs, {k: v.cpu().numpy() for k, v in last.items()})
     if pipeline:
         # both pipeline sets finalized the same batch: their outputs must agree bit for bit
         for c2, _, _, o2 in sets[1:]:
-            for k in out:
+            for k in out if a.full else ():
                 if not torch.equal(out[k], o2[k]):
                     raise RuntimeError(f"pipelined step: output '{k}' differs between the table sets")
             c2.close()
 
     # the finalized table's digest on every rank (all ranks hold the merged job): C3 checks it
     # against the other ranks and against the G = 1 digest of the same global set
-    digest = table_digest(out)
+    digest = table_digest(out) if a.full else None
     digest_check = None
-    if c3:
+    if c3 and a.full:
         digests = [digest]
         if dist is not None:
             digests = [None] * world
@@ -400,7 +455,7 @@ def main():
         print(f"[debug] column sums before/after: {sums0 == sums1} {sums0} {sums1}", file=sys.stderr, flush=True)
     cpu = parity = None
     shuffled_parity = None
-    if shuffled:
+    if shuffled and a.full:
         # the whole shuffled batch must give the clustered batch's result bit for bit (every cell's
         # m0..m4 and every counter): permutation invariance at full size
         ref_out = {k: torch.empty_like(v) for k, v in out.items()}
@@ -417,16 +472,17 @@ def main():
         shuffled_parity = {"result": "exact", "records": n,
                            "checked": "m0..m4, present and all counters of the shuffled full batch == the clustered batch"}
     full = None
-    if rank == 0 and world == 1 and c3 and a.cpu_sample > 0:
+    cpu_leg = a.full and rank == 0 and world == 1 and a.cpu_sample > 0
+    if cpu_leg and c3:
         # configs[2] pinned at full size: the CPU port over the WHOLE global set, bit for bit
         cpu, full = c3_full_oracle(clustered_cols, n, S, a.cpu_threads or usable_cpus(), out, st, digest)
-    elif rank == 0 and world == 1 and a.cpu_sample > 0 and shuffled:
+    elif cpu_leg and shuffled:
         # the shuffled batch as it is (any order: no prefix of it is trace-complete) through the port's
         # hash-partitioned mode, against the GPU's table of the same batch
         cpu, parity = shuffled_oracle(cols, n, S, a.cpu_threads or usable_cpus(), out, st)
-    elif rank == 0 and world == 1 and a.cpu_sample > 0:
+    elif cpu_leg:
         cpu, parity = cpu_baseline(clustered_cols, min(a.cpu_sample, n), S, a.cpu_threads or usable_cpus(), dev)
-    if c3:
+    if c3 and a.full:
         parity = {"digest": digest_check, "full_vs_oracle": full, "prefix_vs_oracle": parity}
 
     # PMC counters need their own rocprofv3 --pmc run (tools/pmc.sh), so the traffic figure is the
@@ -450,6 +506,8 @@ def main():
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "warmup_steps": warmed,  # the untimed steps actually run: --warmup is a lower bound
+            "full": a.full,
             "ms_per_step": elapsed * 1e3 / a.steps,
             "higher_is_better": True,
             "scaling": "strong" if c3 else "weak",
@@ -492,10 +550,11 @@ def main():
                 "bound": "hbm",
                 "kernel": ("k_group_join (+ the fallback's P3 list pass and K1 append, normally empty)"
                            if shuffled and not a.verify else "k_span_join_stream"),
-                "achieved": n * BYTES_PER_RECORD / (k1_isolated_ms * 1e-3) / 1e9,
+                # achieved, frac, avg_launch_ms, launches: the serial steps of a --full run (else null)
+                "achieved": n * BYTES_PER_RECORD / (k1_isolated_ms * 1e-3) / 1e9 if a.full else None,
                 "peak": PEAK_HBM_GBS,
                 "unit": "GB/s",
-                "frac": n * BYTES_PER_RECORD / (k1_isolated_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
+                "frac": n * BYTES_PER_RECORD / (k1_isolated_ms * 1e-3) / 1e9 / PEAK_HBM_GBS if a.full else None,
                 "traffic": traffic if not shuffled else None,
                 "traffic_source": traffic_src if not shuffled else None,
                 "algorithmic_bytes_per_launch": n * BYTES_PER_RECORD,
@@ -985,6 +1044,10 @@ def bench_c5(a):
     tm1 = ctx.timing()
     calls = tm1["join_calls"] - tm0["join_calls"]
     join_ms = (tm1["join_ms_total"] - tm0["join_ms_total"]) / max(1, calls)
+    if a.dump_outputs and rank == 0:
+        # the sketch of the last timed step (the set that took it)
+        dr, dh = (sets[(k[0] - 1) % 2][1] if a.pipeline != 0 else rt).read()
+        dump_outputs(a.dump_outputs, {"hll_registers": dr, "histogram": dh})
     if a.pipeline != 0:
         # both sets sketched the same batch: registers and bins must agree exactly
         (ra, ha), (rb, hb) = rt.read(), rt2.read()
@@ -1086,6 +1149,8 @@ def bench_c1(a):
         ctx.finalize(out_device=out)
 
     wall, ev_ms = _timed(step, a.steps, a.warmup, stream)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {k: v.cpu().numpy() for k, v in out.items()})
     got = ctx.finalize()
     st = ctx.stats()
     ref = oracle.aggregate(host, S)
@@ -1190,6 +1255,11 @@ def bench_c4(a):
         kv.topk_all(10)
         qt.append((time.perf_counter() - t0) * 1e3)
     query_ms = sorted(qt)[2]
+    if a.dump_outputs:
+        # the sketch of the last timed step (the set that took it), as its query answers it
+        dk, de, dc = (sets[(k[0] - 1) % 2][0] if a.pipeline != 0 else kv).topk_all(10)
+        dump_outputs(a.dump_outputs, {"topk_key_hi": dk >> np.uint64(32), "topk_key_lo": dk & np.uint64(0xFFFFFFFF),
+                                      "topk_estimate": de, "topk_count": dc})
     if a.pipeline != 0:
         kk2, est2, cnt2 = kv2.topk_all(10)
         if not (np.array_equal(kk, kk2) and np.array_equal(est, est2) and np.array_equal(cnt, cnt2)):

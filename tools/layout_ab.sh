@@ -2,12 +2,14 @@
 # A/B: the C2 columns as seven allocations vs one packed block (DeviceColumns(packed=True)), pipelined
 # and serial steps, interleaved. Prints ms_per_step and K1's event ms per line.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+OUT=${OUT:-bench_logs}  # where the runs' logs go
+mkdir -p "$OUT"
 for r in 1 2; do
   for lay in separate packed; do
     for pipe in 3 0; do
-      timeout -k 10 200 python -u bench.py --layout $lay --pipeline $pipe --cpu-sample 0 --steps 20 > gpurun_out/lay_${lay}_${pipe}_$r.json 2> gpurun_out/lay_${lay}_${pipe}_$r.err || { echo "bench failed"; tail gpurun_out/lay_${lay}_${pipe}_$r.err; exit 1; }
-      python - "$lay" "$pipe" "$r" gpurun_out/lay_${lay}_${pipe}_$r.json <<'PY'
+      # --full: K1's event ms and frac printed below come from its serial steps
+      timeout -k 10 200 python -u bench.py --full --layout $lay --pipeline $pipe --cpu-sample 0 --steps 20 > "$OUT/lay_${lay}_${pipe}_$r.json" 2> "$OUT/lay_${lay}_${pipe}_$r.err" || { echo "bench failed"; tail "$OUT/lay_${lay}_${pipe}_$r.err"; exit 1; }
+      python - "$lay" "$pipe" "$r" "$OUT/lay_${lay}_${pipe}_$r.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[4]).read().strip().splitlines()[-1])
 r = d.get("roofline", {})

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-launch HBM bytes of K1 from rocprofv3 --pmc passes -> profiles/pmc_latest.json.
 
-Reads every *counter_collection.csv under the given directory (default gpurun_out/pmc), averages
+Reads every *counter_collection.csv under the given directory (default bench_logs/pmc), averages
 FETCH_SIZE and WRITE_SIZE (KiB) over the launches of the K1 kernel and applies the gfx950
 correction of /opt/skills/guides/MI355X_MICROARCH.md ("HBM"): FETCH_SIZE reports half the bytes of
 a wide coalesced streaming read, so it is doubled; WRITE_SIZE is taken as is.
@@ -14,7 +14,7 @@ import sys
 from pathlib import Path
 
 KERNEL = sys.argv[2] if len(sys.argv) > 2 else "k_span_join"
-root = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/pmc"
+root = sys.argv[1] if len(sys.argv) > 1 else "bench_logs/pmc"
 records = int(sys.argv[3]) if len(sys.argv) > 3 else 99999986
 
 vals = {"FETCH_SIZE": [], "WRITE_SIZE": []}

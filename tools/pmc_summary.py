@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Average PMC counters per kernel over all pmc passes in gpurun_out/pmc (rocprofv3 csv)."""
+"""Average PMC counters per kernel over all pmc passes in bench_logs/pmc (rocprofv3 csv)."""
 import csv, glob, sys
 from collections import defaultdict
 
-root = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/pmc"
+root = sys.argv[1] if len(sys.argv) > 1 else "bench_logs/pmc"
 acc = defaultdict(lambda: defaultdict(list))
 for f in glob.glob(f"{root}/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):

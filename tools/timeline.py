@@ -2,7 +2,7 @@
 """Timeline of the last timed steps from a rocprofv3 --kernel-trace CSV: every dispatch's start/end
 relative to the first K1 of the window, its stream, and the idle time between K1 launches.
 
-  python tools/timeline.py gpurun_out/tl/<...>_kernel_trace.csv [--last 4]
+  python tools/timeline.py bench_logs/tl/<...>_kernel_trace.csv [--last 4]
 """
 import argparse
 import csv
