@@ -650,7 +650,9 @@ __global__ __launch_bounds__(WG, ZK_K1_WGS_PER_CU * WG / 256) void k_span_join_s
         uint64_t r_link[2], r_item[2];
         uint32_t r_isvc[2];
         uint64_t r_lkey[2] = {0, 0};  // kModeLinks: the link's realtime item key (child-major cell | d)
-        uint32_t nl = 0, ni = 0;
+        // lm: bit e set when element e emits a link. Not read off r_link: the link of cell 2^24 - 1 with
+        // d = 2^40 - 1 (S = 4096) is the all-ones word
+        uint32_t lm = 0, ni = 0;
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             r_link[e] = ~0ull;
@@ -724,15 +726,15 @@ __global__ __launch_bounds__(WG, ZK_K1_WGS_PER_CU * WG / 256) void k_span_join_s
             r_link[e] = (cell << 40) | d;
             if constexpr (LINKS) r_lkey[e] = (((uint64_t)(sL & kSvcIdMask) * a.S + (sp & kSvcIdMask)) << 40) | d;
             if (a.nb) atomicAdd(&s_hist[cell >> a.cb_shift], 1u);
-            ++nl;
+            lm |= 1u << e;
         }
         ZK_STAMP(5);
         // ---- 7. append the window's links (and sketch items) to this workgroup's lists ----------
         // no barrier: each wave claims its slice of the workgroup's lists with ONE LDS atomic on a
         // cursor (links in the low 32 bits, sketch items in the high 32); lane offsets from ballots
-        // (nl, ni are 0..2). The waves' order inside a list is whatever the atomics give -- the
+        // (0..2 links and items per lane). The waves' order inside a list is whatever the atomics give -- the
         // reduce adds exact integers, so it is free.
-        const uint64_t l1 = __ballot(nl >= 1u), l2 = __ballot(nl >= 2u);
+        const uint64_t l1 = __ballot(lm != 0u), l2 = __ballot(lm == 3u);
         const uint64_t i1 = EMIT ? __ballot(ni >= 1u) : 0ull, i2 = EMIT ? __ballot(ni >= 2u) : 0ull;
         uint32_t lbase = 0, ibase = 0;
         {
@@ -763,7 +765,7 @@ __global__ __launch_bounds__(WG, ZK_K1_WGS_PER_CU * WG / 256) void k_span_join_s
 #elif !defined(ZK_K1_DIAG_NOSTORE)
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-                const bool v = r_link[e] != ~0ull;
+                const bool v = (lm >> e) & 1u;
                 const uint64_t at = v ? (uint64_t)pos : trash;
                 out[at] = r_link[e];
                 if constexpr (LINKS) {  // the realtime link item at the link's own position
@@ -1368,7 +1370,7 @@ __global__ __launch_bounds__(kGWG, kGPerCU * kGWG / 256) void k_group_join(JoinA
         ld2_u64((const uint64_t*)a.c.last_ts, nbase + 2 * threadIdx.x, a.c.n, cur.last);
         // ---- filter(isValid), join on (parentId, traceId), links ---------------------------------
         uint64_t r_link[2];
-        uint32_t nl = 0;
+        uint32_t lm = 0;  // bit e: element e emits a link (a link may itself be the all-ones word)
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             r_link[e] = ~0ull;
@@ -1427,14 +1429,14 @@ __global__ __launch_bounds__(kGWG, kGPerCU * kGWG / 256) void k_group_join(JoinA
             const uint64_t cell = (uint64_t)(sp & kSvcIdMask) * a.S + (sL & kSvcIdMask);
             r_link[e] = (cell << 40) | d;
             if (a.nb) atomicAdd(&s_hist[cell >> a.cb_shift], 1u);
-            ++nl;
+            lm |= 1u << e;
         }
         ZK_STAMP(4);
         ld2_u64(a.c.trace_id, nbase + 2 * threadIdx.x, a.c.n, cur.tid);
         ld2_u64(a.c.parent_id, nbase + 2 * threadIdx.x, a.c.n, cur.pid);
         ld2_u32(a.c.flags, nbase + 2 * threadIdx.x, a.c.n, cur.flags);
         // ---- append: one LDS atomic per wave claims its slice of the workgroup's list ------------
-        const uint64_t l1 = __ballot(nl >= 1u), l2 = __ballot(nl >= 2u);
+        const uint64_t l1 = __ballot(lm != 0u), l2 = __ballot(lm == 3u);
         uint32_t lbase = 0;
         {
             const uint32_t wtot = (uint32_t)(__popcll(l1) + __popcll(l2));
@@ -1445,7 +1447,7 @@ __global__ __launch_bounds__(kGWG, kGPerCU * kGWG / 256) void k_group_join(JoinA
         uint32_t pos = lbase;
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            const bool v = r_link[e] != ~0ull;
+            const bool v = (lm >> e) & 1u;
             out[v ? (uint64_t)pos : trash] = r_link[e];
             pos += v ? 1u : 0u;
         }

@@ -58,7 +58,8 @@ __global__ __launch_bounds__(kRlWG) void k_rl_gather(const uint64_t* __restrict_
     }
 }
 
-// items of the window whose key lies in [lo, hi): counted (k_rl_count), then copied out in any order
+// items of the window whose key lies in [lo, hi] (hi inclusive: the last server's range ends at the
+// all-ones key, whose successor does not fit 64 bits): counted (k_rl_count), then copied out in any order
 // (k_rl_select, one output claim per wave)
 __global__ __launch_bounds__(kRlWG) void k_rl_count(const uint64_t* __restrict__ wkey, const unsigned long long* __restrict__ wcount,
                                                     uint64_t wcap, uint64_t lo, uint64_t hi, unsigned long long* __restrict__ out) {
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(kRlWG) void k_rl_count(const uint64_t* __restrict__
     uint32_t c = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * kRlWG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kRlWG) {
         const uint64_t k = wkey[i];
-        c += (k >= lo && k < hi) ? 1u : 0u;
+        c += (k >= lo && k <= hi) ? 1u : 0u;
     }
     // wave sum, one atomic per wave
     for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(kRlWG) void k_rl_select(const uint64_t* __restrict_
     for (uint64_t i0 = (uint64_t)blockIdx.x * kRlWG + (threadIdx.x & ~63u); i0 < n; i0 += step) {
         const uint64_t i = i0 + lane;
         const uint64_t k = i < n ? wkey[i] : 0ull;
-        const bool take = i < n && k >= lo && k < hi;
+        const bool take = i < n && k >= lo && k <= hi;
         const uint64_t m = __ballot(take);
         if (!m) continue;
         unsigned long long base = 0;
@@ -289,7 +290,9 @@ zk_status zk_rl_server_links(zk_rl* r, uint32_t server, uint32_t* parent, int64_
     if (!r || !n) return ZK_ERR_INVALID_ARG;
     if (server >= r->S) return lfail(r, ZK_ERR_SERVICE_RANGE, "server service id >= num_services");
     RL_HIP(r, hipSetDevice(r->device));
-    const uint64_t lo = ((uint64_t)server * r->S) << 40, hi = ((uint64_t)(server + 1) * r->S) << 40;
+    // the server's keys, both ends inclusive: (server + 1) * S << 40 wraps to 0 for server 4095 of 4096, and
+    // the wrapped value minus one is still the range's last key (all ones)
+    const uint64_t lo = ((uint64_t)server * r->S) << 40, hi = (((uint64_t)(server + 1) * r->S) << 40) - 1;
     const uint32_t grid = r->cus * 4;
     RL_HIP(r, hipMemsetAsync(r->cnt + 2, 0, 8, r->stream));
     if (r->wkey)
