@@ -73,7 +73,8 @@ typedef enum zk_status {
  *   first_ts, last_ts              min/max annotation timestamp, us (Span.scala:174-191,72-74)
  *   service_id                     dictionary id of the fragment's service name (Span.scala:125-131):
  *                                  the host of its first sr/ss annotation, else of its first cs/cr
- *   flags                          ZK_F_* below
+ *   flags                          ZK_F_* below: bits 0..15 the fragment's own bits and counts, bits
+ *                                  16..31 its span-name id (Span.name), 0 = no name
  * ------------------------------------------------------------------------------------------ */
 #define ZK_F_HAS_PARENT      (1u << 0)   /* parentId.isDefined */
 #define ZK_F_HAS_ANNOTATIONS (1u << 1)   /* first_ts/last_ts are meaningful */
@@ -86,6 +87,14 @@ typedef enum zk_status {
 #define ZK_F_SR_SHIFT 12
 #define ZK_F_SS_SHIFT 14
 #define ZK_F_COUNT_MASK 3u
+/* Bits 16..31: the fragment's span-name id. 0 = no name -- the name is "", "Unknown" or absent,
+   exactly the names Span.mergeSpan never selects (Span.scala:153-158); 1..65535 = the host's
+   span-name dictionary id plus one. The dependency path masks the fields it reads and ignores these
+   bits (a batch with zeros there means what it always meant); they reach the realtime link store
+   (zksketch.h, zk_rl_server_rpc_links), where a merged span's name id is the MAXIMUM over its
+   fragments. */
+#define ZK_F_NAME_SHIFT 16
+#define ZK_F_NAME_MASK 0xFFFFu
 
 typedef struct zk_span_cols {
     const uint64_t* trace_id;

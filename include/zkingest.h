@@ -52,6 +52,13 @@ extern "C" {
 #define ZK_INGEST_ONE_THREAD 2u    /* host decoder: decode on the calling thread only (by default up to
                                       16 threads decode contiguous ranges; records, items, service ids
                                       and errors are the same either way) */
+#define ZK_INGEST_SPAN_NAMES 4u     /* host decoder: keep a span-name dictionary (ids in order of first
+                                      appearance, the same for any thread count, names compared byte for
+                                      byte) and write id + 1 into bits 16..31 of every record's flags
+                                      (zkagg.h ZK_F_NAME_SHIFT); "" and "Unknown" get 0. At most 65535
+                                      names: a batch that needs more fails with ZK_ERR_CAPACITY. Without
+                                      the flag those bits are 0. The device decoder has no span-name
+                                      dictionary and returns ZK_ERR_UNSUPPORTED for this flag. */
 /* Both decoders (host zk_ingest_spans, device zk_ingest_dev_spans) reject a Snappy fragment whose
  * header announces more than ZK_INGEST_MAX_FRAGMENT bytes, or more than the format can expand its
  * payload to (a 3-byte copy emits at most 64 bytes: < ZK_SNAPPY_MAX_EXPANSION x), before any
@@ -89,6 +96,10 @@ zk_status zk_ingest_spans(zk_ingest* ing, const uint8_t* buf, const uint64_t* of
 zk_status zk_ingest_num_services(const zk_ingest* ing, uint32_t* n);
 zk_status zk_ingest_service_id(zk_ingest* ing, const char* name, uint64_t len, uint32_t* id);  /* adds if new */
 zk_status zk_ingest_service_name(const zk_ingest* ing, uint32_t id, char* buf, uint64_t cap, uint64_t* len);
+/* the span-name dictionary (ZK_INGEST_SPAN_NAMES); a record's flags carry id + 1 */
+zk_status zk_ingest_num_span_names(const zk_ingest* ing, uint32_t* n);
+zk_status zk_ingest_span_name_id(zk_ingest* ing, const char* name, uint64_t len, uint32_t* id);  /* adds if new */
+zk_status zk_ingest_span_name(const zk_ingest* ing, uint32_t id, char* buf, uint64_t cap, uint64_t* len);
 /* the string behind a key / value hash seen by this decoder (two-phase: buf NULL -> *len) */
 zk_status zk_ingest_string(const zk_ingest* ing, uint64_t hash, char* buf, uint64_t cap, uint64_t* len);
 

@@ -177,14 +177,24 @@ zk_status   zk_rt_dropped(zk_rt* rt, uint64_t* service_range, uint64_t* duration
  * service, child = server service, child duration, traceId) row per joined child span
  * (ZipkinAggregateJob.scala:25-37). Bound to a dependency ctx, every later zk_deps_accumulate writes
  * one item per link it emits (K1 and the spill kernel, beside the link, in the same pass) and
- * appends them to the store's window in HBM (16 B per link; grown as it fills: one link per record at
- * most). zk_rl_server_links answers one server service: every row whose child is `server`, as
- * parent ids, durations (us) and traceIds, ordered by (parent, duration, traceId) -- one filter pass
- * over the window, then a host sort of that server's rows. zk_rl_reset starts a new window (the
- * host keeps one store per time window). The ctx and the store must agree on num_services; a store
- * cannot share a ctx with a ZK_RT_WITH_DEPS sketch (ZK_ERR_UNSUPPORTED), and unclustered batches take
- * the streaming join (not the group join) while a store is bound. The record has no span name, so the
- * trait's rpcName is not a key here (GpuRealtimeAggregates).
+ * appends them to the store's window in HBM (20 B per link: u64 key, u64 traceId, u32 rpc id; grown
+ * as it fills: one link per record at most). zk_rl_server_links answers one server service: every row
+ * whose child is `server`, as parent ids, durations (us) and traceIds, ordered by (parent, duration,
+ * traceId) -- one filter pass over the window, then a host sort of that server's rows. zk_rl_reset
+ * starts a new window in O(1) (the host keeps one store per time window). The ctx and the store must
+ * agree on num_services; a store cannot share a ctx with a ZK_RT_WITH_DEPS sketch
+ * (ZK_ERR_UNSUPPORTED), and unclustered batches take the streaming join (not the group join) while a
+ * store is bound.
+ *
+ * rpcName is a key: a row's rpc id is the span-name id of the server (child) span, carried in bits
+ * 16..31 of the record's flags (zkagg.h, ZK_F_NAME_SHIFT; the host decoder fills them with
+ * ZK_INGEST_SPAN_NAMES, zkingest.h). The merged span's id is the MAXIMUM id over its fragments, 0 when
+ * none carries a name. Span.mergeSpan (Span.scala:153-158) takes the first name of its reduce order
+ * that is neither "" nor "Unknown" -- the names with id 0 -- so when the named fragments of a span
+ * agree, the normal case, the maximum is the reference's pick under every order; when they disagree
+ * the reference's pick depends on the order and the maximum is the deterministic choice, as the
+ * smallest service key and parentId are for those fields. zk_rl_server_rpc_links selects the rows of
+ * (server, rpc) in the same device count and select passes.
  * ------------------------------------------------------------------------------------------ */
 typedef struct zk_rl_config {
     uint32_t num_services;  /* S <= 4096, the ctx's */
@@ -205,6 +215,13 @@ zk_status   zk_rl_count(zk_rl* rl, uint64_t* items, uint64_t* dropped);
 /* every link whose child service is `server` (host arrays of cap entries; all NULL: *n = the count) */
 zk_status   zk_rl_server_links(zk_rl* rl, uint32_t server, uint32_t* parent, int64_t* duration,
                                uint64_t* trace_id, uint64_t cap, uint64_t* n);
+/* the links whose child service is `server` and whose rpc id (span-name id of the child span, 0 = no
+ * name) is `rpc`; ZK_RL_ANY_RPC: every rpc, which is zk_rl_server_links. Two-phase like it (all four
+ * arrays NULL: *n = the count), rows ordered by (parent, duration, traceId, rpc); rpc_out (optional)
+ * receives each row's id. An rpc above 65535 other than ZK_RL_ANY_RPC is ZK_ERR_INVALID_ARG. */
+#define ZK_RL_ANY_RPC 0xFFFFFFFFu
+zk_status   zk_rl_server_rpc_links(zk_rl* rl, uint32_t server, uint32_t rpc, uint32_t* parent, int64_t* duration,
+                                   uint64_t* trace_id, uint32_t* rpc_out, uint64_t cap, uint64_t* n);
 
 #ifdef __cplusplus
 }

@@ -171,6 +171,32 @@ JNIEXPORT jlongArray JNICALL FN(rlServerLinks)(JNIEnv* env, jobject self, jlong 
     return out;
 }
 
+/* the rows of (server, rpc) as 4 longs each (parent, duration, traceId, rpc id), ordered by (parent,
+   duration, traceId, rpc); rpc = -1: every rpc (ZK_RL_ANY_RPC), 0: the rows without a name; null on error */
+JNIEXPORT jlongArray JNICALL FN(rlServerRpcLinks)(JNIEnv* env, jobject self, jlong rl, jint server, jint rpc) {
+    const uint32_t r = rpc < 0 ? ZK_RL_ANY_RPC : (uint32_t)rpc;
+    uint64_t n = 0;
+    if (zk_rl_server_rpc_links(RL(rl), (uint32_t)server, r, NULL, NULL, NULL, NULL, 0, &n) != ZK_OK) return NULL;
+    uint32_t* par = (uint32_t*)malloc((n ? n : 1) * sizeof(uint32_t));
+    int64_t* dur = (int64_t*)malloc((n ? n : 1) * sizeof(int64_t));
+    uint64_t* tid = (uint64_t*)malloc((n ? n : 1) * sizeof(uint64_t));
+    uint32_t* ids = (uint32_t*)malloc((n ? n : 1) * sizeof(uint32_t));
+    jlongArray out = NULL;
+    if (par && dur && tid && ids &&
+        (n == 0 || zk_rl_server_rpc_links(RL(rl), (uint32_t)server, r, par, dur, tid, ids, n, &n) == ZK_OK)) {
+        out = (*env)->NewLongArray(env, (jsize)(4 * n));
+        for (uint64_t i = 0; out && i < n; ++i) {
+            const jlong row[4] = {(jlong)par[i], (jlong)dur[i], (jlong)tid[i], (jlong)ids[i]};
+            (*env)->SetLongArrayRegion(env, out, (jsize)(4 * i), 4, row);
+        }
+    }
+    free(par);
+    free(dur);
+    free(tid);
+    free(ids);
+    return out;
+}
+
 /* ---- ingest --------------------------------------------------------------------------------------- */
 JNIEXPORT jlong JNICALL FN(ingestCreate)(JNIEnv* env, jobject self) {
     zk_ingest* g = NULL;

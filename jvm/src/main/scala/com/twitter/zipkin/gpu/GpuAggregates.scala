@@ -29,6 +29,7 @@ class Dictionary {
     if (got != null) got.intValue else { ids.put(name, names.size); names += name; names.size - 1 }
   }
   def name(id: Int): String = synchronized { names(id) }
+  def contains(name: String): Boolean = ids.containsKey(name)
   def size: Int = synchronized { names.size }
 }
 

@@ -16,9 +16,14 @@
  *   getSpanDurations          Map(client -> every call's duration in us, ascending)
  *   getServiceNamesToTraceIds Map(client -> the calls' distinct trace ids, ascending)
  * and an unknown window or server name gives an empty map, as NullRealtimeAggregates does.
- * rpcName is not a key: the 48-B record carries no span name (the dependency job never reads one),
- * so both cover every rpc of the server; the web UI passes spanName.getOrElse("")
- * (Handlers.scala:83-104). `services` numbers the services (the device keys rows by id); a span naming
+ * rpcName is a key: SpanRecords.put writes the span's name id (this store's span-name dictionary id + 1;
+ * 0 for "" and "Unknown", the names Span.mergeSpan never selects) into bits 16..31 of the record's flags,
+ * the device keeps the largest id of a merged span's fragments with its row, and the query filters on it:
+ *   ""                    every rpc -- the web UI passes spanName.getOrElse("") (Handlers.scala:83-104)
+ *   "Unknown"             the rows whose span has no name (id 0)
+ *   a name seen so far    only that rpc's rows (zk_rl_server_rpc_links, filtered on the device)
+ *   any other name        an empty map
+ * `services` numbers the services (the device keys rows by id); a span naming
  * a service outside it fails its batch.
  */
 package com.twitter.zipkin.gpu
@@ -36,7 +41,8 @@ class GpuRealtimeAggregates(
   windowUs: Long = 3600L * 1000 * 1000,
   keep: Int = 24,
   device: Int = 0,
-  pool: FuturePool = FuturePool.unboundedPool
+  pool: FuturePool = FuturePool.unboundedPool,
+  rpcs: Dictionary = new Dictionary  // span names; accumulate adds the names it meets
 ) extends RealtimeAggregates {
   require(services.nonEmpty && windowUs > 0 && keep > 0)
   private[this] val names = new Dictionary
@@ -74,7 +80,7 @@ class GpuRealtimeAggregates(
   /** one batch of whole traces, its spans in any order, into the window of timestampUs */
   def accumulate(spans: Seq[Span], timestampUs: Long): Future[Unit] = pool {
     val c = new Columns(spans.size)
-    spans.foreach(put(c, _, names))
+    spans.foreach(put(c, _, names, Some(rpcs)))
     require(names.size == S, "a span names a service outside the store's list")
     val win = window(timestampUs, create = true).get
     win.synchronized {
@@ -83,22 +89,32 @@ class GpuRealtimeAggregates(
     }
   }
 
-  /** the server's rows (parent, duration, traceId) in the window of ts, or None */
-  private[this] def rows(ts: Time, server: String): Option[Array[Long]] = {
+  /** rpcName -> the rpc id to select: -1 every rpc, 0 the rows without a name; None: an unknown name */
+  private[this] def rpcId(rpcName: String): Option[Int] = rpcName match {
+    case ""        => Some(-1)
+    case "Unknown" => Some(0)
+    case n         => if (rpcs.contains(n)) Some(rpcs.id(n) + 1) else None
+  }
+
+  /** the rows of (server, rpc) as (parent, duration, traceId) triples in the window of ts, or None */
+  private[this] def rows(ts: Time, server: String, rpcName: String): Option[Array[Long]] = {
     val id = services.indexOf(server)
     if (id < 0) None
-    else window(ts.inMicroseconds, create = false).map { win =>
-      win.synchronized {
-        val r = ZkNative.rlServerLinks(win.rl, id)
-        if (r == null) throw new IllegalStateException(s"zk_rl_server_links: ${ZkNative.rlLastError(win.rl)}")
-        r
+    else rpcId(rpcName).flatMap { rpc =>
+      window(ts.inMicroseconds, create = false).map { win =>
+        win.synchronized {
+          val r = ZkNative.rlServerRpcLinks(win.rl, id, rpc)
+          if (r == null) throw new IllegalStateException(s"zk_rl_server_rpc_links: ${ZkNative.rlLastError(win.rl)}")
+          // (parent, duration, traceId, rpc) quadruples -> the triples the two queries read
+          Array.tabulate(r.length / 4 * 3)(i => r(i / 3 * 4 + i % 3))
+        }
       }
     }
   }
 
   def getSpanDurations(timeStamp: Time, serverServiceName: String, rpcName: String): Future[Map[String, List[Long]]] =
     pool {
-      rows(timeStamp, serverServiceName) match {
+      rows(timeStamp, serverServiceName, rpcName) match {
         case None => Map.empty[String, List[Long]]
         case Some(r) =>
           // rows come ordered by (parent, duration): each client's list is ascending already
@@ -110,7 +126,7 @@ class GpuRealtimeAggregates(
 
   def getServiceNamesToTraceIds(timeStamp: Time, serverServiceName: String, rpcName: String): Future[Map[String, List[Long]]] =
     pool {
-      rows(timeStamp, serverServiceName) match {
+      rows(timeStamp, serverServiceName, rpcName) match {
         case None => Map.empty[String, List[Long]]
         case Some(r) =>
           (0 until r.length / 3).groupBy(i => r(3 * i).toInt).map { case (p, is) =>

@@ -22,8 +22,10 @@ object SpanRecords {
     val firstTs = direct(n, 8); val lastTs = direct(n, 8); val serviceId = direct(n, 4); val flags = direct(n, 4)
   }
 
-  /** the record of one stored fragment (SURVEY.md Appendix A.1; zkagg.h ZK_F_*) */
-  def put(c: Columns, s: Span, names: Dictionary): Unit = {
+  /** the record of one stored fragment (SURVEY.md Appendix A.1; zkagg.h ZK_F_*). With `rpcs`, bits
+    * 16..31 of flags carry the span-name id: dictionary id + 1, or 0 for the names mergeSpan never selects
+    * ("" and "Unknown", Span.scala:153-158). At most 65535 names. */
+  def put(c: Columns, s: Span, names: Dictionary, rpcs: Option[Dictionary] = None): Unit = {
     val ts = s.annotations.map(_.timestamp)
     def host(vals: Seq[String]) =
       s.annotations.find(a => vals.contains(a.value) && a.host.isDefined).flatMap(_.host).map(_.serviceName)
@@ -36,6 +38,11 @@ object SpanRecords {
     for ((v, shift) <- Seq(Constants.ClientSend -> 8, Constants.ClientRecv -> 10, Constants.ServerRecv -> 12,
                            Constants.ServerSend -> 14))
       f |= math.min(2, s.annotations.count(_.value == v)) << shift
+    for (d <- rpcs if s.name != "" && s.name != "Unknown") {
+      val id = d.id(s.name) + 1
+      require(id <= 0xFFFF, "more than 65535 span names")
+      f |= id << 16
+    }
     c.traceId.putLong(s.traceId); c.spanId.putLong(s.id); c.parentId.putLong(s.parentId.getOrElse(0L))
     c.firstTs.putLong(if (ts.nonEmpty) ts.min else 0L); c.lastTs.putLong(if (ts.nonEmpty) ts.max else 0L)
     c.serviceId.putInt(svc); c.flags.putInt(f)

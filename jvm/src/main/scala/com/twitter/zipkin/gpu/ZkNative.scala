@@ -77,6 +77,10 @@ object ZkNative {
   /** the rows whose child (server) service is `server`: (parent, duration us, traceId) triples ordered
     * by (parent, duration, traceId); null on error */
   @native def rlServerLinks(rl: Long, server: Int): Array[Long]
+  /** the rows of (server, rpc): (parent, duration us, traceId, rpc id) quadruples ordered by (parent,
+    * duration, traceId, rpc). rpc is the server span's name id (SpanRecords.put: dictionary id + 1; 0 = the
+    * rows without a name), -1 = every rpc; the filter runs on the device. null on error */
+  @native def rlServerRpcLinks(rl: Long, server: Int, rpc: Int): Array[Long]
 
   // ---- ingest (zkingest.h) -----------------------------------------------------------------------
   @native def ingestCreate(): Long

@@ -173,6 +173,7 @@ int main(int argc, char** argv) {
         for (const auto& c : corpus) b.add(c);
         decoded += decode(g, b, codec, 0);
         decoded += decode(g, b, codec, ZK_INGEST_STRICT);
+        decoded += decode(g, b, codec, ZK_INGEST_SPAN_NAMES);  // the span-name dictionary
     }
     // large batches: the decoder's thread pool (contiguous ranges, one ordered commit), clean and
     // with mutated fragments spread over the ranges, against the one-thread decode
@@ -185,6 +186,8 @@ int main(int argc, char** argv) {
         for (uint32_t codec = 0; codec < 2; ++codec) {
             decoded += decode(g, b, codec, 0);
             decoded += decode(g, b, codec, ZK_INGEST_ONE_THREAD);
+            decoded += decode(g, b, codec, ZK_INGEST_SPAN_NAMES);
+            decoded += decode(g, b, codec, ZK_INGEST_SPAN_NAMES | ZK_INGEST_ONE_THREAD);
             decoded += decode(g, b, codec, ZK_INGEST_STRICT);
         }
     }

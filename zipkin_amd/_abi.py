@@ -37,6 +37,8 @@ ZK_F_CS_SHIFT = 8
 ZK_F_CR_SHIFT = 10
 ZK_F_SR_SHIFT = 12
 ZK_F_SS_SHIFT = 14
+ZK_F_NAME_SHIFT = 16  # bits 16..31: the fragment's span-name id, 0 = no name
+ZK_F_NAME_MASK = 0xFFFF
 
 ZK_BATCH_DEVICE_PTRS = 1 << 0
 ZK_BATCH_TRACE_CLUSTERED = 1 << 1
@@ -199,6 +201,7 @@ class zk_rl_config(C.Structure):
 
 ZK_RT_WITH_DEPS = 0
 ZK_RT_ONLY = 1
+ZK_RL_ANY_RPC = 0xFFFFFFFF
 
 
 class zk_ingest_items(C.Structure):
@@ -218,6 +221,7 @@ ZK_CODEC_THRIFT = 0
 ZK_CODEC_SNAPPY_THRIFT = 1
 ZK_INGEST_STRICT = 1
 ZK_INGEST_ONE_THREAD = 2
+ZK_INGEST_SPAN_NAMES = 4
 
 
 class zk_moments(C.Structure):
@@ -305,6 +309,7 @@ _SIGNATURES = [
     ("zk_rl_bind", C.c_int, [_P, _P]),
     ("zk_rl_count", C.c_int, [_P, _U64P, _U64P]),
     ("zk_rl_server_links", C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint64, _U64P]),
+    ("zk_rl_server_rpc_links", C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_uint64, _U64P]),
     # include/zkcomm.h: RCCL communicator and the multi-GPU merges
     ("zk_comm_unique_id", C.c_int, [_P, C.c_uint64]),
     ("zk_comm_create", C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(_P)]),
@@ -326,6 +331,9 @@ _SIGNATURES = [
     ("zk_ingest_num_services", C.c_int, [_P, _U32P]),
     ("zk_ingest_service_id", C.c_int, [_P, C.c_char_p, C.c_uint64, _U32P]),
     ("zk_ingest_service_name", C.c_int, [_P, C.c_uint32, C.c_char_p, C.c_uint64, _U64P]),
+    ("zk_ingest_num_span_names", C.c_int, [_P, _U32P]),
+    ("zk_ingest_span_name_id", C.c_int, [_P, C.c_char_p, C.c_uint64, _U32P]),
+    ("zk_ingest_span_name", C.c_int, [_P, C.c_uint32, C.c_char_p, C.c_uint64, _U64P]),
     ("zk_ingest_string", C.c_int, [_P, C.c_uint64, C.c_char_p, C.c_uint64, _U64P]),
     ("zk_hash_string", C.c_uint64, [C.c_char_p, C.c_uint64]),
     ("zk_snappy_uncompress", C.c_int, [_P, C.c_uint64, _P, C.c_uint64, _U64P]),

@@ -324,6 +324,11 @@ class _DeviceLinkWindow:
         self.ctx.sync()
         return self.rl.server_links(server)
 
+    def server_rpc_links(self, server: int, rpc: int):
+        """the server's rows of one rpc id (0: the rows without a name), filtered on the device"""
+        self.ctx.sync()
+        return self.rl.server_rpc_links(server, rpc)[:3]
+
     def close(self) -> None:
         self.rl.close()
         self.ctx.close()
@@ -344,16 +349,29 @@ class GpuRealtimeAggregates(RealtimeAggregates):
       getServiceNamesToTraceIds(t, server, rpc) {client: the calls' distinct trace ids, ascending,
                                                  as signed 64-bit Longs}
 
-    rpcName is not a key: the 48-B record carries no span name (the dependency job never reads
-    one), so both answers cover every rpc of the server; the web UI passes spanName.getOrElse("")
-    (Handlers.scala:83-104). `window_factory(num_services)` builds a window (default: the device);
-    the CPU tests pass the oracle's."""
+    rpcName is a key when the store has a span-name dictionary (`rpcs`): a row's rpc is the name of
+    the server (child) span, carried as dictionary id + 1 in bits 16..31 of the record's flags
+    (SpanColumns.set_name_ids; the host decoder writes them with ZK_INGEST_SPAN_NAMES), the merged
+    span taking the largest id of its fragments. Then
+      ""                     every rpc -- what the web UI passes for no selected span name
+                             (spanName.getOrElse(""), Handlers.scala:83-104); the window is asked
+                             server_links(server), exactly as without a dictionary
+      "Unknown"              the rows whose span has no name (id 0: "", "Unknown" or absent, the names
+                             Span.mergeSpan never selects)
+      a name of `rpcs`       only that rpc's rows, selected on the device (server_rpc_links)
+      any other name         {}
+    Without `rpcs` the argument is ignored and both answers cover every rpc of the server.
+    `window_factory(num_services)` builds a window (default: the device); the CPU tests pass the
+    oracle's. The number of services is fixed when the store is constructed, as in the JVM class: a
+    query for a service added to the dictionary later answers {}."""
 
     def __init__(self, services: Dictionary, *, window_us: int = 3_600_000_000, keep: int = 24, device: int = 0,
-                 window_factory=None):
+                 window_factory=None, rpcs: Optional[Dictionary] = None):
         if window_us <= 0 or keep <= 0:
             raise ValueError("window_us and keep must be positive")
         self.services = services
+        self.rpcs = rpcs
+        self._num_services = max(1, len(services))
         self.window_us = int(window_us)
         self.keep = int(keep)
         self._factory = window_factory or (lambda S: _DeviceLinkWindow(S, device))
@@ -363,7 +381,7 @@ class GpuRealtimeAggregates(RealtimeAggregates):
         w = int(timestamp_us) // self.window_us
         win = self._windows.get(w)
         if win is None and create:
-            win = self._factory(max(1, len(self.services)))
+            win = self._factory(self._num_services)
             self._windows[w] = win
             for old in sorted(self._windows)[:-self.keep]:  # the oldest windows leave the store
                 self._windows.pop(old).close()
@@ -373,14 +391,23 @@ class GpuRealtimeAggregates(RealtimeAggregates):
         """One batch of span fragments (service ids from `services`) into the window of timestamp_us."""
         self._window(timestamp_us, True).add(cols, clustered)
 
-    def _rows(self, timeStamp: int, serverServiceName: str):
+    def _rows(self, timeStamp: int, serverServiceName: str, rpcName: str):
         win = self._window(timeStamp, False)
         if win is None or serverServiceName not in self.services:
             return None
-        return win.server_links(self.services.id(serverServiceName))
+        server = self.services.id(serverServiceName)
+        if server >= self._num_services:  # a service the dictionary got after the store was built
+            return None
+        if self.rpcs is None or rpcName == "":
+            return win.server_links(server)
+        if rpcName == "Unknown":
+            return win.server_rpc_links(server, 0)
+        if rpcName not in self.rpcs:
+            return None
+        return win.server_rpc_links(server, self.rpcs.id(rpcName) + 1)
 
     def getSpanDurations(self, timeStamp: int, serverServiceName: str, rpcName: str) -> Dict[str, List[int]]:
-        rows = self._rows(timeStamp, serverServiceName)
+        rows = self._rows(timeStamp, serverServiceName, rpcName)
         if rows is None:
             return {}
         par, dur, _ = rows
@@ -390,7 +417,7 @@ class GpuRealtimeAggregates(RealtimeAggregates):
         return out
 
     def getServiceNamesToTraceIds(self, timeStamp: int, serverServiceName: str, rpcName: str) -> Dict[str, List[int]]:
-        rows = self._rows(timeStamp, serverServiceName)
+        rows = self._rows(timeStamp, serverServiceName, rpcName)
         if rows is None:
             return {}
         par, _, tid = rows

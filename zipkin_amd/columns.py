@@ -51,6 +51,24 @@ class SpanColumns:
     def take(self, idx) -> "SpanColumns":
         return SpanColumns(*[np.ascontiguousarray(getattr(self, k)[idx]) for k, _ in COLUMNS])
 
+    def name_ids(self) -> np.ndarray:
+        """The span-name id of every fragment: bits 16..31 of flags (0 = no name, else the span-name
+        dictionary id plus one; include/zkagg.h ZK_F_NAME_SHIFT)."""
+        return (self.flags >> np.uint32(_abi.ZK_F_NAME_SHIFT)).astype(np.uint32)
+
+    def set_name_ids(self, ids) -> None:
+        """Write the span-name ids (0..65535) into bits 16..31 of flags; the low half is kept."""
+        ids = np.asarray(ids, dtype=np.int64)
+        if ids.shape != self.flags.shape or (len(ids) and (ids.min() < 0 or ids.max() > _abi.ZK_F_NAME_MASK)):
+            raise ValueError("one span-name id in 0..65535 per record")
+        self.flags[:] = (self.flags & np.uint32(0xFFFF)) | (ids.astype(np.uint32) << np.uint32(_abi.ZK_F_NAME_SHIFT))
+
+    def without_names(self) -> "SpanColumns":
+        """A copy whose flags keep only the low 16 bits (every name id 0)."""
+        out = self.take(slice(None))
+        out.flags = np.ascontiguousarray(out.flags & np.uint32(0xFFFF))
+        return out
+
     def validate(self) -> None:
         n = len(self)
         for k, dt in COLUMNS:

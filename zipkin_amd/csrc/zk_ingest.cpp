@@ -208,11 +208,15 @@ struct BinAnn {
 struct SpanT {
     int64_t trace_id = 0, id = 0, parent_id = 0;
     bool has_parent = false, has_name = false;
+    const char* name = nullptr;  // Span.name (valid while the fragment's bytes are)
+    uint32_t name_len = 0;
     std::vector<Ann> anns;
     std::vector<BinAnn> banns;
     void clear() {
         trace_id = id = parent_id = 0;
         has_parent = has_name = false;
+        name = nullptr;
+        name_len = 0;
         anns.clear();
         banns.clear();
     }
@@ -270,9 +274,7 @@ bool read_span(Rd& r, SpanT* s) {
         if (id == 1 && t == T_I64) {
             s->trace_id = r.i64();
         } else if (id == 3 && t == T_STRING) {
-            const char* nm;
-            uint32_t l;
-            s->has_name = r.str(&nm, &l);
+            s->has_name = r.str(&s->name, &s->name_len);
         } else if (id == 4 && t == T_I64) {
             s->id = r.i64();
         } else if (id == 5 && t == T_I64) {
@@ -373,6 +375,7 @@ struct Decoded {
     uint32_t flags;
     int32_t svc_name;  // -1: no service
     uint32_t kv0, kv_n, ann0, ann_n;
+    int32_t span_name;  // ZK_INGEST_SPAN_NAMES: index into DecodeRange::span_names, -1: no name (id 0)
 };
 struct DecodeRange {
     uint64_t lo = 0, hi = 0;
@@ -381,6 +384,8 @@ struct DecodeRange {
     std::vector<std::string> names, strs;
     std::unordered_map<std::string, int32_t> name_ix;
     std::unordered_map<uint64_t, uint32_t> str_ix;
+    std::vector<std::string> span_names;  // ZK_INGEST_SPAN_NAMES: the range's distinct span names
+    std::unordered_map<std::string, int32_t> span_name_ix;
     uint64_t rejected = 0;
     uint64_t err_index = UINT64_MAX;  // first fragment that fails the batch (strict / bad offsets)
     zk_status err_status = ZK_OK;
@@ -393,6 +398,18 @@ struct DecodeRange {
         const int32_t ix = (int32_t)names.size();
         name_ix.emplace(s, ix);
         names.push_back(std::move(s));
+        return ix;
+    }
+    // Span.name for the record's name id; "" and "Unknown" are the names mergeSpan never selects
+    // (Span.scala:153-158): no name
+    int32_t span_name(const char* p, uint32_t l) {
+        if (!p || l == 0 || (l == 7 && memcmp(p, "Unknown", 7) == 0)) return -1;
+        std::string s(p, l);
+        auto it = span_name_ix.find(s);
+        if (it != span_name_ix.end()) return it->second;
+        const int32_t ix = (int32_t)span_names.size();
+        span_name_ix.emplace(s, ix);
+        span_names.push_back(std::move(s));
         return ix;
     }
     Item item(const Host& h, const char* s, uint32_t l) {
@@ -411,7 +428,7 @@ struct DecodeRange {
 };
 
 void decode_range(const uint8_t* buf, const uint64_t* offsets, uint32_t codec, bool strict, bool want_kv,
-                  bool want_ann, DecodeRange* d) {
+                  bool want_ann, bool want_names, DecodeRange* d) {
     std::vector<uint8_t> scratch;
     SpanT s;
     std::vector<const Ann*> distinct;
@@ -498,7 +515,8 @@ void decode_range(const uint8_t* buf, const uint64_t* offsets, uint32_t codec, b
         f |= (cnt[0] << ZK_F_CS_SHIFT) | (cnt[1] << ZK_F_CR_SHIFT) | (cnt[2] << ZK_F_SR_SHIFT) | (cnt[3] << ZK_F_SS_SHIFT);
         Decoded rec{i, (uint64_t)s.trace_id, (uint64_t)s.id, s.has_parent ? (uint64_t)s.parent_id : 0ull,
                     s.anns.empty() ? 0 : first, s.anns.empty() ? 0 : last, f, svc,
-                    (uint32_t)d->kv.size(), 0u, (uint32_t)d->ann.size(), 0u};
+                    (uint32_t)d->kv.size(), 0u, (uint32_t)d->ann.size(), 0u,
+                    want_names ? d->span_name(s.name, s.name_len) : -1};
         // ---- indexer items: only spans with a last annotation (CassieSpanStore.scala:214-218) ----
         if (!s.anns.empty()) {
             if (want_kv)
@@ -610,6 +628,10 @@ struct zk_ingest {
     std::unordered_map<std::string, uint32_t> svc_ids;
     std::vector<std::string> svc_names;
     std::unordered_map<uint64_t, std::string> strings;
+    // the span-name dictionary (ZK_INGEST_SPAN_NAMES): ids in order of first appearance; a record
+    // carries id + 1, at most 65535 names
+    std::unordered_map<std::string, uint32_t> span_ids;
+    std::vector<std::string> span_names;
     std::string err;
     DecodePool pool;
 
@@ -629,6 +651,16 @@ struct zk_ingest {
         const uint32_t id = (uint32_t)svc_names.size();
         svc_ids.emplace(name, id);
         svc_names.push_back(std::move(name));
+        return id;
+    }
+    // -> id, or -1 when the dictionary is full (the name id field of a record is 16 bits, 0 = none)
+    int64_t span_name(const std::string& name) {
+        auto it = span_ids.find(name);
+        if (it != span_ids.end()) return it->second;
+        if (span_names.size() >= ZK_F_NAME_MASK) return -1;
+        const uint32_t id = (uint32_t)span_names.size();
+        span_ids.emplace(name, id);
+        span_names.push_back(name);
         return id;
     }
     void keep(uint64_t h, const std::string& s) {  // the string behind a hash (the first one seen)
@@ -698,10 +730,11 @@ zk_status zk_ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* offs
     const bool strict = (flags & ZK_INGEST_STRICT) != 0;
     const bool want_kv = items && items->kv_service && items->kv_key;
     const bool want_ann = items && items->ann_service && items->ann_value;
+    const bool want_names = (flags & ZK_INGEST_SPAN_NAMES) != 0;
     // Phase 1, in parallel over contiguous fragment ranges: decode and validate every fragment into
     // a thread-local list (names copied into the thread's own table). Phase 2, in input order on
-    // this thread: assign service ids (in order of first appearance, exactly as a one-pass decode
-    // would), write the records and items, intern the strings, stop at the first error.
+    // this thread: assign service ids and span-name ids (in order of first appearance, exactly as a
+    // one-pass decode would), write the records and items, intern the strings, stop at the first error.
     uint32_t T = std::thread::hardware_concurrency();
     T = T < 1 ? 1 : T > kIngestThreads ? kIngestThreads : T;
     if (flags & ZK_INGEST_ONE_THREAD) T = 1;
@@ -712,7 +745,7 @@ zk_status zk_ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* offs
         d.lo = n * t / T;
         d.hi = n * (t + 1) / T;
         try {
-            decode_range(buf, offsets, codec, strict, want_kv, want_ann, &d);
+            decode_range(buf, offsets, codec, strict, want_kv, want_ann, want_names, &d);
         } catch (...) {
             d.err_index = d.lo;
             d.err_status = ZK_ERR_CAPACITY;
@@ -736,6 +769,7 @@ zk_status zk_ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* offs
             if (gid[name] < 0) gid[name] = g->exact(d.names[name]);
             return (uint32_t)gid[name];
         };
+        std::vector<int64_t> ngid(d.span_names.size(), -1);  // this range's span names -> dictionary ids
         std::vector<uint8_t> kept(d.strs.size(), 0);  // strings of this range already interned
         auto keep = [&](const Item& it) {
             if (kept[it.str]) return;
@@ -746,13 +780,21 @@ zk_status zk_ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* offs
             if (r.index >= d.err_index) break;  // records after this range's first error are not committed
             uint32_t svc = 0;
             if (r.svc_name >= 0) svc = id_of(r.svc_name);
+            uint32_t name_bits = 0;
+            if (r.span_name >= 0) {
+                if (ngid[r.span_name] < 0 && (ngid[r.span_name] = g->span_name(d.span_names[r.span_name])) < 0) {
+                    g->err = "span " + std::to_string(r.index) + ": more than 65535 span names";
+                    return ZK_ERR_CAPACITY;
+                }
+                name_bits = ((uint32_t)ngid[r.span_name] + 1u) << ZK_F_NAME_SHIFT;
+            }
             o_tid[k] = r.tid;
             o_sid[k] = r.sid;
             o_pid[k] = r.pid;
             o_first[k] = r.first;
             o_last[k] = r.last;
             o_svc[k] = svc;
-            o_flags[k] = r.flags;
+            o_flags[k] = r.flags | name_bits;
             ++k;
             for (uint32_t q = r.kv0; q < r.kv0 + r.kv_n; ++q) {  // :235-241 one per binary annotation with a host
                 if (items->kv_n >= items->kv_cap) {
@@ -817,6 +859,40 @@ zk_status zk_ingest_service_name(const zk_ingest* g, uint32_t id, char* buf, uin
     if (!g || !len) return ZK_ERR_INVALID_ARG;
     if (id >= g->svc_names.size()) return ZK_ERR_SERVICE_RANGE;
     const std::string& s = g->svc_names[id];
+    *len = s.size();
+    if (!buf) return ZK_OK;
+    if (cap < s.size()) return ZK_ERR_CAPACITY;
+    memcpy(buf, s.data(), s.size());
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_ingest_num_span_names(const zk_ingest* g, uint32_t* n) {
+    ZK_GUARD_BEGIN
+    if (!g || !n) return ZK_ERR_INVALID_ARG;
+    *n = (uint32_t)g->span_names.size();
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_ingest_span_name_id(zk_ingest* g, const char* name, uint64_t len, uint32_t* id) {
+    ZK_GUARD_BEGIN
+    if (!g || !id || (!name && len)) return ZK_ERR_INVALID_ARG;
+    const int64_t v = g->span_name(std::string(name ? name : "", len));
+    if (v < 0) {
+        g->err = "more than 65535 span names";
+        return ZK_ERR_CAPACITY;
+    }
+    *id = (uint32_t)v;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_ingest_span_name(const zk_ingest* g, uint32_t id, char* buf, uint64_t cap, uint64_t* len) {
+    ZK_GUARD_BEGIN
+    if (!g || !len) return ZK_ERR_INVALID_ARG;
+    if (id >= g->span_names.size()) return ZK_ERR_INVALID_ARG;
+    const std::string& s = g->span_names[id];
     *len = s.size();
     if (!buf) return ZK_OK;
     if (cap < s.size()) return ZK_ERR_CAPACITY;

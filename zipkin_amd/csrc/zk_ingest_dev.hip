@@ -2562,6 +2562,7 @@ zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* off
     if (!g || !n_out || !n_rejected) return ZK_ERR_INVALID_ARG;
     *n_out = *n_rejected = 0;
     if (items) items->kv_n = items->ann_n = 0;
+    if (flags & ZK_INGEST_SPAN_NAMES) return dfail(g, ZK_ERR_UNSUPPORTED, "the device decoder keeps no span-name dictionary");
     const bool want_kv = items && items->kv_service && items->kv_key && items->kv_cap;
     const bool want_ann = items && items->ann_service && items->ann_value && items->ann_cap;
     if (n == 0) return ZK_OK;
@@ -2985,6 +2986,7 @@ zk_status ingest_multi(zk_ingest_dev* g, uint32_t nb, const uint8_t* const* bufs
     if (!g || !n_out || !n_rejected) return ZK_ERR_INVALID_ARG;
     *n_out = *n_rejected = 0;
     if (items) items->kv_n = items->ann_n = 0;
+    if (flags & ZK_INGEST_SPAN_NAMES) return dfail(g, ZK_ERR_UNSUPPORTED, "the device decoder keeps no span-name dictionary");
     if (nb && (!bufs || !offsets || !ns)) return dfail(g, ZK_ERR_INVALID_ARG, "null batch arrays");
     uint64_t n = 0;
     uintptr_t base = UINTPTR_MAX;

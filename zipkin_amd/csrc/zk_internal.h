@@ -131,12 +131,13 @@ struct JoinArgs {
     const uint32_t* skip_dev;
     // realtime link items (zk_rl, a bound RealtimeAggregates store), lk_key == nullptr: none. One item
     // per emitted link, at the link's own list position: key ((child * S + parent) << 40) | duration,
-    // and the child's traceId; the spill kernel appends to list `grid` (lk_spill_count, capacity
-    // lk_spill_cap items)
+    // the child's traceId and the child's merged span-name id (the maximum of its fragments' flags
+    // bits 16..31); the spill kernel appends to list `grid` (lk_spill_count, capacity lk_spill_cap items)
     uint64_t* lk_key;
     uint64_t* lk_tid;
     uint32_t* lk_spill_count;
     uint64_t lk_spill_cap;
+    uint32_t* lk_name;  // (last: the fields before it keep their kernel-argument offsets)
 };
 
 // host-side launchers (implemented in the .hip files)

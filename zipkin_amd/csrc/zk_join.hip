@@ -202,6 +202,21 @@ __device__ __forceinline__ uint32_t frag_bits(uint32_t f, uint32_t* once) {
 }
 __device__ __forceinline__ bool slot_valid(uint32_t w) { return ((w >> kSlotB) & 0xFu) == 0u; }
 
+// max of v into the 16-bit field i of an LDS array of two fields per word. There is no 16-bit LDS
+// atomic, so a compare-and-swap on the word; a field only grows, so a fragment whose id is not above
+// its leader's (a fragment that agrees with it, the normal case, or has no name) stops at the first read
+__device__ __forceinline__ void lds_max_u16(uint32_t* words, int i, uint32_t v) {
+    uint32_t* const w = &words[i >> 1];
+    const int sh = 16 * (i & 1);
+    uint32_t old = *(volatile uint32_t*)w;
+    while (((old >> sh) & 0xFFFFu) < v) {
+        const uint32_t want = (old & ~(0xFFFFu << sh)) | (v << sh);
+        const uint32_t prev = atomicCAS(w, old, want);
+        if (prev == old) break;
+        old = prev;
+    }
+}
+
 // Two consecutive elements starting at i (i even), RAW: elements at or past `lim` are garbage and
 // every consumer masks by record index. Branch-free and unmasked on purpose: a conditional tail
 // load, or a select right after the load, makes the compiler wait (vmcnt) for the load at once,
@@ -378,6 +393,10 @@ __global__ __launch_bounds__(WG, ZK_K1_WGS_PER_CU * WG / 256) void k_span_join_s
     __shared__ __align__(16) long long s_last[TILE];
     __shared__ __align__(16) uint64_t s_pid[TILE];
     __shared__ __align__(16) uint32_t s_svck[TILE];
+    // kModeLinks: the merged span-name ids (the maximum of the fragments' flags bits 16..31), two
+    // 16-bit ids per word (record j in half j & 1 of word j >> 1): 1 KB. A u32 per record would put
+    // this instantiation 136 B over the 40 KB of four workgroups per CU (join_geometry)
+    __shared__ __align__(16) uint32_t s_name[(MODE & kModeLinks) ? TILE / 2 : 1];
     __shared__ __align__(16) uint32_t s_ht[H];
     __shared__ __align__(16) uint64_t s_mask[NWORD];
     __shared__ uint32_t s_stat[ST_N];
@@ -566,6 +585,8 @@ __global__ __launch_bounds__(WG, ZK_K1_WGS_PER_CU * WG / 256) void k_span_join_s
             *reinterpret_cast<ulonglong2*>(&s_last[j0]) = make_ulonglong2(v_last[0], v_last[1]);
             *reinterpret_cast<ulonglong2*>(&s_pid[j0]) = make_ulonglong2(v_pid[0], v_pid[1]);
             *reinterpret_cast<uint2*>(&s_svck[j0]) = make_uint2(r_svck[0], r_svck[1]);
+            if constexpr (LINKS)  // record 2t's id in the low half of word t, record 2t+1's in the high half
+                s_name[tid] = (cur.flags[0] >> ZK_F_NAME_SHIFT) | (cur.flags[1] & (ZK_F_NAME_MASK << ZK_F_NAME_SHIFT));
         }
         ZK_PHASE_SYNC(2);  // (the hash table is empty here: cleared once, then by its leaders)
 
@@ -635,6 +656,7 @@ __global__ __launch_bounds__(WG, ZK_K1_WGS_PER_CU * WG / 256) void k_span_join_s
                 }
                 if (r_svck[e] != kSvcNone) atomicMin(&s_svck[L], r_svck[e]);
                 if (f & ZK_F_HAS_PARENT) atomicMin((unsigned long long*)&s_pid[L], (unsigned long long)cur.pid[e]);
+                if constexpr (LINKS) lds_max_u16(s_name, L, f >> ZK_F_NAME_SHIFT);
                 uint32_t once;
                 const uint32_t bits = frag_bits(f, &once);
                 uint32_t* const wp = &s_ht[r_slot[e]];
@@ -650,6 +672,7 @@ __global__ __launch_bounds__(WG, ZK_K1_WGS_PER_CU * WG / 256) void k_span_join_s
         uint64_t r_link[2], r_item[2];
         uint32_t r_isvc[2];
         uint64_t r_lkey[2] = {0, 0};  // kModeLinks: the link's realtime item key (child-major cell | d)
+        uint32_t r_lname[2] = {0, 0};  // kModeLinks: the child span's merged name id
         // lm: bit e set when element e emits a link. Not read off r_link: the link of cell 2^24 - 1 with
         // d = 2^40 - 1 (S = 4096) is the all-ones word
         uint32_t lm = 0, ni = 0;
@@ -724,7 +747,10 @@ __global__ __launch_bounds__(WG, ZK_K1_WGS_PER_CU * WG / 256) void k_span_join_s
             }
             const uint64_t cell = (uint64_t)(sp & kSvcIdMask) * a.S + (sL & kSvcIdMask);
             r_link[e] = (cell << 40) | d;
-            if constexpr (LINKS) r_lkey[e] = (((uint64_t)(sL & kSvcIdMask) * a.S + (sp & kSvcIdMask)) << 40) | d;
+            if constexpr (LINKS) {
+                r_lkey[e] = (((uint64_t)(sL & kSvcIdMask) * a.S + (sp & kSvcIdMask)) << 40) | d;
+                r_lname[e] = (s_name[j >> 1] >> (16 * (j & 1))) & ZK_F_NAME_MASK;
+            }
             if (a.nb) atomicAdd(&s_hist[cell >> a.cb_shift], 1u);
             lm |= 1u << e;
         }
@@ -757,7 +783,9 @@ __global__ __launch_bounds__(WG, ZK_K1_WGS_PER_CU * WG / 256) void k_span_join_s
         }
         if constexpr (JOIN) {
             // exactly two stores per thread on every path (absent links go to the list's trash
-            // slot), so the loop-end wait for the prefetched window can count them: vmcnt(2)
+            // slot), so the loop-end wait for the prefetched window can count them: vmcnt(2). With
+            // kModeLinks each of the two carries three item stores (key, traceId, name id), eight in
+            // all, as unconditional as the link stores: the count stays a constant of the instantiation
             uint32_t pos = lbase;
 #if defined(ZK_K1_DIAG_TRASHONLY)
             out[trash] = r_link[0];
@@ -771,6 +799,7 @@ __global__ __launch_bounds__(WG, ZK_K1_WGS_PER_CU * WG / 256) void k_span_join_s
                 if constexpr (LINKS) {  // the realtime link item at the link's own position
                     a.lk_key[(uint64_t)blockIdx.x * a.link_stride + at] = r_lkey[e];
                     a.lk_tid[(uint64_t)blockIdx.x * a.link_stride + at] = cur.tid[e];
+                    a.lk_name[(uint64_t)blockIdx.x * a.link_stride + at] = r_lname[e];
                 }
                 pos += v ? 1u : 0u;
             }
@@ -852,6 +881,7 @@ struct SpillScratch {
     uint64_t* cntB;  // ss | npar << 21
     uint64_t* pid;
     uint32_t* svck;
+    uint32_t* name;  // merged span-name id (written and read only with realtime link items)
     uint32_t* ht;
 };
 
@@ -879,6 +909,8 @@ __host__ __device__ inline SpillScratch spill_carve(uint8_t* base, uint32_t L) {
     s.pid = (uint64_t*)p;
     p += 8ull * L;
     s.svck = (uint32_t*)p;
+    p += 4ull * L + 4ull * (L & 1);
+    s.name = (uint32_t*)p;
     p += 4ull * L + 4ull * (L & 1);
     s.ht = (uint32_t*)p;
     return s;
@@ -949,6 +981,7 @@ __global__ __launch_bounds__(kSpillWG) void k_span_join_spill(JoinArgs a) {
             st_sc(&sc.cntB[j], B);
             st_sc(&sc.pid[j], (uint64_t)((f & ZK_F_HAS_PARENT) ? (a.join ? a.c.parent_id[gi] : 0ull) : ~0ull));
             st_sc(&sc.svck[j], svc_key(f, a.c.service_id[gi], a.S, &rerr));
+            if (a.lk_key) st_sc(&sc.name[j], f >> ZK_F_NAME_SHIFT);
             if (rerr) st.inc(ST_SVC_RANGE);
         }
         for (uint32_t x = threadIdx.x; x < H; x += kSpillWG) st_sc(&sc.ht[x], 0u);
@@ -994,6 +1027,7 @@ __global__ __launch_bounds__(kSpillWG) void k_span_join_spill(JoinArgs a) {
                 if (sk != kSvcNone) atomicMin(&sc.svck[Ld], sk);
                 if (f & ZK_F_HAS_PARENT)
                     atomicMin((unsigned long long*)&sc.pid[Ld], (unsigned long long)(a.join ? a.c.parent_id[gi] : 0ull));
+                if (a.lk_key && (f >> ZK_F_NAME_SHIFT)) atomicMax(&sc.name[Ld], f >> ZK_F_NAME_SHIFT);
             }
         }
         __syncthreads();
@@ -1070,6 +1104,7 @@ __global__ __launch_bounds__(kSpillWG) void k_span_join_spill(JoinArgs a) {
                                 const uint64_t at = (uint64_t)a.grid * a.link_stride + q;
                                 a.lk_key[at] = (((uint64_t)(sL & kSvcIdMask) * a.S + (spv & kSvcIdMask)) << 40) | d;
                                 a.lk_tid[at] = a.c.trace_id[gi];
+                                a.lk_name[at] = ld_sc(&sc.name[Ld]);
                             }
                         }
                     }
@@ -1501,7 +1536,7 @@ constexpr int kTile = 2 * kTileWG;
 
 uint64_t spill_scratch_bytes_per_wg(uint32_t max_trace) {
     const uint64_t L = max_trace;
-    uint64_t b = 8ull * L * 6 + 4ull * L + 4ull * (L & 1) + 4ull * spill_ht_slots(max_trace);
+    uint64_t b = 8ull * L * 6 + 2 * (4ull * L + 4ull * (L & 1)) + 4ull * spill_ht_slots(max_trace);
     return (b + 255) & ~255ull;
 }
 

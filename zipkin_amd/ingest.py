@@ -44,13 +44,14 @@ class SpanDecoder:
             raise _abi.ZkError(st, self._L.zk_ingest_last_error(self._h).decode() or _abi.status_str(st))
 
     def decode(self, blobs, *, snappy: bool = True, strict: bool = True, items: bool = False,
-               item_cap: int | None = None, one_thread: bool = False):
+               item_cap: int | None = None, one_thread: bool = False, span_names: bool = False):
         """Decode stored fragments: a sequence of bytes objects (one per fragment), or the packed
         form (buf uint8[total], offsets uint64[n + 1]) -- fragment i is buf[offsets[i]:offsets[i+1]].
         Returns (SpanColumns, rejected) or, with items=True, (SpanColumns, rejected,
         (kv_service, kv_key), (ann_service, ann_value)). one_thread: decode on the calling thread
         only (ZK_INGEST_ONE_THREAD; the default splits large batches over up to 16 threads, with the
-        same results)."""
+        same results). span_names: keep the span-name dictionary and write every record's name id
+        (id + 1; 0 for "" and "Unknown") into bits 16..31 of flags (ZK_INGEST_SPAN_NAMES)."""
         if isinstance(blobs, tuple) and len(blobs) == 2 and isinstance(blobs[0], np.ndarray):
             buf = np.ascontiguousarray(blobs[0], dtype=np.uint8)
             offsets = np.ascontiguousarray(blobs[1], dtype=np.uint64)
@@ -74,6 +75,7 @@ class SpanDecoder:
                                       arrs[2].ctypes.data, arrs[3].ctypes.data, cap, 0)
         codec = _abi.ZK_CODEC_SNAPPY_THRIFT if snappy else _abi.ZK_CODEC_THRIFT
         flags = (_abi.ZK_INGEST_STRICT if strict else 0) | (_abi.ZK_INGEST_ONE_THREAD if one_thread else 0)
+        flags |= _abi.ZK_INGEST_SPAN_NAMES if span_names else 0
         ab = cols.abi()
         self._check(self._L.zk_ingest_spans(self._h, buf.ctypes.data, offsets.ctypes.data, n, codec, flags,
                                             C.byref(ab), C.byref(nout), C.byref(nrej),
@@ -106,6 +108,29 @@ class SpanDecoder:
 
     def service_names(self) -> List[str]:
         return [self.service_name(i) for i in range(self.num_services)]
+
+    @property
+    def num_span_names(self) -> int:
+        n = C.c_uint32()
+        self._check(self._L.zk_ingest_num_span_names(self._h, C.byref(n)))
+        return int(n.value)
+
+    def span_name_id(self, name: str) -> int:
+        """The span-name dictionary id of `name` (added if new); a record's flags carry id + 1."""
+        b = name.encode()
+        i = C.c_uint32()
+        self._check(self._L.zk_ingest_span_name_id(self._h, b, len(b), C.byref(i)))
+        return int(i.value)
+
+    def span_name(self, i: int) -> str:
+        ln = C.c_uint64()
+        self._check(self._L.zk_ingest_span_name(self._h, i, None, 0, C.byref(ln)))
+        buf = C.create_string_buffer(max(1, ln.value))
+        self._check(self._L.zk_ingest_span_name(self._h, i, buf, ln.value, C.byref(ln)))
+        return buf.raw[: ln.value].decode("utf-8", "surrogateescape")
+
+    def span_names(self) -> List[str]:
+        return [self.span_name(i) for i in range(self.num_span_names)]
 
     def string(self, h: int) -> str:
         ln = C.c_uint64()

@@ -166,8 +166,8 @@ class RtSketch:
 
 class RealtimeLinks:
     """The realtime link store (zk_rl_*): every join row (parent service, child service, child
-    duration, traceId) of the dependency path since the last reset, kept in HBM and queried by
-    server (child) service -- the state behind RealtimeAggregates (GpuRealtimeAggregates below in
+    duration, traceId, rpc = the child span's name id) of the dependency path since the last reset,
+    kept in HBM and queried by server (child) service and rpc -- the state behind RealtimeAggregates (GpuRealtimeAggregates below in
     zipkin_amd/aggregates.py). Bound to a DepsContext, K1 writes the rows beside its links."""
 
     def __init__(self, num_services: int, *, device: int = 0, stream: int | None = None):
@@ -239,3 +239,23 @@ class RealtimeLinks:
             self._check(self._L.zk_rl_server_links(self._h, server, par.ctypes.data, dur.ctypes.data, tid.ctypes.data,
                                                    m, C.byref(n)))
         return par[:m], dur[:m], tid[:m]
+
+    def server_rpc_links(self, server: int, rpc: int | None = None):
+        """(parent ids uint32, durations int64 us, traceIds uint64, rpc ids uint32) of the rows whose
+        child service is `server` and whose rpc id -- the child span's name id, bits 16..31 of the
+        record flags, 0 = no name -- is `rpc` (None: any rpc), ordered by (parent, duration, traceId,
+        rpc). The filter runs on the device (zk_rl_server_rpc_links)."""
+        r = _abi.ZK_RL_ANY_RPC if rpc is None else int(rpc)
+        if not 0 <= r <= _abi.ZK_RL_ANY_RPC:
+            raise _abi.ZkError(_abi.ZK_ERR_INVALID_ARG, "rpc name id out of range")
+        n = C.c_uint64()
+        self._check(self._L.zk_rl_server_rpc_links(self._h, server, r, None, None, None, None, 0, C.byref(n)))
+        m = int(n.value)
+        par = np.zeros(max(1, m), np.uint32)
+        dur = np.zeros(max(1, m), np.int64)
+        tid = np.zeros(max(1, m), np.uint64)
+        ids = np.zeros(max(1, m), np.uint32)
+        if m:
+            self._check(self._L.zk_rl_server_rpc_links(self._h, server, r, par.ctypes.data, dur.ctypes.data,
+                                                       tid.ctypes.data, ids.ctypes.data, m, C.byref(n)))
+        return par[:m], dur[:m], tid[:m], ids[:m]
