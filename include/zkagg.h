@@ -198,7 +198,8 @@ typedef struct zk_timing {
     double reduce_ms_total;
     double cluster_ms;        /* clustering pass of the last unclustered batch (0 when none) */
     double cluster_ms_total;  /* cumulative clustering-pass time */
-    double reserved[2];
+    double link_hist_ms;        /* per-link duration histogram of the last batch (zksketch.h zk_lh_*; */
+    double link_hist_ms_total;  /* cumulative; both 0 unless a handle is bound) */
 } zk_timing;
 
 /* Dense S x S output table of DependencyLink(parent=i, child=j, Moments) for cell i*S+j

@@ -14,6 +14,7 @@
  *                      limbs + the counter tail, zkagg.h) -> zk_deps_note_merged. Every rank then
  *                      finalizes the same job-wide table and reaches the same status.
  *   zk_rt_allreduce    HyperLogLog registers by u8 MAX, duration histogram bins by u32 SUM.
+ *   zk_lh_allreduce    per-link duration histogram bins by u32 SUM (and its drop counter).
  *   zk_kv_allreduce    all-gather of every rank's candidate lists, u32 SUM of the count-min
  *                      counters and u64 SUM of the totals, then zk_kv_merge_candidates: every rank
  *                      holds the same top-K lists.
@@ -57,6 +58,7 @@ const char* zk_comm_last_error(const zk_comm* comm);
 zk_status   zk_deps_allreduce(zk_ctx* ctx, zk_comm* comm, uint64_t total_records);
 zk_status   zk_rt_allreduce(zk_rt* rt, zk_comm* comm);
 zk_status   zk_kv_allreduce(zk_kv* kv, zk_comm* comm);
+zk_status   zk_lh_allreduce(zk_lh* lh, zk_comm* comm);
 
 #ifdef __cplusplus
 }

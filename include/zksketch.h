@@ -223,6 +223,66 @@ zk_status   zk_rl_server_links(zk_rl* rl, uint32_t server, uint32_t* parent, int
 zk_status   zk_rl_server_rpc_links(zk_rl* rl, uint32_t server, uint32_t rpc, uint32_t* parent, int64_t* duration,
                                    uint64_t* trace_id, uint32_t* rpc_out, uint64_t cap, uint64_t* n);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-link duration histogram: p50/p99 (any quantile) of every dependency edge.
+ *
+ * A DependencyLink carries Moments only (Dependencies.scala:34): mean, variance, skew and kurtosis of
+ * the child durations of a (parent, child) edge, but no quantile. Bound to a dependency ctx, every
+ * later zk_deps_accumulate also counts each link it emits -- the same (parent, child, child duration)
+ * rows the table sums -- into an exact histogram per edge: cell = parent * S + child (the link
+ * table's cell), bins in zk_rt's log-linear layout with m = sub_bits mantissa bits (the value itself
+ * below 2^m, else (exponent, top m mantissa bits); (41 - m) << m bins cover [0, 2^40) us). Counts are
+ * integers, so the state is independent of batch order and batch cuts and merges across traceId
+ * shards by SUM, like the table.
+ *
+ * State: u32[S * S][bins] in HBM, S * S * bins * 4 bytes, allocated once by zk_lh_create
+ * (ZK_ERR_CAPACITY when the device refuses; nothing is allocated during an accumulate, so a batch is
+ * never half applied). bins = 592 at m = 4 (the default; a bin spans <= 1/16 of its lower bound) and
+ * 4352 at m = 7: at S = 500, 592 MB and 4.35 GB; at S = 61, 8.8 MB and 64.8 MB.
+ *
+ * A link with duration >= 2^40 us is dropped by the dependency path before it reaches the histogram
+ * (zk_stats.duration_range); zk_lh_dropped reports how many were dropped while this handle was bound,
+ * since its reset. Counters are u32: the handle bounds the records accumulated since its own reset on
+ * the host (links <= records), and an accumulate that would take the bound to >= 2^32 fails with
+ * ZK_ERR_CAPACITY before any kernel of the batch is launched.
+ *
+ * Binding: the handle and the ctx agree on num_services and device (else ZK_ERR_INVALID_ARG). A ctx
+ * with a ZK_RT_ONLY sketch emits no links: binding both, in either order, is ZK_ERR_UNSUPPORTED. The
+ * handle coexists with a zk_rl store and with a ZK_RT_WITH_DEPS sketch, and leaves unclustered
+ * batches on the group join.
+ *
+ * Quantiles follow zk_rt_quantiles: nearest rank max(1, ceil(q N)), lo/hi the bounds of the bin
+ * holding it (lo <= exact <= hi), count = N = the edge's link count (the table's m0), all 0 when
+ * N = 0.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct zk_lh_config {
+    uint32_t num_services;  /* S <= 4096, the ctx's */
+    int32_t  device;
+    void*    stream;        /* hipStream_t or NULL for a private stream (the bound ctx's while bound) */
+    uint32_t sub_bits;      /* histogram mantissa bits m, 2..7; 0 = 4 */
+    uint32_t reserved[8];
+} zk_lh_config;
+
+typedef struct zk_lh zk_lh;
+
+zk_status   zk_lh_create(const zk_lh_config* cfg, zk_lh** out);
+zk_status   zk_lh_destroy(zk_lh* lh);
+const char* zk_lh_last_error(const zk_lh* lh);
+zk_status   zk_lh_reset(zk_lh* lh);
+zk_status   zk_lh_geometry(const zk_lh* lh, uint32_t* bins);   /* (41 - m) << m */
+zk_status   zk_lh_bind(zk_ctx* ctx, zk_lh* lh);                /* lh = NULL unbinds */
+/* one edge: q[nq] in [0, 1] -> host lo[nq], hi[nq] (us) and the edge's link count (may be NULL) */
+zk_status   zk_lh_quantiles(zk_lh* lh, uint32_t parent, uint32_t child, const double* q, uint32_t nq, int64_t* lo,
+                            int64_t* hi, uint64_t* count);
+/* every edge in one device pass: lo/hi host int64[S * S][nq], count host u64[S * S] (may be NULL) */
+zk_status   zk_lh_quantiles_all(zk_lh* lh, const double* q, uint32_t nq, int64_t* lo, int64_t* hi, uint64_t* count);
+/* host copy of the rows of cells [first_cell, first_cell + n_cells): out u32[n_cells][bins] */
+zk_status   zk_lh_read(zk_lh* lh, uint64_t first_cell, uint64_t n_cells, uint32_t* out);
+/* the device histogram u32[S * S][bins] for an in-place u32 SUM all-reduce across traceId shards */
+zk_status   zk_lh_partial(zk_lh* lh, void** hist, uint64_t* bytes);
+/* links dropped for a duration >= 2^40 us while bound, since reset (syncs) */
+zk_status   zk_lh_dropped(zk_lh* lh, uint64_t* duration_range);
+
 #ifdef __cplusplus
 }
 #endif

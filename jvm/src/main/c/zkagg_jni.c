@@ -197,6 +197,43 @@ JNIEXPORT jlongArray JNICALL FN(rlServerRpcLinks)(JNIEnv* env, jobject self, jlo
     return out;
 }
 
+/* ---- per-link duration histogram (zksketch.h zk_lh_*) ---- */
+#define LH(h) ((zk_lh*)(intptr_t)(h))
+
+JNIEXPORT jlong JNICALL FN(lhCreate)(JNIEnv* env, jobject self, jint S, jint dev, jint sub_bits) {
+    zk_lh_config c;
+    zk_lh* h = NULL;
+    memset(&c, 0, sizeof(c));
+    c.num_services = (uint32_t)S;
+    c.device = dev;
+    c.sub_bits = (uint32_t)sub_bits;
+    return zk_lh_create(&c, &h) == ZK_OK ? (jlong)(intptr_t)h : 0;
+}
+
+JNIEXPORT jint JNICALL FN(lhDestroy)(JNIEnv* env, jobject self, jlong lh) { return zk_lh_destroy(LH(lh)); }
+
+JNIEXPORT jint JNICALL FN(lhReset)(JNIEnv* env, jobject self, jlong lh) { return zk_lh_reset(LH(lh)); }
+
+JNIEXPORT jint JNICALL FN(lhBind)(JNIEnv* env, jobject self, jlong h, jlong lh) { return zk_lh_bind(CTX(h), LH(lh)); }
+
+/* lo / hi: S*S*nq longs, count: S*S longs (the caller sizes them from its numServices) */
+JNIEXPORT jint JNICALL FN(lhQuantilesAll)(JNIEnv* env, jobject self, jlong lh, jdoubleArray q, jlongArray lo,
+                                          jlongArray hi, jlongArray count) {
+    const jsize nq = (*env)->GetArrayLength(env, q);
+    jdouble* qp = (*env)->GetDoubleArrayElements(env, q, NULL);
+    jlong* lp = (*env)->GetLongArrayElements(env, lo, NULL);
+    jlong* hp = (*env)->GetLongArrayElements(env, hi, NULL);
+    jlong* cp = (*env)->GetLongArrayElements(env, count, NULL);
+    jint st = ZK_ERR_CAPACITY;
+    if (qp && lp && hp && cp)
+        st = zk_lh_quantiles_all(LH(lh), qp, (uint32_t)nq, (int64_t*)lp, (int64_t*)hp, (uint64_t*)cp);
+    if (qp) (*env)->ReleaseDoubleArrayElements(env, q, qp, JNI_ABORT);
+    if (lp) (*env)->ReleaseLongArrayElements(env, lo, lp, 0);
+    if (hp) (*env)->ReleaseLongArrayElements(env, hi, hp, 0);
+    if (cp) (*env)->ReleaseLongArrayElements(env, count, cp, 0);
+    return st;
+}
+
 /* ---- ingest --------------------------------------------------------------------------------------- */
 JNIEXPORT jlong JNICALL FN(ingestCreate)(JNIEnv* env, jobject self) {
     zk_ingest* g = NULL;

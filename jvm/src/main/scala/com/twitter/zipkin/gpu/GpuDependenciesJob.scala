@@ -32,6 +32,13 @@
  * ZK_ERR_SERVICE_RANGE). `services` seeds the dictionary in a fixed order (e.g. from
  * SpanStore.getAllServiceNames): a multi-GPU job needs it, because the ranks' tables are summed cell
  * by cell and so must agree on every service id -- a rank that meets a name outside the list fails.
+ *
+ * `linkQuantiles` (e.g. Seq(0.5, 0.99)): the job also binds a per-link duration histogram
+ * (zksketch.h zk_lh_*, numServices^2 x 592 u32 counters in HBM) and, after a run, `linkDurations`
+ * holds one LinkDuration per link of the record, in the record's order: for each q the bounds of the
+ * histogram bin that holds the nearest-rank quantile of the edge's child durations. A side output:
+ * zipkinDependencies.thrift has no field for it, so it travels beside the Dependencies record. (A
+ * multi-GPU job reports the rank's own part: the histogram is not exchanged here.)
  */
 package com.twitter.zipkin.gpu
 
@@ -44,12 +51,16 @@ import com.twitter.zipkin.storage.Aggregates
 
 import SpanRecords.{Columns, direct, put}
 
+/** the duration quantiles of one dependency edge: q -> (lo, hi) in us, lo <= exact quantile <= hi */
+final case class LinkDuration(parent: String, child: String, count: Long, quantiles: Map[Double, (Long, Long)])
+
 /** rank / world of a multi-GPU job and the communicator id rank 0 made (ZkNative.commUniqueId) */
 final case class GpuShard(rank: Int, world: Int, commId: Array[Byte])
 
 class GpuDependenciesJob(aggregates: Aggregates, device: Int = 0, strict: Boolean = true,
                          maxTraceRecords: Int = 0, numServices: Int = 1024, verify: Boolean = false,
-                         services: Seq[String] = Nil, shard: Option[GpuShard] = None) {
+                         services: Seq[String] = Nil, shard: Option[GpuShard] = None,
+                         linkQuantiles: Seq[Double] = Nil) {
   require(shard.isEmpty || services.nonEmpty, "a multi-GPU job needs the service list every rank numbers alike")
   require(services.size <= numServices, "more services than numServices")
 
@@ -62,12 +73,16 @@ class GpuDependenciesJob(aggregates: Aggregates, device: Int = 0, strict: Boolea
 
   private[this] def check(ctx: Long, st: Int): Unit = if (st != ZkNative.Ok) fail(ctx, st)
 
+  @volatile private[this] var durations: Seq[LinkDuration] = Nil
+  /** after a run with linkQuantiles: one entry per link of the record, in the record's order */
+  def linkDurations: Seq[LinkDuration] = durations
+
   private[this] def accumulate(ctx: Long, c: Columns, n: Long, flags: Int): Unit =
     check(ctx, ZkNative.accumulate(ctx, c.traceId, c.spanId, c.parentId, c.firstTs, c.lastTs, c.serviceId, c.flags,
       n, flags | (if (verify) ZkNative.BatchVerifyTraces else 0)))
 
   /** [all-reduce across ranks,] finalize; the Dependencies record of the whole job on every rank */
-  private[this] def finish(ctx: Long, comm: Long, names: Int => String): Option[Dependencies] = {
+  private[this] def finish(ctx: Long, comm: Long, lh: Long, names: Int => String): Option[Dependencies] = {
     if (comm != 0) check(ctx, ZkNative.depsAllreduce(ctx, comm, 0L))
     val S = numServices
     val m0 = new Array[Long](S * S); val m1 = new Array[Double](S * S); val m2 = new Array[Double](S * S)
@@ -75,12 +90,25 @@ class GpuDependenciesJob(aggregates: Aggregates, device: Int = 0, strict: Boolea
     check(ctx, ZkNative.finalizeTable(ctx, m0, m1, m2, m3, m4, present))
     val links = for (c <- 0 until S * S if present(c) != 0)
       yield DependencyLink(Service(names(c / S)), Service(names(c % S)), Moments(m0(c), m1(c), m2(c), m3(c), m4(c)))
+    if (lh != 0) {
+      val nq = linkQuantiles.size
+      val lo = new Array[Long](S * S * nq); val hi = new Array[Long](S * S * nq); val cnt = new Array[Long](S * S)
+      check(ctx, ZkNative.lhQuantilesAll(lh, linkQuantiles.toArray, lo, hi, cnt))
+      durations = for (c <- 0 until S * S if present(c) != 0)
+        yield LinkDuration(names(c / S), names(c % S), cnt(c),
+          linkQuantiles.zipWithIndex.map { case (q, i) => q -> ((lo(c * nq + i), hi(c * nq + i))) }.toMap)
+    }
     if (links.isEmpty) None else Some(Dependencies(Time.epoch, Time.now, links)) // :41-42
   }
 
-  private[this] def withCtx[T](body: (Long, Long) => T): T = {
+  private[this] def withCtx[T](body: (Long, Long, Long) => T): T = {
     val ctx = ZkNative.ctxCreate(numServices, device, strict, maxTraceRecords)
     require(ctx != 0, "zk_ctx_create failed (no gfx950 device?)")
+    val lh = if (linkQuantiles.isEmpty) 0L else ZkNative.lhCreate(numServices, device, 0)
+    if (linkQuantiles.nonEmpty) {
+      require(lh != 0, "zk_lh_create failed (no device memory for the per-link histogram?)")
+      check(ctx, ZkNative.lhBind(ctx, lh))
+    }
     val comm = shard match {
       case Some(GpuShard(rank, world, id)) =>
         val c = ZkNative.commCreate(id, rank, world, device)
@@ -88,8 +116,12 @@ class GpuDependenciesJob(aggregates: Aggregates, device: Int = 0, strict: Boolea
         c
       case None => 0L
     }
-    try body(ctx, comm) finally {
+    try body(ctx, comm, lh) finally {
       if (comm != 0) ZkNative.commDestroy(comm)
+      if (lh != 0) {
+        ZkNative.lhBind(ctx, 0L)
+        ZkNative.lhDestroy(lh)
+      }
       ZkNative.ctxDestroy(ctx)
     }
   }
@@ -116,7 +148,7 @@ class GpuDependenciesJob(aggregates: Aggregates, device: Int = 0, strict: Boolea
   def runSpans(batches: Iterator[Seq[Span]]): Future[Option[Dependencies]] = {
     val names = new Dictionary
     services.foreach(names.id)
-    val out = withCtx { (ctx, comm) =>
+    val out = withCtx { (ctx, comm, lh) =>
       guarded(ctx, comm) {
         for (b <- batches) {
           val c = new Columns(b.size)
@@ -126,7 +158,7 @@ class GpuDependenciesJob(aggregates: Aggregates, device: Int = 0, strict: Boolea
           accumulate(ctx, c, b.size, 0)
         }
       }
-      finish(ctx, comm, names.name)
+      finish(ctx, comm, lh, names.name)
     }
     store(out)
   }
@@ -149,7 +181,7 @@ class GpuDependenciesJob(aggregates: Aggregates, device: Int = 0, strict: Boolea
     }
     def submit(vals: Seq[Array[Byte]]) = decoder.submit(new Callable[(Columns, Long)] { def call() = decode(vals) })
     try {
-      val out = withCtx { (ctx, comm) =>
+      val out = withCtx { (ctx, comm, lh) =>
         guarded(ctx, comm) {
           // batch k accumulates (PCIe staging + device work) while batch k+1 decodes on the other thread
           var next = if (batches.hasNext) Some(submit(batches.next())) else None
@@ -163,7 +195,7 @@ class GpuDependenciesJob(aggregates: Aggregates, device: Int = 0, strict: Boolea
           require(S <= numServices, s"$S service names > numServices = $numServices")
           require(shard.isEmpty || S == services.size, "a stored span names a service outside the job's list")
         }
-        finish(ctx, comm, i => ZkNative.ingestServiceName(ing, i))
+        finish(ctx, comm, lh, i => ZkNative.ingestServiceName(ing, i))
       }
       store(out)
     } finally {

@@ -82,6 +82,17 @@ object ZkNative {
     * rows without a name), -1 = every rpc; the filter runs on the device. null on error */
   @native def rlServerRpcLinks(rl: Long, server: Int, rpc: Int): Array[Long]
 
+  // ---- per-link duration histogram (zksketch.h zk_lh_*): p50/p99 of every dependency edge ---------
+  /** subBits: histogram mantissa bits m, 2..7 (0 = 4); 0 on error (ZK_ERR_CAPACITY: S*S*bins*4 B of HBM) */
+  @native def lhCreate(numServices: Int, device: Int, subBits: Int): Long
+  @native def lhDestroy(lh: Long): Int
+  @native def lhReset(lh: Long): Int
+  /** every later accumulate on ctx also counts its links into lh (lh = 0 unbinds) */
+  @native def lhBind(ctx: Long, lh: Long): Int
+  /** every edge at once: lo / hi receive S*S*q.length bin bounds (us), count S*S link counts; cell =
+    * parent * S + child, all 0 for an edge without links */
+  @native def lhQuantilesAll(lh: Long, q: Array[Double], lo: Array[Long], hi: Array[Long], count: Array[Long]): Int
+
   // ---- ingest (zkingest.h) -----------------------------------------------------------------------
   @native def ingestCreate(): Long
   @native def ingestDestroy(ing: Long): Int

@@ -134,7 +134,8 @@ class zk_timing(C.Structure):
         ("reduce_ms_total", C.c_double),
         ("cluster_ms", C.c_double),
         ("cluster_ms_total", C.c_double),
-        ("reserved", C.c_double * 2),
+        ("link_hist_ms", C.c_double),
+        ("link_hist_ms_total", C.c_double),
     ]
 
 
@@ -195,6 +196,16 @@ class zk_rl_config(C.Structure):
         ("num_services", C.c_uint32),
         ("device", C.c_int32),
         ("stream", C.c_void_p),
+        ("reserved", C.c_uint32 * 8),
+    ]
+
+
+class zk_lh_config(C.Structure):
+    _fields_ = [
+        ("num_services", C.c_uint32),
+        ("device", C.c_int32),
+        ("stream", C.c_void_p),
+        ("sub_bits", C.c_uint32),
         ("reserved", C.c_uint32 * 8),
     ]
 
@@ -310,6 +321,18 @@ _SIGNATURES = [
     ("zk_rl_count", C.c_int, [_P, _U64P, _U64P]),
     ("zk_rl_server_links", C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint64, _U64P]),
     ("zk_rl_server_rpc_links", C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_uint64, _U64P]),
+    # include/zksketch.h: per-link duration histogram (quantiles of every dependency edge)
+    ("zk_lh_create", C.c_int, [C.POINTER(zk_lh_config), C.POINTER(_P)]),
+    ("zk_lh_destroy", C.c_int, [_P]),
+    ("zk_lh_last_error", C.c_char_p, [_P]),
+    ("zk_lh_reset", C.c_int, [_P]),
+    ("zk_lh_geometry", C.c_int, [_P, _U32P]),
+    ("zk_lh_bind", C.c_int, [_P, _P]),
+    ("zk_lh_quantiles", C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _U64P]),
+    ("zk_lh_quantiles_all", C.c_int, [_P, _P, C.c_uint32, _P, _P, _U64P]),
+    ("zk_lh_read", C.c_int, [_P, C.c_uint64, C.c_uint64, _P]),
+    ("zk_lh_partial", C.c_int, [_P, C.POINTER(_P), _U64P]),
+    ("zk_lh_dropped", C.c_int, [_P, _U64P]),
     # include/zkcomm.h: RCCL communicator and the multi-GPU merges
     ("zk_comm_unique_id", C.c_int, [_P, C.c_uint64]),
     ("zk_comm_create", C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(_P)]),
@@ -318,6 +341,7 @@ _SIGNATURES = [
     ("zk_deps_allreduce", C.c_int, [_P, _P, C.c_uint64]),
     ("zk_rt_allreduce", C.c_int, [_P, _P]),
     ("zk_kv_allreduce", C.c_int, [_P, _P]),
+    ("zk_lh_allreduce", C.c_int, [_P, _P]),
     # include/zkingest.h: stored span fragments -> columnar records
     ("zk_ingest_create", C.c_int, [C.POINTER(_P)]),
     ("zk_ingest_destroy", C.c_int, [_P]),

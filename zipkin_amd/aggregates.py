@@ -15,10 +15,11 @@ The reference's failed Futures are raised here as ZkError (the C status) or Asse
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import time
 from dataclasses import dataclass, field
-from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence
+from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -599,6 +600,29 @@ def cassandra_row_key(start_time_us: int) -> int:
     return int(_abi.lib().zk_dependencies_row_key(int(start_time_us)))
 
 
+class LinkDuration(NamedTuple):
+    """The duration quantiles of one dependency edge, the side output of a job run with
+    link_quantiles: for each asked q the bounds (lo, hi) in us of the histogram bin that holds the
+    nearest-rank quantile of the edge's child durations (lo <= exact <= hi), and the edge's link count
+    (its Moments.m0)."""
+
+    parent: str
+    child: str
+    count: int
+    quantiles: Dict[float, Tuple[int, int]]
+
+
+def _link_durations(table, names: Sequence[str], hist, qs: Sequence[float]) -> List[LinkDuration]:
+    """One LinkDuration per present cell of the finalized table, in LinkList (cell) order."""
+    lo, hi, cnt = hist.quantiles_all(qs)
+    S = table.num_services
+    out = []
+    for c in np.flatnonzero(table.present).tolist():
+        out.append(LinkDuration(names[c // S], names[c % S], int(cnt[c]),
+                                {float(q): (int(lo[c, i]), int(hi[c, i])) for i, q in enumerate(qs)}))
+    return out
+
+
 def links_from_table(table, services: Dictionary) -> "LinkList":
     """The present cells of a finalized host LinkTable as DependencyLinks (zk_link_table_compact),
     kept in the table's form (LinkList) until read."""
@@ -624,13 +648,22 @@ class ZipkinAggregateJob:
     measures. A caller opts in to it for input it knows to be row-ordered; verify=True then also
     checks that promise exactly on the device (a split trace fails the job), verify=False trusts it.
 
+    link_quantiles (e.g. (0.5, 0.99)): the job also keeps a per-edge duration histogram on the device
+    (realtime.LinkHistogram bound to its context) and link_durations() returns, after run(), the asked
+    quantiles of every link -- a side output beside the Dependencies record, whose thrift form has no
+    field for it. run()'s return value does not change.
+
     The device context is kept between runs (a scheduled job reuses its buffers); close() frees it.
     """
 
     def __init__(self, services: Dictionary, *, device: int = 0, strict: bool = True,
-                 aggregates: Optional[Aggregates] = None, clock=now_us, order: str = "any", verify: bool = True):
+                 aggregates: Optional[Aggregates] = None, clock=now_us, order: str = "any", verify: bool = True,
+                 link_quantiles: Optional[Sequence[float]] = None):
         if order not in ("rows", "any"):
             raise ValueError("order is 'rows' or 'any'")
+        self.link_quantiles = None if link_quantiles is None else tuple(float(q) for q in link_quantiles)
+        self._lh = None
+        self._link_durations: List[LinkDuration] = []
         self.services = services
         self.device = device
         self.strict = strict
@@ -642,6 +675,9 @@ class ZipkinAggregateJob:
         self._ctx = None
 
     def close(self) -> None:
+        if self._lh is not None:
+            self._lh.close()
+            self._lh = None
         if self._ctx is not None:
             self._ctx.close()
             self._ctx = None
@@ -652,8 +688,15 @@ class ZipkinAggregateJob:
         if self._ctx is None or self._ctx.num_services != S:
             self.close()
             self._ctx = DepsContext(S, device=self.device, strict=self.strict)
+            if self.link_quantiles is not None:
+                from .realtime import LinkHistogram
+
+                self._lh = LinkHistogram(S, device=self.device)
+                self._lh.bind(self._ctx)
         else:
             self._ctx.reset()
+            if self._lh is not None:
+                self._lh.reset()
         return self._ctx
 
     def accumulate_all(self, batches, num_services: Optional[int] = None):
@@ -672,7 +715,15 @@ class ZipkinAggregateJob:
         ctx = self.accumulate_all(batches, num_services)
         table = ctx.finalize()  # the job ends here: a held-back trace is aggregated first
         self.stats = ctx.stats()
+        if self._lh is not None:
+            names = [self.services.name(i) for i in range(min(table.num_services, len(self.services)))]
+            self._link_durations = _link_durations(table, names, self._lh, self.link_quantiles)
         return self._publish(table)
+
+    def link_durations(self) -> List[LinkDuration]:
+        """After run() of a job with link_quantiles: one LinkDuration per link of the record, in the
+        order of its LinkList."""
+        return self._link_durations
 
     def _publish(self, table) -> Optional[Dependencies]:
         links = links_from_table(table, self.services)
@@ -717,11 +768,17 @@ class StoredSpanJob:
     max_services sizes the device table (S x S cells) and the sketches before the dictionary is
     known; a stream that names more services fails with ZK_ERR_SERVICE_RANGE. For the same reason the
     count-min width per service is kv_width or the largest, 4096 (the auto width of <= 256 services).
+
+    link_quantiles: as for ZipkinAggregateJob -- run() and run_device() also feed a per-edge duration
+    histogram (max_services^2 x 592 counters of 4 B) and link_durations() returns every link's quantiles.
     """
 
     def __init__(self, *, device: int = 0, strict: bool = True, aggregates: Optional[Aggregates] = None,
                  clock=now_us, top_k: int = 10, snappy: bool = True, kv_width: int = 0, seed: int = 0,
-                 max_services: int = 1024, verify: bool = False):
+                 max_services: int = 1024, verify: bool = False,
+                 link_quantiles: Optional[Sequence[float]] = None):
+        self.link_quantiles = None if link_quantiles is None else tuple(float(q) for q in link_quantiles)
+        self._link_durations: List[LinkDuration] = []
         self.device = device
         self.strict = strict
         self.aggregates = aggregates
@@ -754,12 +811,19 @@ class StoredSpanJob:
         kl, cl = keys[:S].tolist(), cnt[:S].tolist()  # Python ints: no numpy scalar per lookup
         return {dec.service_name(s_): [dec.string(h) for h in kl[s_][: cl[s_]]] for s_ in range(S) if cl[s_]}
 
-    def _finish(self, ctx, names: List[str]) -> Optional[Dependencies]:
+    def link_durations(self) -> List[LinkDuration]:
+        """After run() / run_device() of a job with link_quantiles: one LinkDuration per link of the
+        record, in the order of its LinkList."""
+        return self._link_durations
+
+    def _finish(self, ctx, names: List[str], hist=None) -> Optional[Dependencies]:
         if len(names) > self.max_services:
             raise _abi.ZkError(_abi.ZK_ERR_SERVICE_RANGE, f"{len(names)} services > max_services {self.max_services}")
         self.services = Dictionary(names)
         table = ctx.finalize()
         self.stats = ctx.stats()
+        if hist is not None:
+            self._link_durations = _link_durations(table, names, hist, self.link_quantiles)
         job = ZipkinAggregateJob(self.services, device=self.device, strict=self.strict, clock=self.clock)
         return job._publish(table)
 
@@ -769,14 +833,20 @@ class StoredSpanJob:
         from .context import DepsContext
         from .ingest import SpanDecoder
         from .kv import KvSketch
+        from .realtime import LinkHistogram
 
         dec = SpanDecoder()
         self.rejected = 0
         S = self.max_services
-        with DepsContext(S, device=self.device, strict=self.strict) as ctx, \
+        lh = None
+        with contextlib.ExitStack() as stack, \
+                DepsContext(S, device=self.device, strict=self.strict) as ctx, \
                 KvSketch(S, device=self.device, width=self.kv_width or 4096, seed=self.seed) as kvs, \
                 KvSketch(S, device=self.device, width=self.kv_width or 4096, seed=self.seed) as anns, \
                 ThreadPoolExecutor(max_workers=1) as pool:
+            if self.link_quantiles is not None:
+                lh = stack.enter_context(LinkHistogram(S, device=self.device))
+                lh.bind(ctx)
             it = iter(batches)
             nxt = next(it, None)
             fut = pool.submit(self._decode, dec, nxt) if nxt is not None else None
@@ -808,7 +878,7 @@ class StoredSpanJob:
                     items_in()
             items_in()
             names = dec.service_names()
-            deps = self._finish(ctx, names)
+            deps = self._finish(ctx, names, lh)
             self.top_kv = self._tops(dec, kvs, len(names))
             self.top_annotations = self._tops(dec, anns, len(names))
         if self.aggregates is not None:
@@ -846,10 +916,17 @@ class StoredSpanJob:
             st = {"stream": stream, "pool": None,
                   "dec": DeviceSpanDecoder(max(4096, S), device=self.device, stream=stream.cuda_stream),
                   "ctx": DepsContext(S, device=self.device, strict=self.strict, stream=stream.cuda_stream),
-                  "kvs": None, "anns": None}
+                  "kvs": None, "anns": None, "lh": None}
+            if self.link_quantiles is not None:
+                from .realtime import LinkHistogram
+
+                st["lh"] = LinkHistogram(S, device=self.device, stream=stream.cuda_stream)
+                st["lh"].bind(st["ctx"])
             self._dev = st
         else:
             st["ctx"].reset()
+            if st["lh"] is not None:
+                st["lh"].reset()
         if indexer:
             for k in ("kvs", "anns"):
                 if st[k] is None:
@@ -862,7 +939,7 @@ class StoredSpanJob:
     def close(self) -> None:
         st = getattr(self, "_dev", None)
         if st is not None:
-            for k in ("kvs", "anns", "ctx", "dec"):
+            for k in ("kvs", "anns", "lh", "ctx", "dec"):
                 if st[k] is not None:
                     st[k].close()
             self._dev = None
@@ -954,7 +1031,7 @@ class StoredSpanJob:
             flush()
             t2 = time.perf_counter()
             names = dec.service_names()
-            deps = self._finish(ctx, names)
+            deps = self._finish(ctx, names, st["lh"])
             if indexer:
                 self.top_kv = self._tops(dec, kvs, len(names))
                 self.top_annotations = self._tops(dec, anns, len(names))

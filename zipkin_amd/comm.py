@@ -65,3 +65,7 @@ class Comm:
 
     def allreduce_kv(self, kv) -> None:
         kv._check(self._L.zk_kv_allreduce(kv.handle, self._h))
+
+    def allreduce_lh(self, lh) -> None:
+        """zk_lh_allreduce: the per-link duration histogram by u32 SUM, on the handle's stream."""
+        lh._check(self._L.zk_lh_allreduce(lh.handle, self._h))

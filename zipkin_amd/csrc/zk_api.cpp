@@ -16,6 +16,7 @@
 
 #include "zk_internal.h"
 #include "zk_launch.h"
+#include "zk_lh_internal.h"
 #include "zk_rl_internal.h"
 #include "zk_rt_internal.h"
 
@@ -97,8 +98,10 @@ struct zk_ctx {
     uint32_t rt_mode = ZK_RT_WITH_DEPS;
     // bound realtime link store (zk_rl_bind): K1 writes an item beside every link
     zk_rl* rl = nullptr;
+    // bound per-link duration histogram (zk_lh_bind): fed from the reduced links of every batch
+    zk_lh* lh = nullptr;
     // timing
-    std::vector<EventPair> ev_free, ev_join, ev_reduce, ev_spill, ev_fin, ev_cluster;
+    std::vector<EventPair> ev_free, ev_join, ev_reduce, ev_spill, ev_fin, ev_cluster, ev_lh;
     zk_timing tm{};
 };
 
@@ -439,6 +442,7 @@ zk_status zk_ctx_destroy(zk_ctx* c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     if (c->rt) rt_set_stream(c->rt, nullptr);
     if (c->rl) rl_set_stream(c->rl, nullptr);
+    if (c->lh) lh_set_stream(c->lh, nullptr);
     if (c->own_table) hipFree(c->table);
     c->table = nullptr;
     hipFree(c->stats);
@@ -462,7 +466,7 @@ zk_status zk_ctx_destroy(zk_ctx* c) {
     hipFree(c->xchg);
     hipFree(c->carry);
     hipFree(c->cs);
-    for (auto* v : {&c->ev_free, &c->ev_join, &c->ev_reduce, &c->ev_spill, &c->ev_fin, &c->ev_cluster})
+    for (auto* v : {&c->ev_free, &c->ev_join, &c->ev_reduce, &c->ev_spill, &c->ev_fin, &c->ev_cluster, &c->ev_lh})
         for (auto& p : *v) {
             hipEventDestroy(p.a);
             hipEventDestroy(p.b);
@@ -545,6 +549,11 @@ zk_status zk_deps_accumulate(zk_ctx* c, const zk_span_cols* cols, uint32_t flags
     const bool join = !c->rt || c->rt_mode == ZK_RT_WITH_DEPS;
     if (join && c->records_since_reset + n > kMaxRecordsSinceReset)  // (held records counted with their batch)
         return fail(c, ZK_ERR_CAPACITY, "more than 2^32-1 records since reset");
+    if (c->lh && join) {  // its u32 counters: links <= records since the handle's own reset
+        if (lh_reserved(c->lh) + n > kMaxRecordsSinceReset)
+            return fail(c, ZK_ERR_CAPACITY, "link histogram: more than 2^32-1 records since its reset");
+        lh_reserve(c->lh, n);
+    }
     ZK_HIP(c, hipSetDevice(c->device));
     if (c->merged) {
         // accumulating into a merged table: the table holds the whole job, so the ctx's own counters
@@ -632,28 +641,61 @@ static JoinArgs join_args(zk_ctx* c, const SpanColsDev& d) {
     a.nb = c->nb;
     a.cb_shift = c->cb_shift;
     a.join = 1u;
+    if (c->lh) lh_join_args(c->lh, &a);
     return a;
 }
 
+// the link reduce's arguments over `grid` K1 lists of stride `stride`
+static ReduceArgs reduce_args(zk_ctx* c, uint32_t grid, uint64_t stride) {
+    ReduceArgs r{};
+    r.links = c->links;
+    r.counts = c->link_count;
+    r.stride = stride;
+    r.lists = grid;
+    r.hist = c->hist;
+    r.nb = c->nb;
+    r.cb_shift = c->cb_shift;
+    r.col_off = c->col_off;
+    r.bucket_base = c->bucket_base;
+    r.sorted = c->sorted;
+    r.table = c->table;
+    r.cells = (uint64_t)c->S * c->S;
+    return r;
+}
+
 static zk_status reduce_links(zk_ctx* c, uint32_t grid, uint64_t stride) {
-    if (c->nb) {
-        ReduceArgs r{};
-        r.links = c->links;
-        r.counts = c->link_count;
-        r.stride = stride;
-        r.lists = grid;
-        r.hist = c->hist;
-        r.nb = c->nb;
-        r.cb_shift = c->cb_shift;
-        r.col_off = c->col_off;
-        r.bucket_base = c->bucket_base;
-        r.sorted = c->sorted;
-        r.table = c->table;
-        r.cells = (uint64_t)c->S * c->S;
-        ZK_HIP(c, launch_partitioned_reduce(r, c->stream));
-    } else {
+    if (c->nb)
+        ZK_HIP(c, launch_partitioned_reduce(reduce_args(c, grid, stride), c->stream));
+    else
         ZK_HIP(c, launch_link_reduce(c->links, c->link_count, stride, grid, c->table, c->stream));
+    return ZK_OK;
+}
+
+// A bound link histogram around one batch. Before the join: the ctx's duration-range counter as it
+// stands (the links a batch drops for their duration never reach the lists)...
+static zk_status lh_before(zk_ctx* c) {
+    if (c->lh) ZK_HIP(c, lh_note_dropped(c->lh, c->stats, -1));
+    return ZK_OK;
+}
+// ... right after the link reduce: the batch's links (K2's bucket-ordered copy, else the K1 lists) into
+// the histogram ...
+static zk_status lh_links(zk_ctx* c, uint32_t grid, uint64_t stride) {
+    if (!c->lh) return ZK_OK;
+    EventPair el;
+    if (c->timing) {
+        el = take_pair(c);
+        ZK_HIP(c, hipEventRecord(el.a, c->stream));
     }
+    ZK_HIP(c, lh_accumulate(c->lh, reduce_args(c, grid, stride)));
+    if (c->timing) {
+        ZK_HIP(c, hipEventRecord(el.b, c->stream));
+        c->ev_lh.push_back(el);
+    }
+    return ZK_OK;
+}
+// ... and after the spill pass (which adds its links' bins itself): what the batch dropped
+static zk_status lh_after(zk_ctx* c) {
+    if (c->lh) ZK_HIP(c, lh_note_dropped(c->lh, c->stats, +1));
     return ZK_OK;
 }
 
@@ -695,6 +737,7 @@ static zk_status accumulate_groups(zk_ctx* c, const SpanColsDev& d, const Cluste
     a.nsub = g.nsub;
     a.big_list = g.big_list;
     a.big_count = g.big_count;
+    ZK_ST(lh_before(c));
     if (c->timing) {
         ej = take_pair(c);
         ZK_HIP(c, hipEventRecord(ej.a, c->stream));
@@ -718,6 +761,9 @@ static zk_status accumulate_groups(zk_ctx* c, const SpanColsDev& d, const Cluste
     if (c->timing) {
         ZK_HIP(c, hipEventRecord(er.b, c->stream));
         c->ev_reduce.push_back(er);
+    }
+    ZK_ST(lh_links(c, grid, stride));
+    if (c->timing) {
         es = take_pair(c);
         ZK_HIP(c, hipEventRecord(es.a, c->stream));
     }
@@ -726,6 +772,7 @@ static zk_status accumulate_groups(zk_ctx* c, const SpanColsDev& d, const Cluste
         ZK_HIP(c, hipEventRecord(es.b, c->stream));
         c->ev_spill.push_back(es);
     }
+    ZK_ST(lh_after(c));
     c->records_since_reset += n;
     return ZK_OK;
 }
@@ -800,6 +847,8 @@ static zk_status accumulate_dev(zk_ctx* c, SpanColsDev d, uint32_t flags, uint32
     a.cb_shift = c->cb_shift;
     a.join = join ? 1u : 0u;
     a.skip = skip;
+    const bool lh = c->lh && join;
+    if (lh) lh_join_args(c->lh, &a);
     if (dr) {
         a.skip_dev = dr->skip_dev;
         a.n_dev = dr->n_dev;
@@ -814,6 +863,7 @@ static zk_status accumulate_dev(zk_ctx* c, SpanColsDev d, uint32_t flags, uint32
         if (st != ZK_OK) return fail(c, st, std::string("realtime links: ") + rl_error(c->rl));
     }
     EventPair ej, er, es;
+    if (lh) ZK_ST(lh_before(c));
     if (c->timing) {
         ej = take_pair(c);
         ZK_HIP(c, hipEventRecord(ej.a, c->stream));
@@ -834,29 +884,13 @@ static zk_status accumulate_dev(zk_ctx* c, SpanColsDev d, uint32_t flags, uint32
         er = take_pair(c);
         ZK_HIP(c, hipEventRecord(er.a, c->stream));
     }
-    if (!join) {
-        // sketch-only pass: no links to reduce
-    } else if (c->nb) {
-        ReduceArgs r{};
-        r.links = c->links;
-        r.counts = c->link_count;
-        r.stride = stride;
-        r.lists = grid;
-        r.hist = c->hist;
-        r.nb = c->nb;
-        r.cb_shift = c->cb_shift;
-        r.col_off = c->col_off;
-        r.bucket_base = c->bucket_base;
-        r.sorted = c->sorted;
-        r.table = c->table;
-        r.cells = (uint64_t)c->S * c->S;
-        ZK_HIP(c, launch_partitioned_reduce(r, c->stream));
-    } else {
-        ZK_HIP(c, launch_link_reduce(c->links, c->link_count, stride, grid, c->table, c->stream));
-    }
+    if (join) ZK_ST(reduce_links(c, grid, stride));  // (a sketch-only pass has no links to reduce)
     if (c->timing) {
         ZK_HIP(c, hipEventRecord(er.b, c->stream));
         c->ev_reduce.push_back(er);
+    }
+    if (lh) ZK_ST(lh_links(c, grid, stride));
+    if (c->timing) {
         es = take_pair(c);
         ZK_HIP(c, hipEventRecord(es.a, c->stream));
     }
@@ -866,6 +900,7 @@ static zk_status accumulate_dev(zk_ctx* c, SpanColsDev d, uint32_t flags, uint32
         ZK_HIP(c, hipEventRecord(es.b, c->stream));
         c->ev_spill.push_back(es);
     }
+    if (lh) ZK_ST(lh_after(c));
     if (c->rt) {
         st = rt_consume_lists(c->rt, grid, stride, n + (dr ? c->carry_cap : 0));
         if (st != ZK_OK) return fail(c, st, std::string("sketch: ") + rt_error(c->rt));
@@ -961,7 +996,10 @@ static zk_status flush_carry(zk_ctx* c) {
         const zk_status st = rl_prepare_lists(c->rl, 0, 0, c->carry_cap, &f, c->stream);
         if (st != ZK_OK) return fail(c, st, std::string("realtime links: ") + rl_error(c->rl));
     }
+    const bool lh = c->lh && f.join;  // (the spill kernel adds the held trace's bins: join_args)
+    if (lh) ZK_ST(lh_before(c));
     ZK_HIP(c, launch_spill(f, 1, c->stream));
+    if (lh) ZK_ST(lh_after(c));
     if (c->rt) {
         const zk_status st = rt_consume_lists(c->rt, 0, 0, c->carry_cap);
         if (st != ZK_OK) return fail(c, st, std::string("sketch: ") + rt_error(c->rt));
@@ -1072,6 +1110,7 @@ zk_status zk_ctx_timing(zk_ctx* c, zk_timing* out) {
     drain(c->ev_spill, &c->tm.spill_ms, nullptr, nullptr);
     drain(c->ev_fin, &c->tm.finalize_ms, nullptr, nullptr);
     drain(c->ev_cluster, &c->tm.cluster_ms, &c->tm.cluster_ms_total, nullptr);
+    drain(c->ev_lh, &c->tm.link_hist_ms, &c->tm.link_hist_ms_total, nullptr);
     *out = c->tm;
     return ZK_OK;
     ZK_CATCH(c)
@@ -1166,10 +1205,27 @@ zk_status zk_rl_bind(zk_ctx* c, zk_rl* rl) {
     return ZK_OK;
 }
 
+zk_status zk_lh_bind(zk_ctx* c, zk_lh* lh) {
+    if (!c) return ZK_ERR_INVALID_ARG;
+    if (lh && lh_device(lh) != c->device) return fail(c, ZK_ERR_INVALID_ARG, "link histogram and ctx on different devices");
+    if (lh && lh_services(lh) != c->S) return fail(c, ZK_ERR_INVALID_ARG, "link histogram and ctx differ in num_services");
+    if (lh && c->rt && c->rt_mode == ZK_RT_ONLY)
+        return fail(c, ZK_ERR_UNSUPPORTED, "a link histogram on a ctx with a ZK_RT_ONLY sketch (it emits no links)");
+    if (c->lh && c->lh != lh) {
+        ZK_HIP(c, hipStreamSynchronize(c->stream));
+        lh_set_stream(c->lh, nullptr);
+    }
+    c->lh = lh;
+    if (lh) lh_set_stream(lh, c->stream);  // one stream orders the ctx's and the histogram's work
+    return ZK_OK;
+}
+
 zk_status zk_rt_bind(zk_ctx* c, zk_rt* rt, uint32_t mode) {
     if (!c) return ZK_ERR_INVALID_ARG;
     if (mode != ZK_RT_WITH_DEPS && mode != ZK_RT_ONLY) return fail(c, ZK_ERR_INVALID_ARG, "unknown sketch mode");
     if (rt && rt_device(rt) != c->device) return fail(c, ZK_ERR_INVALID_ARG, "sketch and ctx on different devices");
+    if (rt && c->lh && mode == ZK_RT_ONLY)
+        return fail(c, ZK_ERR_UNSUPPORTED, "a ZK_RT_ONLY sketch (no links) on a ctx with a link histogram");
     if (rt && c->rl && mode == ZK_RT_WITH_DEPS)
         return fail(c, ZK_ERR_UNSUPPORTED, "a ZK_RT_WITH_DEPS sketch and a realtime link store on one ctx");
     if (c->rt && c->rt != rt) {

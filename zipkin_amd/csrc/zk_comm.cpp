@@ -16,6 +16,7 @@
 
 #include "zk_comm.h"
 #include "zk_guard.h"
+#include "zk_lh_internal.h"
 
 namespace {
 
@@ -199,6 +200,13 @@ zk_status zk_comm_destroy(zk_comm* c) {
     }
     delete c;
     return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_lh_allreduce(zk_lh* lh, zk_comm* comm) {
+    ZK_GUARD_BEGIN
+    if (!lh) return ZK_ERR_INVALID_ARG;
+    return zk::lh_allreduce(lh, comm);  // (zk_lh.hip: the histogram by u32 SUM, like zk_rt_allreduce's bins)
     ZK_GUARD_END
 }
 

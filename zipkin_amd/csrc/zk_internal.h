@@ -137,7 +137,12 @@ struct JoinArgs {
     uint64_t* lk_tid;
     uint32_t* lk_spill_count;
     uint64_t lk_spill_cap;
-    uint32_t* lk_name;  // (last: the fields before it keep their kernel-argument offsets)
+    uint32_t* lk_name;  // (after the fields before it: they keep their kernel-argument offsets)
+    // per-link duration histogram (zk_lh, a bound handle), lh_hist == nullptr: none. Read by the spill
+    // kernel only, whose links bypass the lists: u32[S * S][lh_bins], bin = rt_bin(duration, lh_m)
+    uint32_t* lh_hist;
+    uint32_t lh_bins;
+    uint32_t lh_m;
 };
 
 // host-side launchers (implemented in the .hip files)

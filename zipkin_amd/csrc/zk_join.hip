@@ -1098,6 +1098,9 @@ __global__ __launch_bounds__(kSpillWG) void k_span_join_spill(JoinArgs a) {
                         st.inc(ST_DUR_RANGE);
                     } else {
                         emit_link(a.table, (spv & kSvcIdMask) * a.S + (sL & kSvcIdMask), d);
+                        if (a.lh_hist)  // the link's duration bin (spilled traces are rare: one atomic per link)
+                            atomicAdd(&a.lh_hist[((uint64_t)(spv & kSvcIdMask) * a.S + (sL & kSvcIdMask)) * a.lh_bins +
+                                                 rt_bin(d, a.lh_m)], 1u);
                         if (a.lk_key) {  // the realtime link item, appended to the spill list
                             const uint32_t q = atomicAdd(a.lk_spill_count, 1u);
                             if (q < a.lk_spill_cap) {

@@ -1,0 +1,514 @@
+// zk_lh.hip — per-link duration histogram (include/zksketch.h, zk_lh_*): p50/p99 of every
+// dependency edge.
+//
+// A DependencyLink carries only Moments (Dependencies.scala:34). Bound to a dependency ctx, every
+// link the job emits -- (cell << 40) | d, cell = parent * S + child, the rows ZipkinAggregateJob.scala:
+// 25-37 sums -- is also counted into u32 hist[cell][bin], bin = zk_rt's log-linear bin of d
+// (zk_sketch_internal.h rt_bin). Integer counts: independent of batch order and cuts, merged across
+// traceId shards by SUM.
+//
+// k_lh_tiles runs after the link reduce and reads the bucket-ordered copy of the batch's links K2
+// left behind (ReduceArgs.sorted, bucket b = cells [b << cb_shift, (b + 1) << cb_shift) at
+// [bucket_base[b], bucket_base[b + 1])). A bucket's rows (512 cells x 592 bins x 4 B = 1.2 MB at m = 4)
+// do not fit the 160 KiB of LDS, so a bucket is tiled by cell sub-range: T = 2^tshift cells per tile,
+// the largest power of two whose T x bins counters fit (lh_tile_shift: 128 cells at m = 2 and 3, 64
+// at 4, 32 at 5, 16 at 6, 8 at 7). One workgroup per (bucket, tile) walks the bucket's links, counts
+// those of its own cells with LDS atomics and then adds the non-zero counters to the rows in HBM with
+// plain loads and stores: it is the only workgroup that touches those rows, so no global atomic is
+// issued (a global atomic executes at the memory side, one 64-B request per scattered dword, an order
+// of magnitude below contiguous traffic). Every tile of a bucket re-reads the bucket's links; the
+// tiles of one bucket are placed on one XCD so the re-reads meet in its L2. With few buckets (small
+// S) each (bucket, tile) is split over several workgroups by link range for parallelism, and only
+// then the flush adds are atomic -- as K3 does (zk_reduce.hip).
+//
+// The spill kernel bypasses the link lists (zk_join.hip emit_link): it adds its links' bins with one
+// device-scope atomic each (JoinArgs.lh_hist); spilled traces are rare. Without bucket order (S >
+// 1024: the table itself is then reduced with global atomics, k_link_reduce_atomic) k_lh_lists reads
+// the K1 lists and adds one atomic per link.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include <string>
+#include <vector>
+
+#include "zk_comm.h"
+#include "zk_guard.h"
+#include "zk_internal.h"
+#include "zk_launch.h"
+#include "zk_lh_internal.h"
+#include "zk_sketch_internal.h"
+#include "zksketch.h"
+
+namespace zk {
+namespace {
+
+constexpr int kLhWG = 1024;  // one workgroup per CU (its tile takes the LDS): 16 waves hide the link loads
+constexpr int kLhU = 4;      // links per thread per iteration (the next iteration's in flight)
+// LDS of one tile: what a CU has, less room for the kernel's static LDS and the runtime's own
+constexpr uint64_t kLhLdsBudget = 152ull * 1024;
+constexpr uint32_t kLhMaxQ = 8;  // quantiles per k_lh_quantiles pass
+constexpr uint32_t kLhTargetWGs = 512;  // (bucket, tile) pairs below this are split by link range
+
+struct LhArgs {
+    const uint64_t* sorted;       // the batch's links in bucket order
+    const uint64_t* bucket_base;  // [nb + 1]
+    uint32_t cb_shift;
+    uint64_t cells;
+    uint32_t* hist;               // [cells][bins]
+    uint32_t bins, m;
+    uint32_t tshift;              // tile = 2^tshift cells
+    uint32_t nsub;                // tiles per bucket
+    uint32_t splits;              // workgroups per (bucket, tile)
+};
+
+__global__ __launch_bounds__(kLhWG) void k_lh_tiles(LhArgs a) {
+    extern __shared__ uint32_t s_h[];  // [T][bins]
+    const int tid = threadIdx.x;
+    // XCD-aware order (dispatch puts block i on XCD i % 8): the blocks of one XCD take consecutive
+    // work items, so the tiles of one bucket read its links through one L2
+    const uint32_t gx = gridDim.x / 8, gr = gridDim.x % 8, xi = blockIdx.x % 8;
+    const uint32_t item = xi * gx + (xi < gr ? xi : gr) + blockIdx.x / 8;
+    const uint32_t per_bucket = a.nsub * a.splits;
+    const uint32_t b = item / per_bucket, rem = item % per_bucket;
+    const uint32_t sub = rem / a.splits, part = rem % a.splits;
+    const uint64_t lo = a.bucket_base[b], hi = a.bucket_base[b + 1];
+    const uint64_t per = (hi - lo + a.splits - 1) / a.splits;
+    const uint64_t p0 = lo + per * part;
+    const uint64_t p1 = (p0 + per < hi) ? p0 + per : hi;
+    if (p0 >= p1) return;  // (uniform) no link in this range
+    const uint32_t T = 1u << a.tshift;
+    const uint32_t words = T * a.bins;
+    for (uint32_t x = tid; x < words; x += kLhWG) s_h[x] = 0u;
+    const uint64_t cell0 = (uint64_t)b << a.cb_shift;
+    // (a link is never all ones here: bucket order exists for S <= 1024 only, cell < 2^20)
+    uint64_t nxt[kLhU];
+#pragma unroll
+    for (int k = 0; k < kLhU; ++k) {
+        const uint64_t i = p0 + tid + (uint64_t)k * kLhWG;
+        nxt[k] = i < p1 ? a.sorted[i] : ~0ull;
+    }
+    __syncthreads();
+    for (uint64_t base = p0; base < p1; base += (uint64_t)kLhWG * kLhU) {
+        uint64_t v[kLhU];
+#pragma unroll
+        for (int k = 0; k < kLhU; ++k) {
+            v[k] = nxt[k];
+            const uint64_t i = base + (uint64_t)kLhWG * kLhU + tid + (uint64_t)k * kLhWG;
+            nxt[k] = i < p1 ? a.sorted[i] : ~0ull;
+        }
+#pragma unroll
+        for (int k = 0; k < kLhU; ++k) {
+            if (v[k] == ~0ull) continue;
+            const uint32_t c = (uint32_t)((v[k] >> 40) - cell0);
+            if ((c >> a.tshift) != sub) continue;  // another tile's cell (sub < nsub bounds c to the bucket)
+            atomicAdd(&s_h[(c & (T - 1)) * a.bins + rt_bin(v[k] & (kMaxDuration - 1), a.m)], 1u);
+        }
+    }
+    __syncthreads();
+    // one wave per row: the non-zero counters of a row added to HBM side by side
+    const uint32_t wave = tid >> 6, lane = tid & 63;
+    for (uint32_t r = wave; r < T; r += kLhWG / 64) {
+        const uint64_t cell = cell0 + (uint64_t)sub * T + r;
+        if (cell >= a.cells) break;  // (rows ascend) past the table's last cell
+        uint32_t* dst = a.hist + cell * a.bins;
+        const uint32_t* src = s_h + r * a.bins;
+        for (uint32_t x = lane; x < a.bins; x += 64) {
+            const uint32_t n = src[x];
+            if (!n) continue;
+            if (a.splits == 1)
+                dst[x] += n;  // this workgroup owns the row
+            else
+                atomicAdd(&dst[x], n);
+        }
+    }
+}
+
+// no bucket order (S > 1024): the K1 lists as they are, one atomic per link
+__global__ __launch_bounds__(256) void k_lh_lists(const uint64_t* __restrict__ links, const uint32_t* __restrict__ counts,
+                                                  uint64_t stride, uint32_t lists, uint64_t cells,
+                                                  uint32_t* __restrict__ hist, uint32_t bins, uint32_t m) {
+    for (uint32_t w = blockIdx.x; w < lists; w += gridDim.x) {
+        const uint32_t c = counts[w];
+        const uint64_t* L = links + (uint64_t)w * stride;
+        for (uint32_t i = threadIdx.x; i < c; i += 256) {
+            const uint64_t v = L[i];
+            const uint64_t cell = v >> 40;
+            if (cell < cells) atomicAdd(&hist[cell * bins + rt_bin(v & (kMaxDuration - 1), m)], 1u);
+        }
+    }
+}
+
+// dropped += sign * (the ctx's duration-range counter summed over its stats shards)
+__global__ __launch_bounds__(kStatShards) void k_lh_note_dropped(const unsigned long long* __restrict__ stats, int sign,
+                                                                 unsigned long long* __restrict__ dropped) {
+    __shared__ unsigned long long s_w[kStatShards / 64];
+    unsigned long long v = stats[(uint64_t)threadIdx.x * ST_N + ST_DUR_RANGE];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t = 0;
+        for (int w = 0; w < kStatShards / 64; ++w) t += s_w[w];
+        *dropped += sign > 0 ? t : 0ull - t;  // (wraps between the two calls of a batch)
+    }
+}
+
+// One wave per cell: the row's total N, then for each q[i] the bin holding the nearest rank
+// max(1, ceil(q N)), by a wave prefix over 64-bin chunks with a carried running count.
+// count[cell] = N; qbin[cell * nq + i] = the bin (0 when N = 0).
+__global__ __launch_bounds__(256) void k_lh_quantiles(const uint32_t* __restrict__ hist, uint64_t cells, uint32_t bins,
+                                                      const double* __restrict__ q, uint32_t nq,
+                                                      unsigned long long* __restrict__ count, uint32_t* __restrict__ qbin) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t cell = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (cell >= cells) return;
+    const uint32_t* row = hist + cell * bins;
+    unsigned long long n = 0;
+    for (uint32_t x = lane; x < bins; x += 64) n += row[x];
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
+    if (lane == 0) count[cell] = n;
+    if (n == 0) {
+        if (lane < nq) qbin[cell * nq + lane] = 0u;
+        return;
+    }
+    unsigned long long rank[kLhMaxQ];
+#pragma unroll
+    for (uint32_t i = 0; i < kLhMaxQ; ++i) {
+        unsigned long long r = 0;  // (0: no bin matches)
+        if (i < nq) {
+            r = (unsigned long long)ceil(q[i] * (double)n);
+            if (r < 1) r = 1;
+            if (r > n) r = n;
+        }
+        rank[i] = r;
+    }
+    unsigned long long carry = 0;
+    for (uint32_t base = 0; base < bins; base += 64) {
+        const uint32_t x = base + lane;
+        const unsigned long long v = x < bins ? row[x] : 0u;
+        unsigned long long incl = v;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned long long o = __shfl_up(incl, off);
+            if ((int)lane >= off) incl += o;
+        }
+        incl += carry;
+        const unsigned long long excl = incl - v;
+#pragma unroll
+        for (uint32_t i = 0; i < kLhMaxQ; ++i)
+            if (excl < rank[i] && rank[i] <= incl) qbin[cell * nq + i] = x;
+        carry = __shfl(incl, 63);
+    }
+}
+
+// [lo, hi] of a bin (oracle/realtime.py bin_bounds)
+void lh_bin_bounds(uint32_t b, uint32_t m, int64_t* lo, int64_t* hi) {
+    if (b < (1u << m)) {
+        *lo = *hi = (int64_t)b;
+        return;
+    }
+    const uint32_t g = b >> m, mant = b & ((1u << m) - 1u);
+    const uint32_t e = g + m - 1u;
+    *lo = (int64_t)(((1ull << m) | mant) << (e - m));
+    *hi = *lo + (int64_t)(1ull << (e - m)) - 1;
+}
+
+}  // namespace
+}  // namespace zk
+
+using namespace zk;
+
+struct zk_lh {
+    int device = 0;
+    hipStream_t stream = nullptr;  // the bound ctx's while bound, else `own`
+    hipStream_t own = nullptr;
+    uint32_t S = 0, m = 4, bins = 0;
+    uint64_t cells = 0;
+    uint32_t* hist = nullptr;                // [cells][bins]
+    unsigned long long* dropped = nullptr;   // device: links dropped for their duration while bound
+    uint64_t reserved = 0;                   // records accumulated since reset (links <= records)
+    // quantiles_all: one pass of up to kLhMaxQ quantiles
+    double* q_dev = nullptr;
+    unsigned long long* q_cnt = nullptr;     // [cells]
+    uint32_t* q_bin = nullptr;               // [cells][kLhMaxQ]
+    std::string err;
+};
+
+namespace {
+
+zk_status hfail(zk_lh* h, zk_status s, const std::string& m) {
+    if (h) h->err = m;
+    return s;
+}
+
+#define LH_HIP(h, call)                                                                            \
+    do {                                                                                           \
+        hipError_t _e = (call);                                                                    \
+        if (_e != hipSuccess) return hfail(h, is_refusal(_e) ? ZK_ERR_CAPACITY : ZK_ERR_HIP,       \
+                                           std::string(#call) + ": " + launch_error_str(_e));      \
+    } while (0)
+
+zk_status check_q(zk_lh* h, const double* q, uint32_t nq, const int64_t* lo, const int64_t* hi) {
+    if (nq && (!q || !lo || !hi)) return hfail(h, ZK_ERR_INVALID_ARG, "null array");
+    for (uint32_t i = 0; i < nq; ++i)
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return hfail(h, ZK_ERR_INVALID_ARG, "quantile outside [0, 1]");
+    return ZK_OK;
+}
+
+}  // namespace
+
+namespace zk {
+
+uint32_t lh_tile_shift(uint32_t bins, uint32_t cb_shift) {
+    uint32_t t = 0;
+    while (t < cb_shift && (2ull << t) * bins * 4 <= kLhLdsBudget) ++t;
+    return t;
+}
+
+void lh_join_args(zk_lh* h, JoinArgs* a) {
+    a->lh_hist = h->hist;
+    a->lh_bins = h->bins;
+    a->lh_m = h->m;
+}
+
+hipError_t lh_note_dropped(zk_lh* h, const unsigned long long* stats, int sign) {
+    return launch_checked("k_lh_note_dropped", k_lh_note_dropped, dim3(1), dim3(kStatShards), 0, h->stream, stats, sign,
+                          h->dropped);
+}
+
+hipError_t lh_accumulate(zk_lh* h, const ReduceArgs& r) {
+    if (!r.lists) return hipSuccess;
+    if (!r.nb) {
+        const uint32_t grid = r.lists < 4096 ? r.lists : 4096;
+        return launch_checked("k_lh_lists", k_lh_lists, dim3(grid), dim3(256), 0, h->stream, r.links, r.counts, r.stride,
+                              r.lists, h->cells, h->hist, h->bins, h->m);
+    }
+    LhArgs a{};
+    a.sorted = r.sorted;
+    a.bucket_base = r.bucket_base;
+    a.cb_shift = r.cb_shift;
+    a.cells = h->cells;
+    a.hist = h->hist;
+    a.bins = h->bins;
+    a.m = h->m;
+    a.tshift = lh_tile_shift(h->bins, r.cb_shift);
+    a.nsub = 1u << (r.cb_shift - a.tshift);
+    const uint32_t pairs = r.nb * a.nsub;
+    a.splits = pairs >= kLhTargetWGs ? 1u : (kLhTargetWGs + pairs - 1) / pairs;
+    const size_t lds = ((size_t)h->bins << a.tshift) * 4;
+    return launch_checked("k_lh_tiles", k_lh_tiles, dim3(pairs * a.splits), dim3(kLhWG), lds, h->stream, a);
+}
+
+uint64_t lh_reserved(const zk_lh* h) { return h->reserved; }
+void lh_reserve(zk_lh* h, uint64_t n) { h->reserved += n; }
+int lh_device(const zk_lh* h) { return h->device; }
+uint32_t lh_services(const zk_lh* h) { return h->S; }
+void lh_set_stream(zk_lh* h, hipStream_t s) {
+    hipStream_t ns = s ? s : h->own;
+    if (ns != h->stream) {
+        if (h->stream) (void)hipStreamSynchronize(h->stream);
+        h->stream = ns;
+    }
+}
+
+zk_status lh_allreduce(zk_lh* h, zk_comm* comm) {
+    if (!comm) return hfail(h, ZK_ERR_INVALID_ARG, "null communicator");
+    LH_HIP(h, hipSetDevice(h->device));
+    // bins and the drop counter by SUM, on the handle's (bound ctx's) stream
+    zk_status st = comm_allreduce(comm, h->hist, h->cells * h->bins, kCommU32, kCommSum, h->device, h->stream, &h->err);
+    if (st == ZK_OK) st = comm_allreduce(comm, h->dropped, 1, kCommU64, kCommSum, h->device, h->stream, &h->err);
+    return st;
+}
+
+}  // namespace zk
+
+extern "C" {
+
+zk_status zk_lh_create(const zk_lh_config* cfg, zk_lh** out) {
+    ZK_GUARD_BEGIN
+    if (!cfg || !out) return ZK_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (cfg->num_services == 0 || cfg->num_services > kMaxServices) return ZK_ERR_INVALID_ARG;
+    if (cfg->sub_bits != 0 && (cfg->sub_bits < 2 || cfg->sub_bits > 7)) return ZK_ERR_INVALID_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || cfg->device < 0 || cfg->device >= ndev) return ZK_ERR_NO_DEVICE;
+    if (hipSetDevice(cfg->device) != hipSuccess) return ZK_ERR_HIP;
+    zk_lh* h = new zk_lh();
+    h->device = cfg->device;
+    h->S = cfg->num_services;
+    h->m = cfg->sub_bits ? cfg->sub_bits : 4u;
+    h->bins = rt_nbins(h->m);
+    h->cells = (uint64_t)h->S * h->S;
+    if (cfg->stream) {
+        h->stream = (hipStream_t)cfg->stream;
+    } else if (hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking) != hipSuccess) {
+        delete h;
+        return ZK_ERR_HIP;
+    } else {
+        h->stream = h->own;
+    }
+    // the whole state at once: no accumulate ever allocates
+    if (hipMalloc(&h->hist, h->cells * h->bins * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        h->hist = nullptr;
+        zk_lh_destroy(h);
+        return ZK_ERR_CAPACITY;
+    }
+    if (hipMalloc(&h->dropped, 8) != hipSuccess || zk_lh_reset(h) != ZK_OK) {
+        (void)hipGetLastError();
+        zk_lh_destroy(h);
+        return ZK_ERR_HIP;
+    }
+    *out = h;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_lh_destroy(zk_lh* h) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    for (void* p : {(void*)h->hist, (void*)h->dropped, (void*)h->q_dev, (void*)h->q_cnt, (void*)h->q_bin})
+        if (p) (void)hipFree(p);
+    if (h->own) (void)hipStreamDestroy(h->own);
+    delete h;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+const char* zk_lh_last_error(const zk_lh* h) { return h ? h->err.c_str() : "null handle"; }
+
+zk_status zk_lh_reset(zk_lh* h) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    LH_HIP(h, hipSetDevice(h->device));
+    LH_HIP(h, hipMemsetAsync(h->hist, 0, h->cells * h->bins * 4, h->stream));
+    LH_HIP(h, hipMemsetAsync(h->dropped, 0, 8, h->stream));
+    h->reserved = 0;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_lh_geometry(const zk_lh* h, uint32_t* bins) {
+    if (!h || !bins) return ZK_ERR_INVALID_ARG;
+    *bins = h->bins;
+    return ZK_OK;
+}
+
+zk_status zk_lh_quantiles(zk_lh* h, uint32_t parent, uint32_t child, const double* q, uint32_t nq, int64_t* lo,
+                          int64_t* hi, uint64_t* count) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (parent >= h->S || child >= h->S) return hfail(h, ZK_ERR_SERVICE_RANGE, "service id >= num_services");
+    const zk_status cs = check_q(h, q, nq, lo, hi);
+    if (cs != ZK_OK) return cs;
+    LH_HIP(h, hipSetDevice(h->device));
+    // one row to the host, scanned there
+    std::vector<uint32_t> row(h->bins);
+    const uint64_t cell = (uint64_t)parent * h->S + child;
+    LH_HIP(h, hipMemcpyAsync(row.data(), h->hist + cell * h->bins, (uint64_t)h->bins * 4, hipMemcpyDeviceToHost, h->stream));
+    LH_HIP(h, hipStreamSynchronize(h->stream));
+    uint64_t N = 0;
+    for (uint32_t c : row) N += c;
+    if (count) *count = N;
+    for (uint32_t i = 0; i < nq; ++i) {
+        lo[i] = hi[i] = 0;
+        if (!N) continue;
+        uint64_t rank = (uint64_t)ceil(q[i] * (double)N);  // nearest rank, 1-based
+        if (rank < 1) rank = 1;
+        if (rank > N) rank = N;
+        uint64_t cum = 0;
+        for (uint32_t b = 0; b < h->bins; ++b) {
+            cum += row[b];
+            if (cum >= rank) {
+                lh_bin_bounds(b, h->m, &lo[i], &hi[i]);
+                break;
+            }
+        }
+    }
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_lh_quantiles_all(zk_lh* h, const double* q, uint32_t nq, int64_t* lo, int64_t* hi, uint64_t* count) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    const zk_status cs = check_q(h, q, nq, lo, hi);
+    if (cs != ZK_OK) return cs;
+    if (!nq && !count) return ZK_OK;
+    LH_HIP(h, hipSetDevice(h->device));
+    if (!h->q_bin) {
+        if (hipMalloc(&h->q_dev, kLhMaxQ * sizeof(double)) != hipSuccess || hipMalloc(&h->q_cnt, h->cells * 8) != hipSuccess ||
+            hipMalloc(&h->q_bin, h->cells * kLhMaxQ * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            for (void* p : {(void*)h->q_dev, (void*)h->q_cnt, (void*)h->q_bin})
+                if (p) (void)hipFree(p);
+            h->q_dev = nullptr;
+            h->q_cnt = nullptr;
+            h->q_bin = nullptr;
+            return hfail(h, ZK_ERR_CAPACITY, "no device memory for the quantile query (40 B per cell)");
+        }
+    }
+    std::vector<unsigned long long> cnt(h->cells);
+    std::vector<uint32_t> qb;
+    const uint32_t grid = (uint32_t)((h->cells + 3) / 4);
+    for (uint32_t i0 = 0; i0 < nq || i0 == 0; i0 += kLhMaxQ) {
+        const uint32_t k = nq - i0 < kLhMaxQ ? nq - i0 : kLhMaxQ;
+        if (k) LH_HIP(h, hipMemcpyAsync(h->q_dev, q + i0, k * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        LH_HIP(h, launch_checked("k_lh_quantiles", k_lh_quantiles, dim3(grid), dim3(256), 0, h->stream,
+                                 (const uint32_t*)h->hist, h->cells, h->bins, (const double*)h->q_dev, k, h->q_cnt, h->q_bin));
+        qb.resize((size_t)h->cells * k);
+        LH_HIP(h, hipMemcpyAsync(cnt.data(), h->q_cnt, h->cells * 8, hipMemcpyDeviceToHost, h->stream));
+        if (k) LH_HIP(h, hipMemcpyAsync(qb.data(), h->q_bin, h->cells * k * 4, hipMemcpyDeviceToHost, h->stream));
+        LH_HIP(h, hipStreamSynchronize(h->stream));  // (also: q was read before the next pass overwrites it)
+        for (uint64_t c = 0; c < h->cells; ++c) {
+            if (count) count[c] = cnt[c];
+            for (uint32_t i = 0; i < k; ++i) {
+                int64_t* l = lo + c * nq + i0 + i;
+                int64_t* u = hi + c * nq + i0 + i;
+                if (cnt[c])
+                    lh_bin_bounds(qb[c * k + i], h->m, l, u);
+                else
+                    *l = *u = 0;
+            }
+        }
+        if (!nq) break;
+    }
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_lh_read(zk_lh* h, uint64_t first_cell, uint64_t n_cells, uint32_t* out) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (first_cell > h->cells || n_cells > h->cells - first_cell) return hfail(h, ZK_ERR_INVALID_ARG, "cell range past S * S");
+    if (n_cells && !out) return hfail(h, ZK_ERR_INVALID_ARG, "null array");
+    LH_HIP(h, hipSetDevice(h->device));
+    if (n_cells)
+        LH_HIP(h, hipMemcpyAsync(out, h->hist + first_cell * h->bins, n_cells * h->bins * 4, hipMemcpyDeviceToHost, h->stream));
+    LH_HIP(h, hipStreamSynchronize(h->stream));
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_lh_partial(zk_lh* h, void** hist, uint64_t* bytes) {
+    if (!h || !hist || !bytes) return ZK_ERR_INVALID_ARG;
+    *hist = h->hist;
+    *bytes = h->cells * h->bins * 4;
+    return ZK_OK;
+}
+
+zk_status zk_lh_dropped(zk_lh* h, uint64_t* duration_range) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    LH_HIP(h, hipSetDevice(h->device));
+    unsigned long long d = 0;
+    LH_HIP(h, hipMemcpyAsync(&d, h->dropped, 8, hipMemcpyDeviceToHost, h->stream));
+    LH_HIP(h, hipStreamSynchronize(h->stream));
+    if (duration_range) *duration_range = d;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+}  // extern "C"

@@ -259,3 +259,132 @@ class RealtimeLinks:
             self._check(self._L.zk_rl_server_rpc_links(self._h, server, r, par.ctypes.data, dur.ctypes.data,
                                                        tid.ctypes.data, ids.ctypes.data, m, C.byref(n)))
         return par[:m], dur[:m], tid[:m], ids[:m]
+
+
+def link_hist_bins(m: int) -> int:
+    """Bins of the log-linear duration histogram with m mantissa bits over [0, 2^40) us."""
+    return (41 - m) << m
+
+
+def link_hist_bin_bounds(b: int, m: int) -> tuple[int, int]:
+    """[lo, hi] (us, inclusive) of bin b: the value itself below 2^m, else (exponent, top m mantissa
+    bits) -- the layout of zk_rt's histogram, which zk_lh shares."""
+    if b < (1 << m):
+        return b, b
+    e = (b >> m) + m - 1
+    lo = ((1 << m) | (b & ((1 << m) - 1))) << (e - m)
+    return lo, lo + (1 << (e - m)) - 1
+
+
+class LinkHistogram:
+    """Per-link duration histogram (zk_lh_*): for every (parent, child) edge of the dependency graph
+    the exact count of its links' child durations per log-linear bin, hence the p50/p99 a
+    DependencyLink's Moments cannot give. Bound to a DepsContext, every later accumulate feeds it from
+    the links the dependency path reduces anyway. State: uint32[S * S, bins] in HBM (S * S * bins * 4
+    bytes: 592 MB at S = 500 with the default sub_bits = 4), summed across traceId shards like the
+    table (partial() / Comm.allreduce_lh)."""
+
+    def __init__(self, num_services: int, *, device: int = 0, stream: int | None = None, sub_bits: int = 0):
+        self._L = _abi.lib()
+        cfg = _abi.zk_lh_config()
+        cfg.num_services = num_services
+        cfg.device = device
+        cfg.stream = stream
+        cfg.sub_bits = sub_bits
+        h = C.c_void_p()
+        st = self._L.zk_lh_create(C.byref(cfg), C.byref(h))
+        if st != _abi.ZK_OK:
+            raise _abi.ZkError(st, _abi.status_str(st))
+        self._h = h
+        self.num_services = num_services
+        self.m = sub_bits or 4
+        self.bins = self.geometry()
+        self._bound = None
+
+    def _check(self, st: int) -> None:
+        if st != _abi.ZK_OK:
+            raise _abi.ZkError(st, self._L.zk_lh_last_error(self._h).decode() or _abi.status_str(st))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self.unbind()
+            self._L.zk_lh_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def geometry(self) -> int:
+        """Bins per edge: (41 - m) << m."""
+        b = C.c_uint32()
+        self._check(self._L.zk_lh_geometry(self._h, C.byref(b)))
+        return int(b.value)
+
+    def bind(self, ctx) -> None:
+        st = self._L.zk_lh_bind(ctx.handle, self._h)
+        if st != _abi.ZK_OK:
+            raise _abi.ZkError(st, self._L.zk_last_error(ctx.handle).decode())
+        self._bound = ctx
+
+    def unbind(self) -> None:
+        if self._bound is not None and getattr(self._bound, "_h", None):
+            self._L.zk_lh_bind(self._bound.handle, None)
+        self._bound = None
+
+    def reset(self) -> None:
+        self._check(self._L.zk_lh_reset(self._h))
+
+    def quantiles(self, parent: int, child: int, qs=(0.5, 0.99)):
+        """([(lo, hi)] bin bounds holding each nearest-rank quantile of one edge, its link count)."""
+        q = np.ascontiguousarray(qs, dtype=np.float64)
+        lo = np.zeros(len(q), np.int64)
+        hi = np.zeros(len(q), np.int64)
+        cnt = C.c_uint64()
+        self._check(self._L.zk_lh_quantiles(self._h, parent, child, q.ctypes.data, len(q), lo.ctypes.data,
+                                            hi.ctypes.data, C.byref(cnt)))
+        return [(int(a), int(b)) for a, b in zip(lo, hi)], int(cnt.value)
+
+    def quantiles_all(self, qs=(0.5, 0.99)):
+        """(lo int64[S * S, nq], hi int64[S * S, nq], count uint64[S * S]) of every edge, cell =
+        parent * S + child, in one device pass (zk_lh_quantiles_all)."""
+        q = np.ascontiguousarray(qs, dtype=np.float64)
+        cells = self.num_services * self.num_services
+        lo = np.zeros((cells, len(q)), np.int64)
+        hi = np.zeros((cells, len(q)), np.int64)
+        cnt = np.zeros(cells, np.uint64)
+        self._check(self._L.zk_lh_quantiles_all(self._h, q.ctypes.data, len(q), lo.ctypes.data, hi.ctypes.data,
+                                                cnt.ctypes.data_as(_abi._U64P)))
+        return lo, hi, cnt
+
+    def read(self, first_cell: int = 0, n_cells: int | None = None) -> np.ndarray:
+        """Host copy uint32[n_cells, bins] of the rows of cells [first_cell, first_cell + n_cells)."""
+        if n_cells is None:
+            n_cells = self.num_services * self.num_services - first_cell
+        out = np.zeros((max(n_cells, 0), self.bins), np.uint32)
+        self._check(self._L.zk_lh_read(self._h, first_cell, n_cells, out.ctypes.data))
+        return out
+
+    def partial(self) -> tuple[int, int]:
+        """(device pointer, bytes) of the histogram: the buffer a u32 SUM all-reduce merges in place."""
+        p, b = C.c_void_p(), C.c_uint64()
+        self._check(self._L.zk_lh_partial(self._h, C.byref(p), C.byref(b)))
+        return int(p.value or 0), int(b.value)
+
+    def dropped(self) -> int:
+        """Links dropped for a duration >= 2^40 us while bound, since reset."""
+        d = C.c_uint64()
+        self._check(self._L.zk_lh_dropped(self._h, C.byref(d)))
+        return int(d.value)
