@@ -106,6 +106,13 @@ zk_status   zk_kv_phase_ms(zk_kv* kv, double out[4]);
  * nearest-rank quantile and its midpoint is within 2^-(m+1) relative of it. Counts are integers,
  * so it is order-independent and mergeable by SUM (RCCL all-reduce SUM, u32) -- which a
  * t-digest is not.
+ * Capacity: a bin is a u32 and holds at most 2^32 - 1 spans since reset. An accumulate that takes a
+ * bin past that is detected on the device (the bin's flush sees the wrap) and remembered in the
+ * handle: from then until zk_rt_reset, zk_rt_quantiles, zk_rt_quantiles_all and zk_rt_tdigest fail
+ * with ZK_ERR_CAPACITY (zk_rt_last_error says so) instead of answering from wrapped counts;
+ * zk_rt_distinct_traces and zk_rt_read are unaffected. Bins summed by the caller's own all-reduce
+ * over zk_rt_partial (or zk_rt_allreduce) are not seen by the handle: keeping every summed bin below
+ * 2^32 is the caller's bound, as it is for the counters of zk_kv_partial.
  * ------------------------------------------------------------------------------------------ */
 typedef struct zk_rt_config {
     uint32_t num_services;  /* S <= 4096 */

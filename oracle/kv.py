@@ -123,7 +123,9 @@ class KvOracle:
                 continue
             est = out.estimate(s, allk)
             o = np.lexsort((allk, -est.astype(np.int64)))[: out.cand]
-            out.lists[s] = [(int(allk[i]), int(est[i])) for i in o]
+            # a gathered entry whose key the summed counters never saw has estimate 0: it is no
+            # entry (est 0 marks an unused slot, zksketch.h), the device drops it
+            out.lists[s] = [(int(allk[i]), int(est[i])) for i in o if est[i] > 0]
         return out
 
     def topk(self, service: int, k: int) -> list[tuple[int, int]]:

@@ -108,7 +108,11 @@ __global__ __launch_bounds__(kRtWG) void k_rt_sketch(RtArgs a) {
     uint32_t* g_bin = a.hist + (uint64_t)s * a.nbins;
     for (uint32_t x = threadIdx.x; x < a.nbins; x += kRtWG) {
         const uint32_t c = s_bin[x];
-        if (c) atomicAdd(&g_bin[x], c);
+        if (!c) continue;
+        // a u32 bin that wraps is counted (the capacity rule of include/zksketch.h): c <= unit_items < 2^32,
+        // so the sum wrapped exactly when it came out below the value the atomic returned
+        const uint32_t old = atomicAdd(&g_bin[x], c);
+        if (old + c < old) atomicAdd(a.wrapped, 1ull);
     }
 }
 

@@ -26,7 +26,7 @@ struct zk_rt {
     uint32_t cus = 256;
     uint8_t* regs = nullptr;           // [S][2^p]
     uint32_t* hist = nullptr;          // [S][nbins]
-    unsigned long long* dropped = nullptr;  // [0] service range, [1] duration range, [2] scratch
+    unsigned long long* dropped = nullptr;  // [0] service range, [1] duration range, [2] scratch, [3] wrapped bins
     // K1 item lists: list w at w * stride, count[w]; list `grid` = spill items (capacity >= records)
     uint64_t* pay = nullptr;
     uint32_t* svc = nullptr;
@@ -101,6 +101,7 @@ zk_status sketch_items(zk_rt* r, const PartitionPlan& plan, bool lists, const ui
     a.nbins = r->nbins;
     a.regs = r->regs;
     a.hist = r->hist;
+    a.wrapped = r->dropped + 3;
     a.items = r->sorted;
     a.seg = r->seg;
     a.unit_base = r->unit_base;
@@ -267,9 +268,18 @@ void rt_set_stream(zk_rt* r, hipStream_t s) {
     }
 }
 
+// The capacity rule of the histogram (include/zksketch.h): once a u32 bin has wrapped (k_rt_sketch
+// counts it in dropped[3]) the bins no longer hold the counts, and every query that reads them fails
+// until zk_rt_reset. `wrapped` is the host copy of that word, made before the query's own sync.
+zk_status bins_ok(zk_rt* r, unsigned long long wrapped) {
+    if (!wrapped) return ZK_OK;
+    return rfail(r, ZK_ERR_CAPACITY, "a histogram bin counted >= 2^32 spans since reset");
+}
+
 // every service's HLL sums and the bins of up to kRtQueryMaxQ quantiles, one kernel and one copy
-// into the pinned mirror: row s of r->q_host = [z_lo, z_hi, zeros, N, bins...]
-zk_status rt_query(zk_rt* r, const double* q, uint32_t nq) {
+// into the pinned mirror: row s of r->q_host = [z_lo, z_hi, zeros, N, bins...]; *wrapped (optional):
+// the wrapped-bin count, copied under the same synchronisation
+zk_status rt_query(zk_rt* r, const double* q, uint32_t nq, unsigned long long* wrapped = nullptr) {
     if (!r->q_out) {
         RT_HIP(r, hipMalloc(&r->q_dev, kRtQueryMaxQ * sizeof(double)));
         RT_HIP(r, hipMalloc(&r->q_out, (uint64_t)r->S * (4 + kRtQueryMaxQ) * 8));
@@ -278,6 +288,7 @@ zk_status rt_query(zk_rt* r, const double* q, uint32_t nq) {
     if (nq) RT_HIP(r, hipMemcpyAsync(r->q_dev, q, nq * sizeof(double), hipMemcpyHostToDevice, r->stream));
     RT_HIP(r, launch_rt_query(r->regs, r->hist, r->S, r->p, r->nbins, r->q_dev, nq, r->q_out, r->stream));
     RT_HIP(r, hipMemcpyAsync(r->q_host, r->q_out, (uint64_t)r->S * (4 + nq) * 8, hipMemcpyDeviceToHost, r->stream));
+    if (wrapped) RT_HIP(r, hipMemcpyAsync(wrapped, r->dropped + 3, 8, hipMemcpyDeviceToHost, r->stream));
     RT_HIP(r, hipStreamSynchronize(r->stream));
     return ZK_OK;
 }
@@ -444,7 +455,9 @@ zk_status zk_rt_quantiles_all(zk_rt* r, const double* q, uint32_t nq, int64_t* l
     RT_HIP(r, hipSetDevice(r->device));
     for (uint32_t i0 = 0; i0 < nq || (i0 == 0 && count); i0 += kRtQueryMaxQ) {
         const uint32_t k = nq - i0 < kRtQueryMaxQ ? nq - i0 : kRtQueryMaxQ;
-        const zk_status st = rt_query(r, q + i0, k);
+        unsigned long long wrapped = 0;
+        zk_status st = rt_query(r, q + i0, k, &wrapped);
+        if (st == ZK_OK) st = bins_ok(r, wrapped);
         if (st != ZK_OK) return st;
         for (uint32_t s = 0; s < r->S; ++s) {
             const unsigned long long* o = r->q_host + (uint64_t)s * (4 + k);
@@ -476,7 +489,10 @@ zk_status zk_rt_quantiles(zk_rt* r, uint32_t service, const double* q, uint32_t 
     std::vector<uint32_t> h(r->nbins);
     RT_HIP(r, hipMemcpyAsync(h.data(), r->hist + (uint64_t)service * r->nbins, (uint64_t)r->nbins * 4,
                              hipMemcpyDeviceToHost, r->stream));
+    unsigned long long wrapped = 0;
+    RT_HIP(r, hipMemcpyAsync(&wrapped, r->dropped + 3, 8, hipMemcpyDeviceToHost, r->stream));
     RT_HIP(r, hipStreamSynchronize(r->stream));
+    if (bins_ok(r, wrapped) != ZK_OK) return ZK_ERR_CAPACITY;
     uint64_t N = 0;
     for (uint32_t c : h) N += c;
     if (count) *count = N;
@@ -512,7 +528,10 @@ zk_status zk_rt_tdigest(zk_rt* r, uint32_t service, double compression, double* 
     std::vector<uint32_t> h(r->nbins);
     RT_HIP(r, hipMemcpyAsync(h.data(), r->hist + (uint64_t)service * r->nbins, (uint64_t)r->nbins * 4,
                              hipMemcpyDeviceToHost, r->stream));
+    unsigned long long wrapped = 0;
+    RT_HIP(r, hipMemcpyAsync(&wrapped, r->dropped + 3, 8, hipMemcpyDeviceToHost, r->stream));
     RT_HIP(r, hipStreamSynchronize(r->stream));
+    if (bins_ok(r, wrapped) != ZK_OK) return ZK_ERR_CAPACITY;
     std::vector<Centroid> c;
     int64_t vmin, vmax;
     uint64_t N;

@@ -128,6 +128,7 @@ struct RtArgs {
     uint32_t S, p, m, nbins;
     uint8_t* regs;               // [S][2^p] (u32-aligned rows)
     uint32_t* hist;              // [S][nbins]
+    unsigned long long* wrapped; // bin additions that wrapped past 2^32 - 1 since reset
     const uint64_t* items;       // service-contiguous payloads
     const uint64_t* seg;         // [S+1]
     const uint32_t* unit_base;   // [S+1]
