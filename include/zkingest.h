@@ -52,13 +52,18 @@ extern "C" {
 #define ZK_INGEST_ONE_THREAD 2u    /* host decoder: decode on the calling thread only (by default up to
                                       16 threads decode contiguous ranges; records, items, service ids
                                       and errors are the same either way) */
-#define ZK_INGEST_SPAN_NAMES 4u     /* host decoder: keep a span-name dictionary (ids in order of first
-                                      appearance, the same for any thread count, names compared byte for
-                                      byte) and write id + 1 into bits 16..31 of every record's flags
-                                      (zkagg.h ZK_F_NAME_SHIFT); "" and "Unknown" get 0. At most 65535
-                                      names: a batch that needs more fails with ZK_ERR_CAPACITY. Without
-                                      the flag those bits are 0. The device decoder has no span-name
-                                      dictionary and returns ZK_ERR_UNSUPPORTED for this flag. */
+#define ZK_INGEST_SPAN_NAMES 4u     /* keep a span-name dictionary (names compared byte for byte, any
+                                      bytes) and write id + 1 into bits 16..31 of every record's flags
+                                      (zkagg.h ZK_F_NAME_SHIFT); "" and "Unknown" (exactly these bytes) get
+                                      0 and are never in the dictionary. A batch that would take the
+                                      dictionary past its limit fails as a whole with ZK_ERR_CAPACITY.
+                                      Without the flag those bits are 0 and the dictionary is untouched.
+                                      Host decoder: ids in order of first appearance, the same for any
+                                      thread count; at most 65535 names.
+                                      Device decoder: only one made by zk_ingest_dev_create_names keeps a
+                                      span-name dictionary (at most max_span_names names); one made by
+                                      zk_ingest_dev_create returns ZK_ERR_UNSUPPORTED for this flag. Its
+                                      ids are NOT the host decoder's: see zk_ingest_dev_create_names. */
 /* Both decoders (host zk_ingest_spans, device zk_ingest_dev_spans) reject a Snappy fragment whose
  * header announces more than ZK_INGEST_MAX_FRAGMENT bytes, or more than the format can expand its
  * payload to (a 3-byte copy emits at most 64 bytes: < ZK_SNAPPY_MAX_EXPANSION x), before any
@@ -148,6 +153,31 @@ zk_status   zk_ingest_dev_num_services(const zk_ingest_dev* ing, uint32_t* n);
 zk_status   zk_ingest_dev_set_scratch(zk_ingest_dev* ing, uint64_t bytes);
 zk_status   zk_ingest_dev_service_name(const zk_ingest_dev* ing, uint32_t id, char* buf, uint64_t cap,
                                        uint64_t* len);
+/* A device decoder that also keeps a span-name dictionary in HBM (a second table, a name arena and
+ * a second publish list), so that ZK_INGEST_SPAN_NAMES works on all three decode calls and both
+ * codecs. max_span_names: 1..65535 (ZK_F_NAME_MASK: id + 1 must fit 16 bits), else
+ * ZK_ERR_INVALID_ARG before any device is touched. Without the flag such a decoder runs the same
+ * kernels as one made by zk_ingest_dev_create.
+ *   - The dictionary is separate from the service dictionary (the same string may be in both with
+ *     unrelated ids) and persists across batches: a name keeps its id for the decoder's life.
+ *   - A batch's new names get ids in the order of their hash-table slots, as the service dictionary
+ *     does, not in order of first appearance: device ids are not the host decoder's ids, and any
+ *     comparison between the two goes through the names (zk_ingest_dev_span_name).
+ *   - A name enters the dictionary only through a record the batch accepts.
+ *   - A batch that would take the dictionary past max_span_names fails as a whole with
+ *     ZK_ERR_CAPACITY; the dictionary then holds exactly the names it held before, and a later batch
+ *     whose names fit decodes normally.
+ *   - Two different names with one 64-bit hash are an error (ZK_ERR_INVALID_SPAN), as for service names.
+ *   - The merge rule downstream (K1 kModeLinks) takes the MAXIMUM id over a span's fragments. Only
+ *     when the fragments of one span carry different names can a device-decoded and a host-decoded
+ *     stream therefore select different names for it; each choice is deterministic for its
+ *     dictionary (the reference's own pick depends on fragment order, Span.scala:153-158).
+ * zk_ingest_dev_num_span_names is 0 on a decoder without the dictionary, and zk_ingest_dev_span_name
+ * then returns ZK_ERR_INVALID_ARG, as for any id past the count; two-phase (buf NULL -> *len). */
+zk_status   zk_ingest_dev_create_names(int32_t device, void* stream, uint32_t max_services, uint32_t max_span_names,
+                                       zk_ingest_dev** out);
+zk_status   zk_ingest_dev_num_span_names(const zk_ingest_dev* ing, uint32_t* n);
+zk_status   zk_ingest_dev_span_name(const zk_ingest_dev* ing, uint32_t id, char* buf, uint64_t cap, uint64_t* len);
 
 /* ---- the Dependencies record on the wire ----------------------------------------------------
  * TBinaryProtocol thriftscala.Dependencies (zipkinDependencies.thrift:24-43) as the Cassandra

@@ -378,6 +378,9 @@ _SIGNATURES = [
     ("zk_ingest_dev_num_services", C.c_int, [_P, C.POINTER(C.c_uint32)]),
     ("zk_ingest_dev_set_scratch", C.c_int, [_P, C.c_uint64]),
     ("zk_ingest_dev_service_name", C.c_int, [_P, C.c_uint32, C.c_char_p, C.c_uint64, _U64P]),
+    ("zk_ingest_dev_create_names", C.c_int, [C.c_int32, _P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    ("zk_ingest_dev_num_span_names", C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    ("zk_ingest_dev_span_name", C.c_int, [_P, C.c_uint32, C.c_char_p, C.c_uint64, _U64P]),
     # include/zkstore.h: the Aggregates store surface (host side)
     ("zk_store_create", C.c_int, [C.c_uint32, C.POINTER(_P)]),
     ("zk_store_destroy", C.c_int, [_P]),

@@ -222,6 +222,51 @@ class Dictionary:
         return name in self._ids
 
 
+class DecoderDictionary:
+    """Read-only view of a decoder's dictionary with Dictionary's read interface: the service names
+    (kind="services") or the span names (kind="span_names") of a SpanDecoder or DeviceSpanDecoder.
+    The decoder owns the ids; the view reads the names it has not seen yet whenever the decoder's
+    count has grown (ids never change, so names already read stay). `id` is a lookup only: KeyError
+    for a name the decoder has not seen."""
+
+    def __init__(self, decoder, kind: str = "services"):
+        if kind not in ("services", "span_names"):
+            raise ValueError("kind is 'services' or 'span_names'")
+        self._dec = decoder
+        self._count = (lambda: decoder.num_services) if kind == "services" else (lambda: decoder.num_span_names)
+        self._name = decoder.service_name if kind == "services" else decoder.span_name
+        self._ids: Dict[str, int] = {}
+        self._names: List[str] = []
+
+    def _refresh(self) -> None:
+        n = self._count()
+        for i in range(len(self._names), n):
+            name = self._name(i)
+            self._names.append(name)
+            self._ids.setdefault(name, i)
+
+    def id(self, name: str) -> int:
+        self._refresh()
+        return self._ids[name]
+
+    def get(self, name: str) -> Optional[int]:
+        self._refresh()
+        return self._ids.get(name)
+
+    def name(self, i: int) -> str:
+        if i >= len(self._names):
+            self._refresh()
+        return self._names[i]
+
+    def __len__(self) -> int:
+        self._refresh()
+        return len(self._names)
+
+    def __contains__(self, name: str) -> bool:
+        self._refresh()
+        return name in self._ids
+
+
 class Aggregates:
     """trait Aggregates (Aggregates.scala:26-37)."""
 
@@ -321,6 +366,12 @@ class _DeviceLinkWindow:
     def add(self, cols, clustered: bool) -> None:
         self.ctx.accumulate(cols, clustered=clustered, verify=False)
 
+    def add_device(self, cols, clustered: bool) -> None:
+        """DeviceColumns: the accumulate is asynchronous and reads them in place, so wait for the
+        ctx to drain them before the caller lets them go"""
+        self.ctx.accumulate(cols, clustered=clustered, verify=False)
+        self.ctx.sync()
+
     def server_links(self, server: int):
         self.ctx.sync()
         return self.rl.server_links(server)
@@ -364,15 +415,24 @@ class GpuRealtimeAggregates(RealtimeAggregates):
     Without `rpcs` the argument is ignored and both answers cover every rpc of the server.
     `window_factory(num_services)` builds a window (default: the device); the CPU tests pass the
     oracle's. The number of services is fixed when the store is constructed, as in the JVM class: a
-    query for a service added to the dictionary later answers {}."""
+    query for a service added to the dictionary later answers {} -- unless `num_services` sizes the
+    store for the ids to come.
+
+    Stored fragments already in HBM go in through `accumulate_stored` and a names-capable
+    DeviceSpanDecoder, with no host decode. The store for that path is built over the decoder's own
+    dictionaries, which start empty and fill as batches arrive:
+        dec = DeviceSpanDecoder(S, max_span_names=R)
+        store = GpuRealtimeAggregates(DecoderDictionary(dec), rpcs=DecoderDictionary(dec, "span_names"),
+                                      num_services=dec.max_services)"""
 
     def __init__(self, services: Dictionary, *, window_us: int = 3_600_000_000, keep: int = 24, device: int = 0,
-                 window_factory=None, rpcs: Optional[Dictionary] = None):
+                 window_factory=None, rpcs: Optional[Dictionary] = None, num_services: Optional[int] = None):
         if window_us <= 0 or keep <= 0:
             raise ValueError("window_us and keep must be positive")
         self.services = services
         self.rpcs = rpcs
-        self._num_services = max(1, len(services))
+        self.device = device
+        self._num_services = max(1, len(services)) if num_services is None else int(num_services)
         self.window_us = int(window_us)
         self.keep = int(keep)
         self._factory = window_factory or (lambda S: _DeviceLinkWindow(S, device))
@@ -391,6 +451,23 @@ class GpuRealtimeAggregates(RealtimeAggregates):
     def accumulate(self, cols, timestamp_us: int, *, clustered: bool = False) -> None:
         """One batch of span fragments (service ids from `services`) into the window of timestamp_us."""
         self._window(timestamp_us, True).add(cols, clustered)
+
+    def accumulate_stored(self, decoder, buf, offsets, n: int, timestamp_us: int, *, snappy: bool = True,
+                          strict: bool = True, clustered: bool = False) -> int:
+        """One batch of STORED fragments already in HBM (buf uint8, offsets int64[n + 1]: torch tensors
+        on the device) into the window of timestamp_us: decoded on the device by `decoder` (a
+        DeviceSpanDecoder made with max_span_names > 0, whose dictionaries `services` and `rpcs` view)
+        with span_names=True, the columns handed to the window's context in place. Returns the
+        number of fragments the decoder rejected (lenient mode). The call returns once the context
+        has consumed the columns; nothing of the batch is referenced afterwards."""
+        import torch
+
+        # the caller's tensors may still be in flight on its stream; the decoder has its own
+        torch.cuda.current_stream(self.device).synchronize()
+        cols, rejected = decoder.decode_device(buf, offsets, n, snappy=snappy, strict=strict, span_names=True)
+        if cols.n:  # (the decode is synchronous: the columns are complete)
+            self._window(timestamp_us, True).add_device(cols.slice(0, cols.n), clustered)
+        return rejected
 
     def _rows(self, timeStamp: int, serverServiceName: str, rpcName: str):
         win = self._window(timeStamp, False)

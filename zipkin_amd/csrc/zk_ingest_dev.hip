@@ -17,6 +17,15 @@
 //   (hipcub scan)       of accepted records -> output positions
 //   D5 k_ing_compact    accepted records -> the caller's columns, input order kept
 //
+// Span names (ZK_INGEST_SPAN_NAMES on a decoder made by zk_ingest_dev_create_names) take the same
+// route through a second dictionary of the same shape: the kNames builds of D2 capture the name
+// field, resolve it against the name table and OR id + 1 into the record's flags, or publish it to
+// a second list; D3 / D4 run over that list through names_view() (k_ing_dict_insert_x /
+// k_ing_lookup_x), the host gives new slots their ids (dict_assign_ids, which also takes a batch's
+// claims back when they would pass max_span_names), and k_ing_name_flags writes the ids D4 found
+// into the flags before D5. Without the flag the kNames = false kernels run: the code before the
+// span names existed.
+//
 // Every byte read is bounds-checked: corrupt input marks the fragment undecodable, never faults.
 #include <string.h>
 
@@ -485,6 +494,52 @@ struct IngArgs {
     uint32_t ck_cap;             // chunks per kind
 };
 
+// ---- span names (ZK_INGEST_SPAN_NAMES on a decoder made by zk_ingest_dev_create_names) ----
+// A second kernel argument of the decoders, so that IngArgs keeps its size (the items builds copy
+// it to the stack). The name dictionary is a second table of the same shape as the service one and
+// its fields carry the same names (resolve16_id reads either). D2 resolves a name the table already
+// holds and ORs id + 1 into the record's flags; any other name is published here, and D3 / D4 run
+// over the list through names_view() below.
+struct IngNames {
+    uint64_t* nm_hash;           // per fragment: 0 = nothing published
+    uint64_t* nm_ptr;            // device address of the span name's bytes (scratch or input buffer)
+    uint32_t* nm_len;
+    uint32_t* nm_id;             // dictionary id after D4 (kNoId until then)
+    uint32_t* npub;              // fragments that published a span name (count in *npub_n), n entries
+    unsigned long long* npub_n;
+    unsigned long long* nclaims; // name-table slots D3 claimed in this batch
+    uint64_t n;                  // fragments in the batch (the list's capacity)
+    uint64_t* d_key;             // the name table (as IngArgs::d_key .. max_services)
+    uint32_t* d_id;
+    uint64_t* d_ptr;
+    uint32_t* d_len;
+    const uint8_t* d_name16;
+    uint32_t d_mask;
+    uint32_t max_services;       // max_span_names
+};
+
+// The span names as "fragments" of D3 / D4 (host side): the per-fragment name arrays and the name
+// table in the places of the service ones; status and keep stay the fragments' own, so a name
+// enters the dictionary only through an accepted record and a hash collision marks the fragment.
+inline IngArgs names_view(const IngArgs& a, const IngNames& nn) {
+    IngArgs v = a;
+    v.svc_hash = nn.nm_hash;
+    v.name_ptr = nn.nm_ptr;
+    v.name_len = nn.nm_len;
+    v.svc = nn.nm_id;
+    v.pub = nn.npub;
+    v.pub_n = nn.npub_n;
+    v.claims = nn.nclaims;
+    v.d_key = nn.d_key;
+    v.d_id = nn.d_id;
+    v.d_ptr = nn.d_ptr;
+    v.d_len = nn.d_len;
+    v.d_name16 = nn.d_name16;
+    v.d_mask = nn.d_mask;
+    v.max_services = nn.max_services;
+    return v;
+}
+
 // A fragment's first bytes (its Snappy header varint is at most 5), issued as independent loads:
 // one round trip. Bytes past the fragment read as 0x80 (a continuation), so they never end it.
 __device__ __forceinline__ void head_bytes(const IngArgs& a, bool have, uint64_t b, uint64_t e, uint32_t h[5]) {
@@ -551,9 +606,10 @@ __device__ __forceinline__ void read_endpoint(DRdT<P>& r, P* name, uint32_t* nle
 
 // The thrift walk of one decompressed Span at [src, src + len): validation (status on failure,
 // -1), the record columns, and the service name (1: *nm/*nl set; 0: the span has no service).
-template <class P>
+// kNames: *sn_out / *snl_out = the span name's bytes (the last name field wins, as in the host decoder).
+template <bool kNames, class P>
 __device__ __forceinline__ int parse_record(const IngArgs& a, uint64_t i, P src, uint64_t len,
-                                            const uint8_t** nm_out, uint32_t* nl_out) {
+                                            const uint8_t** nm_out, uint32_t* nl_out, P* sn_out, uint32_t* snl_out) {
     DRdT<P> r{src, src + len, true};
     int64_t trace = 0, id = 0, parent = 0;
     bool has_parent = false, has_name = false, invalid = false;
@@ -573,6 +629,12 @@ __device__ __forceinline__ int parse_record(const IngArgs& a, uint64_t i, P src,
             P s;
             uint32_t l;
             has_name = r.str(&s, &l);
+            if constexpr (kNames) {
+                if (has_name) {  // (inside [src, src + len): str checked the length against the end)
+                    *sn_out = s;
+                    *snl_out = l;
+                }
+            }
         } else if (fid == 4 && t == T_I64) {
             id = r.i64();
         } else if (fid == 5 && t == T_I64) {
@@ -752,8 +814,10 @@ __device__ __forceinline__ bool fits(uint32_t avail, uint32_t at, int32_t len) {
 
 // lay (for the item walk): [0] the first annotation's offset, [1] their count, [2] the first binary
 // annotation's offset, [3] their count
+template <bool kNames>
 __device__ __forceinline__ int parse_record_fast(const IngArgs& a, uint64_t i, const lds_u8* base, uint32_t p0,
-                                                 uint32_t len, uint32_t* nm_off, uint32_t* nl_out, uint32_t lay[4]) {
+                                                 uint32_t len, uint32_t* nm_off, uint32_t* nl_out, uint32_t lay[4],
+                                                 uint32_t* sn_off, uint32_t* snl_out) {
     constexpr int kNo = -3;
     const uint32_t e = p0 + len;
     uint32_t p = p0;
@@ -764,6 +828,10 @@ __device__ __forceinline__ int parse_record_fast(const IngArgs& a, uint64_t i, c
     const uint64_t trace = w1.be64<3>();
     const int32_t nlen = (int32_t)w1.be32<14>();
     if (!fits(e - p, 18u, nlen)) return kNo;
+    if constexpr (kNames) {
+        *sn_off = p + 18u;  // the span name: nlen bytes that end at or before e (fits)
+        *snl_out = (uint32_t)nlen;
+    }
     p += 18u + (uint32_t)nlen;
     // [0A 0004] id, [0A 0005] parent_id (optional), [0F 0006] [0C] count
     LWin<8> w2;
@@ -999,7 +1067,9 @@ __device__ __forceinline__ bool try_resolve(const IngArgs& a, uint64_t i, const 
 // name's first 16 bytes are loaded once (hashed and compared from registers), and the first probe
 // reads the slot's key, id, length and inline name bytes together. *h: the name's hash (for
 // publish_name when it does not resolve).
-__device__ __forceinline__ bool resolve16_id(const IngArgs& a, const uint8_t* nm, uint32_t nl, uint64_t* h_out,
+// T: IngArgs (the service dictionary) or IngNames (the span-name dictionary; the same field names)
+template <class T>
+__device__ __forceinline__ bool resolve16_id(const T& a, const uint8_t* nm, uint32_t nl, uint64_t* h_out,
                                              uint32_t* id_out) {
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     uint8_t u[16];
@@ -1080,6 +1150,41 @@ __device__ __forceinline__ void publish_name_h(const IngArgs& a, uint64_t i, con
     list_add(a.pub, a.pub_n, i);
 #endif
 }
+
+// ---- span names (the kNames builds of the decoders) ---------------------------------------------
+// "" and "Unknown" are the names mergeSpan never selects (Span.scala:153-158): id 0, no hash, never
+// in the dictionary. Exact bytes: "unknown" is a name.
+template <class P>
+__device__ __forceinline__ bool name_is_none(P s, uint32_t l) {
+    if (l == 0) return true;
+    if (l != 7) return false;
+    const char u[8] = "Unknown";
+    bool eq = true;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) eq &= s[j] == (uint8_t)u[j];
+    return eq;
+}
+
+// A span name the table does not resolve yet, for D3 / D4 (names_view): p is global memory that
+// lives until the batch ends (the scratch or the input buffer). Called once per fragment, by the
+// attempt that accepts it (right before keep = 1), so the list never holds more than n entries;
+// the store is checked all the same.
+__device__ __forceinline__ void publish_span_name(const IngNames& a, uint64_t i, const uint8_t* p, uint32_t l, uint64_t h) {
+    a.nm_hash[i] = h;
+    a.nm_ptr[i] = (uint64_t)(uintptr_t)p;
+    a.nm_len[i] = l;
+    a.nm_id[i] = kNoId;
+    const unsigned long long mask = __ballot(1);
+    const uint32_t lane = __lane_id();
+    const uint32_t leader = (uint32_t)__ffsll(mask) - 1u;
+    unsigned long long base = 0;
+    if (lane == leader) base = atomicAdd(a.npub_n, (unsigned long long)__popcll(mask));
+    base = __shfl(base, (int)leader);
+    const uint64_t at = base + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+    if (at < a.n) a.npub[at] = (uint32_t)i;
+}
+
+__device__ __forceinline__ uint32_t name_bits(uint32_t id) { return (id + 1u) << ZK_F_NAME_SHIFT; }
 
 // ---- the span indexer's items (zk_ingest_dev_spans_items) ---------------------------------------
 // CassieSpanStore.scala:214-242 as the host decoder restates it (zk_ingest.cpp, "indexer items"):
@@ -1467,7 +1572,10 @@ __device__ __forceinline__ bool g_same_value(const GAnn<P>& A, const GAnn<P>& B)
 }
 
 // gsrc: the global address of src (null: src is in LDS only)
-template <class P>
+// kBuild: the calling kernel's kNames. This function is not inlined, and one copy per decoder build
+// keeps the interprocedural passes from specialising it differently once two kernels share it (the
+// kNames = false kernels then compile exactly as they did before the span-name builds existed).
+template <int kBuild, class P>
 __device__ void items_generic(const IngArgs& a, uint64_t i, ItemState& st, P src, uint64_t len, const uint8_t* gsrc,
                               const uint8_t* snm, uint32_t snl, bool snamed, uint32_t* ch) {
     auto G = [&](P p) -> const uint8_t* { return gsrc ? gsrc + (p - src) : nullptr; };
@@ -1518,12 +1626,13 @@ __device__ __forceinline__ void items_failed(const IngArgs& a, uint64_t i, const
 }
 
 // D2 (global memory): a fragment marked `mode` (kStDefer by the LDS kernel, or kStNoScratch)
-template <bool kItems>
-__device__ __forceinline__ void ing_decode_one(const IngArgs& a, uint64_t i, uint32_t mode) {
+template <bool kItems, bool kNames>
+__device__ __forceinline__ void ing_decode_one(const IngArgs& a, const IngNames& nn, uint64_t i, uint32_t mode) {
     if (a.status[i] != mode) return;
     a.status[i] = kStOk;
     a.keep[i] = 0u;
     a.svc_hash[i] = 0ull;
+    if constexpr (kNames) nn.nm_hash[i] = 0ull;
     const uint64_t b = a.offsets[i], e = a.ends[i];
     const uint8_t* src = a.buf + b;
     uint64_t len = e - b;
@@ -1549,15 +1658,29 @@ __device__ __forceinline__ void ing_decode_one(const IngArgs& a, uint64_t i, uin
     }
     const uint8_t* nm;
     uint32_t nl;
-    const int r = parse_record(a, i, src, len, &nm, &nl);
+    const uint8_t* sn = nullptr;
+    uint32_t snl = 0;
+    const int r = parse_record<kNames>(a, i, src, len, &nm, &nl, &sn, &snl);
     if (r < 0) return;
     if (r) publish_name(a, i, nm, nl);
     if constexpr (kItems) {  // a deferred fragment's first attempt (skips 0), or a failed one's next
         ItemState st{{0u, 0u}, {a.skip_kv[i], a.skip_an[i]}, false, {0ull, 0ull}};
-        items_generic(a, i, st, src, len, src, nm, nl, r == 1, nullptr);
+        items_generic<kNames ? 1 : 0>(a, i, st, src, len, src, nm, nl, r == 1, nullptr);
         if (st.fail) {
             items_failed(a, i, st);
             return;
+        }
+    }
+    if constexpr (kNames) {
+        // the span name (sn is set: a record has a name) lies in the decompressed Span in the scratch
+        // or in the input buffer, global memory either way; nothing after this can fail the attempt
+        if (sn && !name_is_none(sn, snl)) {
+            uint64_t h;
+            uint32_t id;
+            if (resolve16_id(nn, sn, snl, &h, &id))
+                a.flags[i] |= name_bits(id);
+            else
+                publish_span_name(nn, i, sn, snl, h);
         }
     }
     a.keep[i] = 1u;
@@ -1565,14 +1688,15 @@ __device__ __forceinline__ void ing_decode_one(const IngArgs& a, uint64_t i, uin
 
 // the deferred fragments (the LDS decoder's list), or every fragment marked kStNoScratch
 // kItems: the items build of the decoders (zk_ingest_dev_spans_items), compiled apart so that the
-// records-only kernels keep their registers
-template <bool kItems>
-__global__ __launch_bounds__(kIngWG) void k_ing_decode(IngArgs a, uint32_t mode) {
+// records-only kernels keep their registers; kNames: the span-name builds (ZK_INGEST_SPAN_NAMES),
+// apart for the same reason
+template <bool kItems, bool kNames>
+__global__ __launch_bounds__(kIngWG) void k_ing_decode(IngArgs a, uint32_t mode, IngNames nn) {
     if (mode == kStDefer) {
-        ING_FOR_LIST(a.def, a.def_n, i) ing_decode_one<kItems>(a, i, mode);
+        ING_FOR_LIST(a.def, a.def_n, i) ing_decode_one<kItems, kNames>(a, nn, i, mode);
     } else {
         for (uint64_t i = (uint64_t)blockIdx.x * kIngWG + threadIdx.x; i < a.n; i += (uint64_t)gridDim.x * kIngWG)
-            ing_decode_one<kItems>(a, i, mode);
+            ing_decode_one<kItems, kNames>(a, nn, i, mode);
     }
 }
 
@@ -1848,8 +1972,8 @@ __device__ __forceinline__ uint32_t copy_blocks(const uint8_t* buf, uint64_t b, 
     return h && e > b ? (uint32_t)((e - b + mis + 15) >> 4) : 0u;
 }
 
-template <bool kItems>
-__global__ __launch_bounds__(kLdsWG) void k_ing_decode_lds(IngArgs a) {
+template <bool kItems, bool kNames>
+__global__ __launch_bounds__(kLdsWG) void k_ing_decode_lds(IngArgs a, IngNames nn) {
     constexpr bool kPre = ZK_ING_PREFETCH && !kItems;  // (the items build has no registers for it)
     uint64_t known[2] = {0ull, 0ull};  // items: the lane's last string hashes found in the set
     __shared__ __align__(16) uint8_t s_buf[kLdsBudget];
@@ -1932,6 +2056,7 @@ __global__ __launch_bounds__(kLdsWG) void k_ing_decode_lds(IngArgs a) {
         if (lane < k && have) {
             a.keep[i] = 0u;
             a.svc_hash[i] = 0ull;
+            if constexpr (kNames) nn.nm_hash[i] = 0ull;
             if constexpr (kItems) {
                 a.skip_kv[i] = 0u;
                 a.skip_an[i] = 0u;
@@ -1997,11 +2122,15 @@ __global__ __launch_bounds__(kLdsWG) void k_ing_decode_lds(IngArgs a) {
                 const lds_u8* const lbase = (const lds_u8*)s_buf;
                 const uint32_t p0 = (uint32_t)(src - lbase);
                 uint32_t nmo, nl, lay[4];
-                int r = parse_record_fast(a, i, lbase, p0, (uint32_t)len, &nmo, &nl, lay);
+                uint32_t sno = 0, snl = 0;  // the span name: snl bytes at LDS offset sno, inside the Span
+                int r = parse_record_fast<kNames>(a, i, lbase, p0, (uint32_t)len, &nmo, &nl, lay, &sno, &snl);
                 const bool fast = r != -3;
                 if (r == -3) {  // not the canonical layout: the generic walk
                     const uint8_t* gnm = nullptr;
-                    r = parse_record(a, i, src, len, &gnm, &nl);
+                    const lds_u8* gsn = lbase;
+                    snl = 0;
+                    r = parse_record<kNames>(a, i, src, len, &gnm, &nl, &gsn, &snl);
+                    sno = (uint32_t)(gsn - lbase);
                     nmo = (r == 1 && gnm != (const uint8_t*)a.unknown) ? (uint32_t)(gnm - (const uint8_t*)lbase)
                                                                        : ~0u;
                 }
@@ -2009,6 +2138,34 @@ __global__ __launch_bounds__(kLdsWG) void k_ing_decode_lds(IngArgs a) {
                 const uint8_t* nm = unknown ? a.unknown : (const uint8_t*)(lbase + nmo);
                 if (unknown) nl = sizeof(kUnknown) - 1;
                 ING_STAMP(3);
+                // the span name: an id the table already holds goes into the record below; any other
+                // name is copied out of this lane's LDS bytes (Snappy) and published below, once the
+                // attempt can no longer fail. A failed copy-out fails the attempt before anything of
+                // the fragment is published (kStNoScratch: decoded again after the scratch grows).
+                uint32_t snbits = 0;
+                uint64_t snh = 0;
+                const uint8_t* sng = nullptr;  // non-null: publish
+                if constexpr (kNames) {
+                    if (r >= 0 && !name_is_none(lbase + sno, snl)) {
+                        const uint8_t* sn = (const uint8_t*)(lbase + sno);
+                        uint32_t id;
+                        if (resolve16_id(nn, sn, snl, &snh, &id)) {
+                            snbits = name_bits(id);
+                        } else if (a.snappy) {
+                            uint8_t* gd = scratch_take(a, snl);
+                            if (gd) {
+#pragma clang loop vectorize(disable)
+                                for (uint32_t q = 0; q < snl; ++q) gd[q] = sn[q];
+                                sng = gd;
+                            } else {
+                                a.status[i] = kStNoScratch;
+                                r = -1;
+                            }
+                        } else {
+                            sng = a.buf + b + (sno - p0);  // thrift codec: the name is in the input buffer
+                        }
+                    }
+                }
                 if (r >= 0) {
 #if ZK_ING_NAME16
                     uint64_t nh = 0;
@@ -2045,7 +2202,7 @@ __global__ __launch_bounds__(kLdsWG) void k_ing_decode_lds(IngArgs a) {
                         if (fast)
                             items_fast(a, i, st, lbase, lay, gx, nm, nl, r == 1, ch);
                         else
-                            items_generic(a, i, st, src, len, gx ? (const uint8_t*)(gx + p0) : nullptr, nm, nl, r == 1,
+                            items_generic<kNames ? 1 : 0>(a, i, st, src, len, gx ? (const uint8_t*)(gx + p0) : nullptr, nm, nl, r == 1,
                                           ch);
                         known[0] = st.known[0];
                         known[1] = st.known[1];
@@ -2053,6 +2210,12 @@ __global__ __launch_bounds__(kLdsWG) void k_ing_decode_lds(IngArgs a) {
                             items_failed(a, i, st);
                             r = -1;
                         }
+                    }
+                    if constexpr (kNames) {
+                        if (r >= 0 && sng)
+                            publish_span_name(nn, i, sng, snl, snh);
+                        else if (r >= 0 && snbits)
+                            a.flags[i] |= snbits;
                     }
                     if (r >= 0) a.keep[i] = 1u;
                 }
@@ -2228,6 +2391,16 @@ __global__ __launch_bounds__(kIngWG) void k_ing_count_extra(IngArgs x) {
     }
 }
 
+// Span names D2 published, after D4 (x = names_view: svc is the name id, n the list's capacity):
+// id + 1 into the record's flags, still at its fragment index (D5 moves the finished flags). A name
+// D2 resolved itself is in the flags already, so in the steady state this kernel is not launched.
+__global__ __launch_bounds__(kIngWG) void k_ing_name_flags(IngArgs x) {
+    ING_FOR_EXTRA(x, i) {
+        const uint32_t id = x.svc[i];
+        if (i < x.n && x.keep[i] && x.svc_hash[i] && id < x.max_services) x.flags[i] |= name_bits(id);
+    }
+}
+
 // item service references -> dictionary ids (after D4 of the fragments and the extra names; a.svc
 // still holds the records at their fragment index)
 __global__ __launch_bounds__(kIngWG) void k_ing_item_fixup(IngArgs a, uint64_t nkv, uint64_t nan) {
@@ -2290,13 +2463,12 @@ __global__ void k_ing_set_rehash(const uint64_t* __restrict__ old, uint64_t n_ol
 
 using namespace zk;
 
-struct zk_ingest_dev {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+// One persistent name dictionary: the open-addressing table on the device, the arena that holds its
+// names, and the host mirrors. A decoder has one for service names and, when it was made by
+// zk_ingest_dev_create_names, a second one for span names (max_services is then max_span_names).
+struct zk_ing_dict {
     uint32_t max_services = 0;
-    uint32_t table = 0;
-    // persistent dictionary
+    uint32_t table = 0;  // slots, a power of two >= 2 x max_services (0: no dictionary)
     uint64_t* d_key = nullptr;
     uint32_t* d_id = nullptr;
     uint64_t* d_ptr = nullptr;
@@ -2307,6 +2479,13 @@ struct zk_ingest_dev {
     uint64_t arena_cap = 0, arena_used = 0;
     std::vector<std::string> names;
     std::vector<uint32_t> slot_id;  // host mirror of d_id
+};
+
+struct zk_ingest_dev : zk_ing_dict {  // (the base: the service dictionary)
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    zk_ing_dict nm;  // the span-name dictionary (nm.table == 0: none, ZK_INGEST_SPAN_NAMES is refused)
     // per-batch scratch
     void* batch = nullptr;
     uint64_t batch_cap = 0;
@@ -2352,13 +2531,44 @@ zk_status dfail(zk_ingest_dev* g, zk_status s, const std::string& m) {
 
 uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
 
-}  // namespace
+// a dictionary's device arrays: an empty table of at least min_table slots (a power of two at least
+// 2 x max_ids, so a probe always ends at an empty slot), the arena starting with `head`
+hipError_t dict_alloc(zk_ing_dict* d, uint32_t max_ids, uint32_t min_table, const char* head, size_t head_len,
+                      hipStream_t s) {
+    d->max_services = max_ids;
+    uint32_t t = min_table;
+    while (t < 2 * max_ids) t <<= 1;
+    d->table = t;
+    d->slot_id.assign(t, kNoId);
+    d->name16.assign((size_t)t * 16, 0);
+    d->arena_cap = 1 << 16;
+    hipError_t e = hipMalloc(&d->d_key, (uint64_t)t * 8);
+    if (e == hipSuccess) e = hipMalloc(&d->d_id, (uint64_t)t * 4);
+    if (e == hipSuccess) e = hipMalloc(&d->d_ptr, (uint64_t)t * 8);
+    if (e == hipSuccess) e = hipMalloc(&d->d_len, (uint64_t)t * 4);
+    if (e == hipSuccess) e = hipMalloc(&d->d_name16, (uint64_t)t * 16);
+    if (e == hipSuccess) e = hipMemsetAsync(d->d_name16, 0, (uint64_t)t * 16, s);
+    if (e == hipSuccess) e = hipMalloc(&d->arena, d->arena_cap);
+    if (e == hipSuccess) e = hipMemsetAsync(d->d_key, 0, (uint64_t)t * 8, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d->d_id, 0xFF, (uint64_t)t * 4, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d->d_ptr, 0, (uint64_t)t * 8, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d->d_len, 0, (uint64_t)t * 4, s);
+    if (e == hipSuccess && head_len) e = hipMemcpyAsync(d->arena, head, head_len, hipMemcpyHostToDevice, s);
+    d->arena_used = head_len;
+    return e;
+}
 
-extern "C" {
+void dict_free(zk_ing_dict* d) {
+    hipFree(d->d_key);
+    hipFree(d->d_id);
+    hipFree(d->d_ptr);
+    hipFree(d->d_len);
+    hipFree(d->d_name16);
+    hipFree(d->arena);
+}
 
-zk_status zk_ingest_dev_create(int32_t device, void* stream, uint32_t max_services, zk_ingest_dev** out) {
-    ZK_GUARD_BEGIN
-    if (!out || max_services == 0 || max_services > (1u << 20)) return ZK_ERR_INVALID_ARG;
+// max_span_names == 0: no span-name dictionary (zk_ingest_dev_create)
+zk_status dev_create(int32_t device, void* stream, uint32_t max_services, uint32_t max_span_names, zk_ingest_dev** out) {
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || device < 0 || device >= ndev) return ZK_ERR_NO_DEVICE;
@@ -2367,12 +2577,6 @@ zk_status zk_ingest_dev_create(int32_t device, void* stream, uint32_t max_servic
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return ZK_ERR_NO_DEVICE;
     zk_ingest_dev* g = new zk_ingest_dev();
     g->device = device;
-    g->max_services = max_services;
-    uint32_t t = 1024;
-    while (t < 2 * max_services) t <<= 1;
-    g->table = t;
-    g->slot_id.assign(t, kNoId);
-    g->name16.assign((size_t)t * 16, 0);
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) {
         if (stream) {
@@ -2382,27 +2586,36 @@ zk_status zk_ingest_dev_create(int32_t device, void* stream, uint32_t max_servic
             g->own_stream = true;
         }
     }
-    g->arena_cap = 1 << 16;
-    if (e == hipSuccess) e = hipMalloc(&g->d_key, (uint64_t)t * 8);
-    if (e == hipSuccess) e = hipMalloc(&g->d_id, (uint64_t)t * 4);
-    if (e == hipSuccess) e = hipMalloc(&g->d_ptr, (uint64_t)t * 8);
-    if (e == hipSuccess) e = hipMalloc(&g->d_len, (uint64_t)t * 4);
-    if (e == hipSuccess) e = hipMalloc(&g->d_name16, (uint64_t)t * 16);
-    if (e == hipSuccess) e = hipMemsetAsync(g->d_name16, 0, (uint64_t)t * 16, g->stream);
-    if (e == hipSuccess) e = hipMalloc(&g->arena, g->arena_cap);
+    if (e == hipSuccess) e = dict_alloc(g, max_services, 1024, kUnknown, sizeof(kUnknown) - 1, g->stream);
+    if (e == hipSuccess && max_span_names) e = dict_alloc(&g->nm, max_span_names, 2, nullptr, 0, g->stream);
     if (e == hipSuccess) e = hipMalloc(&g->counts, 32 * 8);
     if (e == hipSuccess) e = hipHostMalloc((void**)&g->h_counts, 32 * 8, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMemsetAsync(g->d_key, 0, (uint64_t)t * 8, g->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(g->d_id, 0xFF, (uint64_t)t * 4, g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(g->arena, kUnknown, sizeof(kUnknown) - 1, hipMemcpyHostToDevice, g->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    g->arena_used = sizeof(kUnknown) - 1;
     if (e != hipSuccess) {
         zk_ingest_dev_destroy(g);
         return ZK_ERR_HIP;
     }
     *out = g;
     return ZK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+zk_status zk_ingest_dev_create(int32_t device, void* stream, uint32_t max_services, zk_ingest_dev** out) {
+    ZK_GUARD_BEGIN
+    if (!out || max_services == 0 || max_services > (1u << 20)) return ZK_ERR_INVALID_ARG;
+    return dev_create(device, stream, max_services, 0, out);
+    ZK_GUARD_END
+}
+
+zk_status zk_ingest_dev_create_names(int32_t device, void* stream, uint32_t max_services, uint32_t max_span_names,
+                                     zk_ingest_dev** out) {
+    ZK_GUARD_BEGIN
+    if (!out || max_services == 0 || max_services > (1u << 20)) return ZK_ERR_INVALID_ARG;
+    if (max_span_names == 0 || max_span_names > ZK_F_NAME_MASK) return ZK_ERR_INVALID_ARG;  // id + 1 fits 16 bits
+    return dev_create(device, stream, max_services, max_span_names, out);
     ZK_GUARD_END
 }
 
@@ -2411,12 +2624,8 @@ zk_status zk_ingest_dev_destroy(zk_ingest_dev* g) {
     if (!g) return ZK_ERR_INVALID_ARG;
     hipSetDevice(g->device);
     if (g->stream) hipStreamSynchronize(g->stream);
-    hipFree(g->d_key);
-    hipFree(g->d_id);
-    hipFree(g->d_ptr);
-    hipFree(g->d_len);
-    hipFree(g->d_name16);
-    hipFree(g->arena);
+    dict_free(g);
+    dict_free(&g->nm);
     hipFree(g->counts);
     hipHostFree(g->h_counts);
     hipFree(g->batch);
@@ -2556,15 +2765,105 @@ void bind_items(zk_ingest_dev* g, IngArgs& a, IngArgs& x) {
     x.pub_n = a.icnt + 3;
 }
 
+// After D3: ids for the slots a batch claimed in dictionary d, in slot order; their names gathered
+// into d's arena (one kernel) and mirrored on the host. limit > 0 (the span names): when the new
+// names would take the dictionary past it, the slots claimed in this batch -- those without an id
+// yet -- are released instead, *overflow is set and d holds exactly what it held before (a new slot
+// lies on no older key's probe path, since it was empty when that key was inserted).
+zk_status dict_assign_ids(zk_ingest_dev* g, zk_ing_dict* d, hipStream_t s, std::vector<uint8_t*>& retired, uint32_t limit,
+                          bool* overflow) {
+    std::vector<uint64_t> key(d->table), ptr(d->table);
+    std::vector<uint32_t> len(d->table);
+    ING_HIP(g, hipMemcpyAsync(key.data(), d->d_key, key.size() * 8, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipMemcpyAsync(ptr.data(), d->d_ptr, ptr.size() * 8, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipMemcpyAsync(len.data(), d->d_len, len.size() * 4, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipStreamSynchronize(s));
+    // the new slots in slot order, their names gathered into the arena by one kernel and read
+    // back in one copy
+    std::vector<uint32_t> fresh;
+    uint64_t total = 0;
+    for (uint32_t q = 0; q < d->table; ++q)
+        if (key[q] != kEmpty && d->slot_id[q] == kNoId) {
+            fresh.push_back(q);
+            total += len[q];
+        }
+    if (limit && d->names.size() + fresh.size() > limit) {
+        for (uint32_t q : fresh) key[q] = kEmpty;
+        ING_HIP(g, hipMemcpyAsync(d->d_key, key.data(), key.size() * 8, hipMemcpyHostToDevice, s));
+        ING_HIP(g, hipStreamSynchronize(s));
+        *overflow = true;
+        return ZK_OK;
+    }
+    const bool changed = !fresh.empty();
+    if (changed) {
+        if (d->arena_used + total > d->arena_cap) {
+            uint64_t cap = d->arena_cap;
+            while (cap < d->arena_used + total) cap *= 2;
+            uint8_t* na = nullptr;
+            ING_HIP(g, hipMalloc(&na, cap));
+            ING_HIP(g, hipMemcpyAsync(na, d->arena, d->arena_used, hipMemcpyDeviceToDevice, s));
+            // repoint the named slots at the new arena
+            for (uint32_t r = 0; r < d->table; ++r)
+                if (d->slot_id[r] != kNoId)
+                    ptr[r] = (uint64_t)(uintptr_t)na + (ptr[r] - (uint64_t)(uintptr_t)d->arena);
+            retired.push_back(d->arena);
+            d->arena = na;
+            d->arena_cap = cap;
+        }
+        const uint32_t m = (uint32_t)fresh.size();
+        std::vector<uint64_t> gsrc(m), goff(m);
+        std::vector<uint32_t> glen(m);
+        uint64_t at = d->arena_used;
+        for (uint32_t k = 0; k < m; ++k) {
+            gsrc[k] = ptr[fresh[k]];
+            goff[k] = at;
+            glen[k] = len[fresh[k]];
+            at += glen[k];
+        }
+        uint8_t* gt = nullptr;  // the gather's table: sources, arena offsets, lengths
+        ING_HIP(g, hipMalloc(&gt, (uint64_t)m * 20));
+        retired.push_back(gt);
+        ING_HIP(g, hipMemcpyAsync(gt, gsrc.data(), (uint64_t)m * 8, hipMemcpyHostToDevice, s));
+        ING_HIP(g, hipMemcpyAsync(gt + (uint64_t)m * 8, goff.data(), (uint64_t)m * 8, hipMemcpyHostToDevice, s));
+        ING_HIP(g, hipMemcpyAsync(gt + (uint64_t)m * 16, glen.data(), (uint64_t)m * 4, hipMemcpyHostToDevice, s));
+        ING_HIP(g, launch_checked("k_ing_gather_names", k_ing_gather_names, dim3((m + 255) / 256), dim3(256), 0, s,
+                                  (const uint64_t*)gt, (const uint64_t*)(gt + (uint64_t)m * 8),
+                                  (const uint32_t*)(gt + (uint64_t)m * 16), m, d->arena));
+        std::string bytes(total, '\0');
+        if (total)
+            ING_HIP(g, hipMemcpyAsync(&bytes[0], d->arena + d->arena_used, total, hipMemcpyDeviceToHost, s));
+        ING_HIP(g, hipStreamSynchronize(s));
+        for (uint32_t k = 0; k < m; ++k) {
+            const uint32_t q = fresh[k];
+            std::string nm = bytes.substr(goff[k] - d->arena_used, glen[k]);
+            ptr[q] = (uint64_t)(uintptr_t)(d->arena + goff[k]);
+            d->slot_id[q] = (uint32_t)d->names.size();
+            memcpy(&d->name16[(size_t)q * 16], nm.data(), std::min<size_t>(16, nm.size()));
+            d->names.push_back(std::move(nm));
+        }
+        d->arena_used = at;
+    }
+    if (changed) {
+        ING_HIP(g, hipMemcpyAsync(d->d_id, d->slot_id.data(), d->slot_id.size() * 4, hipMemcpyHostToDevice, s));
+        ING_HIP(g, hipMemcpyAsync(d->d_ptr, ptr.data(), ptr.size() * 8, hipMemcpyHostToDevice, s));
+        ING_HIP(g, hipMemcpyAsync(d->d_name16, d->name16.data(), d->name16.size(), hipMemcpyHostToDevice, s));
+        ING_HIP(g, hipStreamSynchronize(s));  // (the uploads read this call's vectors)
+    }
+    return ZK_OK;
+}
+
 zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
                        uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
                        zk_ingest_items* items, const uint64_t* ends = nullptr) {
     if (!g || !n_out || !n_rejected) return ZK_ERR_INVALID_ARG;
     *n_out = *n_rejected = 0;
     if (items) items->kv_n = items->ann_n = 0;
-    if (flags & ZK_INGEST_SPAN_NAMES) return dfail(g, ZK_ERR_UNSUPPORTED, "the device decoder keeps no span-name dictionary");
+    if ((flags & ZK_INGEST_SPAN_NAMES) && !g->nm.table)
+        return dfail(g, ZK_ERR_UNSUPPORTED,
+                     "this device decoder keeps no span-name dictionary (zk_ingest_dev_create_names makes one that does)");
     const bool want_kv = items && items->kv_service && items->kv_key && items->kv_cap;
     const bool want_ann = items && items->ann_service && items->ann_value && items->ann_cap;
+    const bool names = (flags & ZK_INGEST_SPAN_NAMES) != 0;
     if (n == 0) return ZK_OK;
     if (items && n >= (1ull << 30)) return dfail(g, ZK_ERR_INVALID_ARG, "items: batch of 2^30 fragments or more");
     if (!buf || !offsets || !out || !out->trace_id || !out->span_id || !out->parent_id || !out->first_ts ||
@@ -2575,7 +2874,8 @@ zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* off
     ING_HIP(g, hipSetDevice(g->device));
     // per-fragment arrays: 8-byte columns first, then 4-byte, then 1-byte
     const uint64_t n1 = n + 1;
-    const uint64_t bytes = align256(8 * n1) * 8 + align256(4 * n1) * 9 + align256(n1);
+    const uint64_t bytes = align256(8 * n1) * 8 + align256(4 * n1) * 9 + align256(n1) +
+                           (names ? align256(8 * n1) + align256(4 * n1) * 3 : 0);
     if (bytes > g->batch_cap) {
         hipFree(g->batch);
         g->batch = nullptr;
@@ -2604,7 +2904,7 @@ zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* off
     tmp.last_ts = (int64_t*)take(8 * n1);
     a.svc_hash = (uint64_t*)take(8 * n1);
     a.name_ptr = (uint64_t*)take(8 * n1);
-    take(8 * n1);  // (spare)
+    uint64_t* const nm_hash = (uint64_t*)take(8 * n1);  // (the span names' hashes; else spare)
     tmp.flags = (uint32_t*)take(4 * n1);
     tmp.service_id = (uint32_t*)take(4 * n1);
     a.name_len = (uint32_t*)take(4 * n1);
@@ -2622,6 +2922,24 @@ zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* off
     a.skip_kv = (uint32_t*)take(4 * n1);
     a.skip_an = (uint32_t*)take(4 * n1);
     a.status = take(n1);
+    IngNames nn{};  // (all null without the flag: the kNames = false kernels never read it)
+    if (names) {
+        nn.nm_hash = nm_hash;
+        nn.nm_ptr = (uint64_t*)take(8 * n1);
+        nn.nm_len = (uint32_t*)take(4 * n1);
+        nn.nm_id = (uint32_t*)take(4 * n1);
+        nn.npub = (uint32_t*)take(4 * n1);
+        nn.npub_n = g->counts + 14;
+        nn.nclaims = g->counts + 15;
+        nn.n = n;
+        nn.d_key = g->nm.d_key;
+        nn.d_id = g->nm.d_id;
+        nn.d_ptr = g->nm.d_ptr;
+        nn.d_len = g->nm.d_len;
+        nn.d_name16 = g->nm.d_name16;
+        nn.d_mask = g->nm.table - 1;
+        nn.max_services = g->nm.max_services;
+    }
     a.d_key = g->d_key;
     a.d_id = g->d_id;
     a.d_ptr = g->d_ptr;
@@ -2697,7 +3015,8 @@ zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* off
         g->scratch_cap = cap;
     }
     unsigned long long* used = g->counts + 10;
-    ING_HIP(g, hipMemsetAsync(used, 0, 4 * 8, s));  // scratch taken, pub_n, def_n, claims
+    // scratch taken, pub_n, def_n, claims (and the span names' list length and claims)
+    ING_HIP(g, hipMemsetAsync(used, 0, (names ? 6 : 4) * 8, s));
     a.pub_n = g->counts + 11;
     a.def_n = g->counts + 12;
     a.claims = g->counts + 13;
@@ -2708,21 +3027,25 @@ zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* off
     // D1 + D2, D3
     a.lds_block = lds_block;
     const dim3 dgrid((unsigned)((n + a.lds_block - 1) / a.lds_block));
-    if (items) {
-        ING_HIP(g, launch_checked("k_ing_decode_lds", k_ing_decode_lds<true>, dgrid, dim3(kLdsWG), 0, s, a));
-        ING_HIP(g, launch_checked("k_ing_decode", k_ing_decode<true>, lgrid, blk, 0, s, a, (uint32_t)kStDefer));
-    } else {
-        ING_HIP(g, launch_checked("k_ing_decode_lds", k_ing_decode_lds<false>, dgrid, dim3(kLdsWG), 0, s, a));
-        ING_HIP(g, launch_checked("k_ing_decode", k_ing_decode<false>, lgrid, blk, 0, s, a, (uint32_t)kStDefer));
-    }
+    // the decoders' build for this call: without the flag the kNames = false kernels run, on a
+    // names-capable decoder too
+    auto* const decode_lds = items ? (names ? k_ing_decode_lds<true, true> : k_ing_decode_lds<true, false>)
+                                   : (names ? k_ing_decode_lds<false, true> : k_ing_decode_lds<false, false>);
+    auto* const decode_glb = items ? (names ? k_ing_decode<true, true> : k_ing_decode<true, false>)
+                                   : (names ? k_ing_decode<false, true> : k_ing_decode<false, false>);
+    ING_HIP(g, launch_checked("k_ing_decode_lds", decode_lds, dgrid, dim3(kLdsWG), 0, s, a, nn));
+    ING_HIP(g, launch_checked("k_ing_decode", decode_glb, lgrid, blk, 0, s, a, (uint32_t)kStDefer, nn));
     ING_HIP(g, launch_checked("k_ing_dict_insert", k_ing_dict_insert, lgrid, blk, 0, s, a));
     const dim3 xgrid(64);  // the extra-name list kernels (grid-stride; the list is short)
     if (items) ING_HIP(g, launch_checked("k_ing_dict_insert_x", k_ing_dict_insert_x, xgrid, blk, 0, s, ax));
+    // the published span names: D3 / D4 over their list (names_view; status and keep are the fragments')
+    if (names) ING_HIP(g, launch_checked("k_ing_dict_insert_x", k_ing_dict_insert_x, lgrid, blk, 0, s, names_view(a, nn)));
     // D4 and the status counts, then one small read: in the steady state (no scratch overflow, no
     // new service names) this is the batch's only host round trip
     unsigned long long* const hc = g->h_counts;
     auto lookup_and_count = [&]() -> hipError_t {
         hipError_t e = launch_checked("k_ing_lookup", k_ing_lookup, lgrid, blk, 0, s, a);
+        if (names && e == hipSuccess) e = launch_checked("k_ing_lookup_x", k_ing_lookup_x, lgrid, blk, 0, s, names_view(a, nn));
         if (e == hipSuccess) e = hipMemsetAsync(g->counts, 0, 8 * 8, s);
         if (e == hipSuccess) e = hipMemsetAsync(g->counts + 8, 0xFF, 8, s);
         if (e == hipSuccess)
@@ -2733,7 +3056,8 @@ zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* off
             if (e == hipSuccess) e = hipMemsetAsync(a.icnt + 5, 0, 2 * 8, s);
             if (e == hipSuccess) e = launch_checked("k_ing_count_extra", k_ing_count_extra, xgrid, blk, 0, s, ax);
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(hc, g->counts, (items ? 29 : 14) * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(hc, g->counts, (items ? 29 : names ? 16 : 14) * 8, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         return e;
     };
@@ -2741,7 +3065,8 @@ zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* off
     std::vector<uint8_t*> retired;  // old arenas and scratch stay valid until this batch's lookups are done
     unsigned long long* const ic = hc + 16;  // the host copy of a.icnt
     auto items_short = [&]() { return items && (ic[4] > 0 || ic[3] > g->x_cap); };
-    if (hc[10] > g->scratch_cap || hc[13] > 0 || items_short()) {
+    bool name_overflow = false;
+    if (hc[10] > g->scratch_cap || hc[13] > 0 || items_short() || (names && hc[15] > 0)) {
         while (hc[10] > g->scratch_cap || items_short()) {
             // the scratch ran out (kStNoScratch fragments): a larger one, and those fragments again
             if (hc[10] > g->scratch_cap) {
@@ -2771,85 +3096,26 @@ zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* off
                 ING_HIP(g, hipStreamSynchronize(s));
                 bind_items(g, a, ax);
             }
-            ING_HIP(g, launch_checked("k_ing_decode", items ? k_ing_decode<true> : k_ing_decode<false>, lgrid, blk, 0, s,
-                                      a, (uint32_t)kStNoScratch));
+            ING_HIP(g, launch_checked("k_ing_decode", decode_glb, lgrid, blk, 0, s, a, (uint32_t)kStNoScratch, nn));
             ING_HIP(g, launch_checked("k_ing_dict_insert", k_ing_dict_insert, lgrid, blk, 0, s, a));
             if (items) ING_HIP(g, launch_checked("k_ing_dict_insert_x", k_ing_dict_insert_x, xgrid, blk, 0, s, ax));
-            ING_HIP(g, hipMemcpyAsync(hc + 10, used, (items ? 19 : 1) * 8, hipMemcpyDeviceToHost, s));
+            if (names)
+                ING_HIP(g, launch_checked("k_ing_dict_insert_x", k_ing_dict_insert_x, lgrid, blk, 0, s, names_view(a, nn)));
+            ING_HIP(g, hipMemcpyAsync(hc + 10, used, (items ? 19 : names ? 6 : 1) * 8, hipMemcpyDeviceToHost, s));
             ING_HIP(g, hipStreamSynchronize(s));
         }
-        // ids for new slots, in slot order; their names into the device arena
-        std::vector<uint64_t> key(g->table), ptr(g->table);
-        std::vector<uint32_t> len(g->table);
-        ING_HIP(g, hipMemcpyAsync(key.data(), g->d_key, key.size() * 8, hipMemcpyDeviceToHost, s));
-        ING_HIP(g, hipMemcpyAsync(ptr.data(), g->d_ptr, ptr.size() * 8, hipMemcpyDeviceToHost, s));
-        ING_HIP(g, hipMemcpyAsync(len.data(), g->d_len, len.size() * 4, hipMemcpyDeviceToHost, s));
-        ING_HIP(g, hipStreamSynchronize(s));
-        // the new slots in slot order, their names gathered into the arena by one kernel and read
-        // back in one copy
-        std::vector<uint32_t> fresh;
-        uint64_t total = 0;
-        for (uint32_t q = 0; q < g->table; ++q)
-            if (key[q] != kEmpty && g->slot_id[q] == kNoId) {
-                fresh.push_back(q);
-                total += len[q];
-            }
-        const bool changed = !fresh.empty();
-        if (changed) {
-            if (g->arena_used + total > g->arena_cap) {
-                uint64_t cap = g->arena_cap;
-                while (cap < g->arena_used + total) cap *= 2;
-                uint8_t* na = nullptr;
-                ING_HIP(g, hipMalloc(&na, cap));
-                ING_HIP(g, hipMemcpyAsync(na, g->arena, g->arena_used, hipMemcpyDeviceToDevice, s));
-                // repoint the named slots at the new arena
-                for (uint32_t r = 0; r < g->table; ++r)
-                    if (g->slot_id[r] != kNoId)
-                        ptr[r] = (uint64_t)(uintptr_t)na + (ptr[r] - (uint64_t)(uintptr_t)g->arena);
-                retired.push_back(g->arena);
-                g->arena = na;
-                g->arena_cap = cap;
-                a.unknown = na;
-            }
-            const uint32_t m = (uint32_t)fresh.size();
-            std::vector<uint64_t> gsrc(m), goff(m);
-            std::vector<uint32_t> glen(m);
-            uint64_t at = g->arena_used;
-            for (uint32_t k = 0; k < m; ++k) {
-                gsrc[k] = ptr[fresh[k]];
-                goff[k] = at;
-                glen[k] = len[fresh[k]];
-                at += glen[k];
-            }
-            uint8_t* gt = nullptr;  // the gather's table: sources, arena offsets, lengths
-            ING_HIP(g, hipMalloc(&gt, (uint64_t)m * 20));
-            retired.push_back(gt);
-            ING_HIP(g, hipMemcpyAsync(gt, gsrc.data(), (uint64_t)m * 8, hipMemcpyHostToDevice, s));
-            ING_HIP(g, hipMemcpyAsync(gt + (uint64_t)m * 8, goff.data(), (uint64_t)m * 8, hipMemcpyHostToDevice, s));
-            ING_HIP(g, hipMemcpyAsync(gt + (uint64_t)m * 16, glen.data(), (uint64_t)m * 4, hipMemcpyHostToDevice, s));
-            ING_HIP(g, launch_checked("k_ing_gather_names", k_ing_gather_names, dim3((m + 255) / 256), dim3(256), 0, s,
-                                      (const uint64_t*)gt, (const uint64_t*)(gt + (uint64_t)m * 8),
-                                      (const uint32_t*)(gt + (uint64_t)m * 16), m, g->arena));
-            std::string bytes(total, '\0');
-            if (total)
-                ING_HIP(g, hipMemcpyAsync(&bytes[0], g->arena + g->arena_used, total, hipMemcpyDeviceToHost, s));
-            ING_HIP(g, hipStreamSynchronize(s));
-            for (uint32_t k = 0; k < m; ++k) {
-                const uint32_t q = fresh[k];
-                std::string nm = bytes.substr(goff[k] - g->arena_used, glen[k]);
-                ptr[q] = (uint64_t)(uintptr_t)(g->arena + goff[k]);
-                g->slot_id[q] = (uint32_t)g->names.size();
-                memcpy(&g->name16[(size_t)q * 16], nm.data(), std::min<size_t>(16, nm.size()));
-                g->names.push_back(std::move(nm));
-            }
-            g->arena_used = at;
+        // ids for new slots, in slot order; their names into the device arenas
+        {
+            const zk_status st = dict_assign_ids(g, g, s, retired, 0, nullptr);
+            if (st != ZK_OK) return st;
+            a.unknown = g->arena;
         }
-        if (changed) {
-            ING_HIP(g, hipMemcpyAsync(g->d_id, g->slot_id.data(), g->slot_id.size() * 4, hipMemcpyHostToDevice, s));
-            ING_HIP(g, hipMemcpyAsync(g->d_ptr, ptr.data(), ptr.size() * 8, hipMemcpyHostToDevice, s));
-            ING_HIP(g, hipMemcpyAsync(g->d_name16, g->name16.data(), g->name16.size(), hipMemcpyHostToDevice, s));
+        if (names) {
+            const zk_status st = dict_assign_ids(g, &g->nm, s, retired, g->nm.max_services, &name_overflow);
+            if (st != ZK_OK) return st;
         }
-        ING_HIP(g, lookup_and_count());  // D4 again, now that every claimed slot has its id
+        if (!name_overflow)
+            ING_HIP(g, lookup_and_count());  // D4 again, now that every claimed slot has its id
     }
     unsigned long long c[9];
     memcpy(c, hc, sizeof(c));
@@ -2890,9 +3156,12 @@ zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* off
     for (int q = 0; q < 8; ++q) dropped += c[q];
     const uint64_t kept = n - dropped;
     const unsigned first_bad = (unsigned)(c[8] & 0xFFFFFFFFu);
+    if (name_overflow)  // (the batch's new names were taken out of the table again: dict_assign_ids)
+        return dfail(g, ZK_ERR_CAPACITY, "more distinct span names than max_span_names (" +
+                                             std::to_string(g->nm.max_services) + "): the batch is not decoded");
     if (c[kStCollision])
-        return dfail(g, ZK_ERR_INVALID_SPAN, "two service names share a 64-bit hash (fragment " +
-                                                  std::to_string(first_bad) + ")");
+        return dfail(g, ZK_ERR_INVALID_SPAN, std::string(names ? "two service names or two span names" : "two service names") +
+                                                 " share a 64-bit hash (fragment " + std::to_string(first_bad) + ")");
     if (icf[5]) return dfail(g, ZK_ERR_INVALID_SPAN, "two service names (an item's host) share a 64-bit hash");
     if (c[kStRange] || icf[6])
         return dfail(g, ZK_ERR_SERVICE_RANGE, "more distinct service names than max_services");
@@ -2901,6 +3170,10 @@ zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* off
     if (strict && bad)
         return dfail(g, ZK_ERR_INVALID_SPAN, "span " + std::to_string(first_bad) + ": " +
                                                  (c[kStUndecodable] ? "undecodable or invalid span" : "invalid span"));
+    if (names && hc[14]) {  // span names D2 published: their ids into the flags (before D5 moves them)
+        ING_HIP(g, launch_checked("k_ing_name_flags", k_ing_name_flags, lgrid, blk, 0, s, names_view(a, nn)));
+        ING_HIP(g, hipStreamSynchronize(s));
+    }
     uint64_t nkv = 0, nan = 0, tot[2] = {0, 0};
     if (items) {
         // the chunks and the direct items into the caller's buffers (k_ing_item_compact), then the item
@@ -2986,7 +3259,9 @@ zk_status ingest_multi(zk_ingest_dev* g, uint32_t nb, const uint8_t* const* bufs
     if (!g || !n_out || !n_rejected) return ZK_ERR_INVALID_ARG;
     *n_out = *n_rejected = 0;
     if (items) items->kv_n = items->ann_n = 0;
-    if (flags & ZK_INGEST_SPAN_NAMES) return dfail(g, ZK_ERR_UNSUPPORTED, "the device decoder keeps no span-name dictionary");
+    if ((flags & ZK_INGEST_SPAN_NAMES) && !g->nm.table)
+        return dfail(g, ZK_ERR_UNSUPPORTED,
+                     "this device decoder keeps no span-name dictionary (zk_ingest_dev_create_names makes one that does)");
     if (nb && (!bufs || !offsets || !ns)) return dfail(g, ZK_ERR_INVALID_ARG, "null batch arrays");
     uint64_t n = 0;
     uintptr_t base = UINTPTR_MAX;
@@ -3089,6 +3364,27 @@ zk_status zk_ingest_dev_service_name(const zk_ingest_dev* g, uint32_t id, char* 
     if (!g || !len) return ZK_ERR_INVALID_ARG;
     if (id >= g->names.size()) return ZK_ERR_SERVICE_RANGE;
     const std::string& s = g->names[id];
+    *len = s.size();
+    if (!buf) return ZK_OK;
+    if (cap < s.size()) return ZK_ERR_CAPACITY;
+    memcpy(buf, s.data(), s.size());
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_ingest_dev_num_span_names(const zk_ingest_dev* g, uint32_t* n) {
+    ZK_GUARD_BEGIN
+    if (!g || !n) return ZK_ERR_INVALID_ARG;
+    *n = (uint32_t)g->nm.names.size();  // (0 without a span-name dictionary)
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_ingest_dev_span_name(const zk_ingest_dev* g, uint32_t id, char* buf, uint64_t cap, uint64_t* len) {
+    ZK_GUARD_BEGIN
+    if (!g || !len) return ZK_ERR_INVALID_ARG;
+    if (id >= g->nm.names.size()) return ZK_ERR_INVALID_ARG;  // (as zk_ingest_span_name)
+    const std::string& s = g->nm.names[id];
     *len = s.size();
     if (!buf) return ZK_OK;
     if (cap < s.size()) return ZK_ERR_CAPACITY;

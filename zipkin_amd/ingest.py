@@ -158,17 +158,28 @@ class DeviceSpanDecoder:
     """zk_ingest_dev: stored fragments already in HBM -> device columns (one lane per fragment).
 
     `decode_device(buf, offsets, n)` takes torch tensors (uint8 bytes, int64 offsets[n+1]) on the
-    device; `decode(blobs)` uploads a list of bytes objects first (tests, small batches)."""
+    device; `decode(blobs)` uploads a list of bytes objects first (tests, small batches).
 
-    def __init__(self, max_services: int = 4096, *, device: int = 0, stream: int | None = None,
-                 scratch_bytes: int = 0):
+    max_span_names > 0 (at most 65535) makes a decoder that also keeps a span-name dictionary in HBM
+    (zk_ingest_dev_create_names): the decode calls then take span_names=True and write every
+    record's name id (id + 1; 0 for "" and "Unknown") into bits 16..31 of flags. Its ids follow
+    hash-table slot order, not the host decoder's first-appearance order: compare through
+    span_name(i). With 0 (the default) span_names=True raises ZK_ERR_UNSUPPORTED."""
+
+    def __init__(self, max_services: int = 4096, *, max_span_names: int = 0, device: int = 0,
+                 stream: int | None = None, scratch_bytes: int = 0):
         self._L = _abi.lib()
         h = C.c_void_p()
-        st = self._L.zk_ingest_dev_create(device, stream, max_services, C.byref(h))
+        if max_span_names:
+            st = self._L.zk_ingest_dev_create_names(device, stream, max_services, max_span_names, C.byref(h))
+        else:
+            st = self._L.zk_ingest_dev_create(device, stream, max_services, C.byref(h))
         if st != _abi.ZK_OK:
             raise _abi.ZkError(st, _abi.status_str(st))
         self._h = h
         self.device = device
+        self.max_services = max_services
+        self.max_span_names = max_span_names
         if scratch_bytes:  # the Snappy scratch's first size (zk_ingest_dev_set_scratch); it grows on demand
             st = self._L.zk_ingest_dev_set_scratch(self._h, scratch_bytes)
             if st != _abi.ZK_OK:
@@ -190,12 +201,13 @@ class DeviceSpanDecoder:
             raise _abi.ZkError(st, self._L.zk_ingest_dev_last_error(self._h).decode() or _abi.status_str(st))
 
     def decode_device(self, buf, offsets, n: int, *, snappy: bool = True, strict: bool = True, out=None,
-                      items: bool = False, item_cap: int | None = None):
+                      items: bool = False, item_cap: int | None = None, span_names: bool = False):
         """-> (DeviceColumns with .n = records written, rejected), or with items=True
         (cols, rejected, (kv_service, kv_key), (ann_service, ann_value)): the span indexer's items as
         device tensors (int32 service ids of this decoder, int64 hashes = uint64 bit patterns), in no
         particular order within the batch (zk_ingest_dev_spans_items). item_cap: the items per kind
-        to allow for (default 2n + 16; a batch with more is decoded again with 4x the room)."""
+        to allow for (default 2n + 16; a batch with more is decoded again with 4x the room).
+        span_names: ZK_INGEST_SPAN_NAMES (a decoder made with max_span_names > 0)."""
         L, h = self._L, self._h
         bp, op = buf.data_ptr(), offsets.data_ptr()
 
@@ -205,10 +217,10 @@ class DeviceSpanDecoder:
             return L.zk_ingest_dev_spans_items(h, bp, op, n, codec, flags, C.byref(ab), C.byref(nout), C.byref(nrej),
                                                C.byref(it))
 
-        return self._run(call, n, snappy, strict, out, items, item_cap)
+        return self._run(call, n, snappy, strict, out, items, item_cap, span_names)
 
     def decode_device_many(self, batches, *, snappy: bool = True, strict: bool = True, out=None,
-                           items: bool = False, item_cap: int | None = None):
+                           items: bool = False, item_cap: int | None = None, span_names: bool = False):
         """Several HBM-resident batches [(buf, offsets, n), ...] in ONE decode
         (zk_ingest_dev_spans_multi): the results of decode_device over the batches joined in order,
         for one set of launches and one host round trip."""
@@ -223,9 +235,9 @@ class DeviceSpanDecoder:
             return L.zk_ingest_dev_spans_multi(h, nb, bufs, offs, ns, codec, flags, C.byref(ab), C.byref(nout),
                                                C.byref(nrej), None if it is None else C.byref(it))
 
-        return self._run(call, n, snappy, strict, out, items, item_cap)
+        return self._run(call, n, snappy, strict, out, items, item_cap, span_names)
 
-    def _run(self, call, n, snappy, strict, out, items, item_cap):
+    def _run(self, call, n, snappy, strict, out, items, item_cap, span_names=False):
         import torch
 
         from .columns import DeviceColumns
@@ -235,7 +247,7 @@ class DeviceSpanDecoder:
         nout, nrej = C.c_uint64(), C.c_uint64()
         ab = cols.abi(n)
         codec = _abi.ZK_CODEC_SNAPPY_THRIFT if snappy else _abi.ZK_CODEC_THRIFT
-        flags = _abi.ZK_INGEST_STRICT if strict else 0
+        flags = (_abi.ZK_INGEST_STRICT if strict else 0) | (_abi.ZK_INGEST_SPAN_NAMES if span_names else 0)
         if not items:
             self._check(call(codec, flags, ab, nout, nrej, None))
             cols.n = int(nout.value)
@@ -271,7 +283,8 @@ class DeviceSpanDecoder:
         memo[h] = v
         return v
 
-    def decode(self, blobs: Sequence[bytes], *, snappy: bool = True, strict: bool = True, items: bool = False):
+    def decode(self, blobs: Sequence[bytes], *, snappy: bool = True, strict: bool = True, items: bool = False,
+               span_names: bool = False):
         import torch
 
         dev = f"cuda:{self.device}"
@@ -281,7 +294,8 @@ class DeviceSpanDecoder:
         raw = np.frombuffer(b"".join(blobs) or b"\0", dtype=np.uint8)
         buf = torch.from_numpy(raw.copy()).to(dev)
         off = torch.from_numpy(offsets).to(dev)
-        return self.decode_device(buf, off, len(blobs), snappy=snappy, strict=strict, items=items)
+        return self.decode_device(buf, off, len(blobs), snappy=snappy, strict=strict, items=items,
+                                  span_names=span_names)
 
     @property
     def num_services(self) -> int:
@@ -304,3 +318,25 @@ class DeviceSpanDecoder:
 
     def service_names(self) -> List[str]:
         return [self.service_name(i) for i in range(self.num_services)]
+
+    @property
+    def num_span_names(self) -> int:
+        n = C.c_uint32()
+        self._check(self._L.zk_ingest_dev_num_span_names(self._h, C.byref(n)))
+        return int(n.value)
+
+    def span_name(self, i: int) -> str:
+        """Memoised: a span name keeps its id for the decoder's life. A record's flags carry id + 1."""
+        memo = self.__dict__.setdefault("_span_names", {})
+        if i in memo:
+            return memo[i]
+        ln = C.c_uint64()
+        self._check(self._L.zk_ingest_dev_span_name(self._h, i, None, 0, C.byref(ln)))
+        buf = C.create_string_buffer(max(1, ln.value))
+        self._check(self._L.zk_ingest_dev_span_name(self._h, i, buf, ln.value, C.byref(ln)))
+        v = buf.raw[: ln.value].decode("utf-8", "surrogateescape")
+        memo[i] = v
+        return v
+
+    def span_names(self) -> List[str]:
+        return [self.span_name(i) for i in range(self.num_span_names)]
