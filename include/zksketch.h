@@ -290,6 +290,65 @@ zk_status   zk_lh_partial(zk_lh* lh, void** hist, uint64_t* bytes);
 /* links dropped for a duration >= 2^40 us while bound, since reset (syncs) */
 zk_status   zk_lh_dropped(zk_lh* lh, uint64_t* duration_range);
 
+/* ------------------------------------------------------------------------------------------
+ * Link-histogram snapshots: the present bins only, so the state can be stored and merged by window.
+ *
+ * The dense table is almost all zeros (a service graph has thousands of edges, not S * S), and it
+ * lives only as long as its handle. A snapshot is the canonical sparse form of one histogram state
+ * -- one state has exactly one byte string -- that a store keeps beside a Dependencies record and
+ * that sums with other snapshots (integer counts), which two quantiles cannot. Little-endian:
+ *
+ *   header, 64 bytes   u32 magic "ZKLH" (0x484C4B5A), u32 version = 1, u32 sub_bits m,
+ *                      u32 bins = (41 - m) << m, u64 rows, u64 entries, u64 links = the sum of all
+ *                      counts, u64 dropped (zk_lh_dropped), zero padding to 64 bytes
+ *   rows x 16 bytes    { u32 parent, u32 child, u64 first }: strictly ascending by (parent, child);
+ *                      `first` = index of the row's first entry; a row ends where the next begins, the
+ *                      last at `entries`; every row has at least one entry
+ *   entries x 8 bytes  u64 (bin << 32) | count: ascending by bin inside a row, count >= 1, bin < bins
+ *
+ * Rows carry (parent, child), not the cell index, so a snapshot survives a change of S and a remap
+ * of the service ids (zk_lh_snapshot_remap).
+ *
+ * zk_lh_snapshot compacts the table on the device (a count pass, two u64 scans over the cells, a
+ * write pass; no atomics, so the bytes are deterministic) and copies the blob to the host. Two-phase:
+ * out == NULL gives *bytes = the size; else the blob is written when cap >= size, and nothing is
+ * written with ZK_ERR_CAPACITY when it is not. Scratch (S * S x 24 B plus the blob) is allocated on
+ * first use; a refused allocation is ZK_ERR_CAPACITY and leaves the state as it was.
+ * zk_lh_snapshot_ms: device times (ms, HIP events) of the last written snapshot: [0] count pass and
+ * scans, [1] write pass, [2] copy to the host.
+ *
+ * zk_lh_merge adds a snapshot into the handle's table (bound or not, on its current stream). The blob
+ * is validated completely on the host first; every (parent, child) must be below S
+ * (ZK_ERR_SERVICE_RANGE) and m must be the handle's (ZK_ERR_INVALID_ARG). Capacity is the handle's
+ * rule: with `reserved` the records and merged links since reset, reserved + links > 2^32 - 1 fails
+ * with ZK_ERR_CAPACITY before anything is copied or launched; else reserved += links and dropped +=
+ * the header's. A refused merge leaves the table unchanged.
+ *
+ * The zk_lh_snapshot_* functions are host-only (no device, no handle): a query host without a GPU
+ * answers from stored snapshots. All of them validate their input blobs first (ZK_ERR_INVALID_ARG for
+ * a malformed one; nothing is read past `bytes`), and the two-phase outputs follow zk_lh_snapshot.
+ *   _validate   ZK_OK for a well-formed canonical blob
+ *   _plus       the canonical snapshot of the summed state; dropped adds; a different m is
+ *               ZK_ERR_INVALID_ARG; a counter that would pass 2^32 - 1 is ZK_ERR_CAPACITY
+ *   _remap      every id replaced through map[n_map] and the rows re-sorted; an id >= n_map is
+ *               ZK_ERR_SERVICE_RANGE, two rows landing on one pair ZK_ERR_INVALID_ARG
+ *   _quantiles  per row, in row order: lo/hi int64[rows][nq], count u64[rows] (may be NULL), by the
+ *               nearest-rank rule and bin bounds of zk_lh_quantiles
+ * ------------------------------------------------------------------------------------------ */
+#define ZK_LH_SNAPSHOT_MAGIC   0x484C4B5Au
+#define ZK_LH_SNAPSHOT_VERSION 1u
+#define ZK_LH_SNAPSHOT_HEADER  64u
+zk_status   zk_lh_snapshot(zk_lh* lh, void* out, uint64_t cap, uint64_t* bytes);
+zk_status   zk_lh_snapshot_ms(zk_lh* lh, double out[3]);
+zk_status   zk_lh_merge(zk_lh* lh, const void* blob, uint64_t bytes);
+zk_status   zk_lh_snapshot_validate(const void* blob, uint64_t bytes);
+zk_status   zk_lh_snapshot_plus(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes, void* out,
+                                uint64_t cap, uint64_t* bytes_out);
+zk_status   zk_lh_snapshot_remap(const void* in, uint64_t bytes, const uint32_t* map, uint32_t n_map, void* out,
+                                 uint64_t cap, uint64_t* bytes_out);
+zk_status   zk_lh_snapshot_quantiles(const void* blob, uint64_t bytes, const double* q, uint32_t nq, int64_t* lo,
+                                     int64_t* hi, uint64_t* count);
+
 #ifdef __cplusplus
 }
 #endif

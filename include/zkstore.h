@@ -92,6 +92,21 @@ const char* zk_store_last_error(const zk_store* st);
 /* storeDependencies: one Dependencies record (its links are copied). */
 zk_status zk_store_put_dependencies(zk_store* st, int64_t start_us, int64_t end_us, const zk_dep_link* links,
                                     uint64_t n_links);
+/* The same record with a link-histogram snapshot attached (zksketch.h, zk_lh_snapshot: the per-link
+ * duration histogram of the record's links; validated here, ZK_ERR_INVALID_ARG when malformed, and
+ * copied). The attachment shares the record's fate in every mode: clobbered with its Cassandra day
+ * row, replaced with its HBase ms key. blob == NULL attaches nothing, which is all
+ * zk_store_put_dependencies does. */
+zk_status zk_store_put_dependencies_hist(zk_store* st, int64_t start_us, int64_t end_us, const zk_dep_link* links,
+                                         uint64_t n_links, const void* blob, uint64_t bytes);
+/* The zk_lh_snapshot_plus of the attachments of exactly the records zk_store_get_dependencies sums
+ * for the same window in the store's mode (one selection, shared by both calls). Two-phase like it
+ * (out == NULL: *bytes = the size). *records = the records that matched, *with_hist = how many of them
+ * carried a snapshot (either may be NULL): with_hist < records means the quantiles do not cover the
+ * whole window. No attachment in the window gives an empty snapshot (0 rows, sub_bits 4, 64 bytes);
+ * attachments that differ in sub_bits are ZK_ERR_INVALID_ARG. */
+zk_status zk_store_get_link_hist(zk_store* st, const int64_t* start_us, const int64_t* end_us, int64_t now_us,
+                                 void* out, uint64_t cap, uint64_t* bytes, uint64_t* records, uint64_t* with_hist);
 /* getDependencies(startDate, endDate). start_us/end_us NULL = None. Two-phase: with out == NULL,
  * *n_links receives the number of links; otherwise up to `cap` links are written
  * (ZK_ERR_CAPACITY if cap is too small) together with the result's start/end times. */

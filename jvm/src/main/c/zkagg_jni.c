@@ -234,6 +234,81 @@ JNIEXPORT jint JNICALL FN(lhQuantilesAll)(JNIEnv* env, jobject self, jlong lh, j
     return st;
 }
 
+/* a two-phase blob output as a new byte[] (NULL on error) */
+static jbyteArray blob_out(JNIEnv* env, const void* blob, uint64_t n) {
+    jbyteArray out = (*env)->NewByteArray(env, (jsize)n);
+    if (out) (*env)->SetByteArrayRegion(env, out, 0, (jsize)n, (const jbyte*)blob);
+    return out;
+}
+
+JNIEXPORT jbyteArray JNICALL FN(lhSnapshot)(JNIEnv* env, jobject self, jlong lh) {
+    uint64_t n = 0;
+    if (zk_lh_snapshot(LH(lh), NULL, 0, &n) != ZK_OK) return NULL;
+    void* buf = malloc(n);
+    jbyteArray out = NULL;
+    if (buf && zk_lh_snapshot(LH(lh), buf, n, &n) == ZK_OK) out = blob_out(env, buf, n);
+    free(buf);
+    return out;
+}
+
+JNIEXPORT jint JNICALL FN(lhMerge)(JNIEnv* env, jobject self, jlong lh, jbyteArray snapshot) {
+    const jsize n = (*env)->GetArrayLength(env, snapshot);
+    jbyte* p = (*env)->GetByteArrayElements(env, snapshot, NULL);
+    const jint st = p ? zk_lh_merge(LH(lh), p, (uint64_t)n) : ZK_ERR_CAPACITY;
+    if (p) (*env)->ReleaseByteArrayElements(env, snapshot, p, JNI_ABORT);
+    return st;
+}
+
+JNIEXPORT jbyteArray JNICALL FN(lhSnapshotRemap)(JNIEnv* env, jobject self, jbyteArray snapshot, jintArray map) {
+    const jsize n = (*env)->GetArrayLength(env, snapshot), nm = (*env)->GetArrayLength(env, map);
+    jbyte* p = (*env)->GetByteArrayElements(env, snapshot, NULL);
+    jint* m = (*env)->GetIntArrayElements(env, map, NULL);
+    jbyteArray out = NULL;
+    uint64_t need = 0;
+    if (p && m && zk_lh_snapshot_remap(p, (uint64_t)n, (const uint32_t*)m, (uint32_t)nm, NULL, 0, &need) == ZK_OK) {
+        void* buf = malloc(need);
+        if (buf && zk_lh_snapshot_remap(p, (uint64_t)n, (const uint32_t*)m, (uint32_t)nm, buf, need, &need) == ZK_OK)
+            out = blob_out(env, buf, need);
+        free(buf);
+    }
+    if (p) (*env)->ReleaseByteArrayElements(env, snapshot, p, JNI_ABORT);
+    if (m) (*env)->ReleaseIntArrayElements(env, map, m, JNI_ABORT);
+    return out;
+}
+
+/* per row 3 + 2 * nq longs: parent, child, count, lo[nq], hi[nq] (rows = the header's u64 at byte 16) */
+JNIEXPORT jlongArray JNICALL FN(lhSnapshotQuantiles)(JNIEnv* env, jobject self, jbyteArray snapshot, jdoubleArray q) {
+    const jsize n = (*env)->GetArrayLength(env, snapshot), nq = (*env)->GetArrayLength(env, q);
+    jbyte* p = (*env)->GetByteArrayElements(env, snapshot, NULL);
+    jdouble* qp = (*env)->GetDoubleArrayElements(env, q, NULL);
+    jlongArray out = NULL;
+    if (p && qp && zk_lh_snapshot_validate(p, (uint64_t)n) == ZK_OK) {
+        uint64_t rows = 0;
+        memcpy(&rows, p + 16, 8);
+        int64_t* lo = (int64_t*)malloc((rows * nq + 1) * 8);
+        int64_t* hi = (int64_t*)malloc((rows * nq + 1) * 8);
+        uint64_t* cnt = (uint64_t*)malloc((rows + 1) * 8);
+        const jsize w = 3 + 2 * nq;
+        if (lo && hi && cnt && zk_lh_snapshot_quantiles(p, (uint64_t)n, qp, (uint32_t)nq, lo, hi, cnt) == ZK_OK &&
+            (out = (*env)->NewLongArray(env, (jsize)(rows * w))) != NULL) {
+            for (uint64_t r = 0; r < rows; ++r) {
+                uint32_t ids[2];
+                memcpy(ids, p + ZK_LH_SNAPSHOT_HEADER + r * 16, 8);
+                const jlong head[3] = {ids[0], ids[1], (jlong)cnt[r]};
+                (*env)->SetLongArrayRegion(env, out, (jsize)(r * w), 3, head);
+                (*env)->SetLongArrayRegion(env, out, (jsize)(r * w + 3), nq, (const jlong*)(lo + r * nq));
+                (*env)->SetLongArrayRegion(env, out, (jsize)(r * w + 3 + nq), nq, (const jlong*)(hi + r * nq));
+            }
+        }
+        free(lo);
+        free(hi);
+        free(cnt);
+    }
+    if (p) (*env)->ReleaseByteArrayElements(env, snapshot, p, JNI_ABORT);
+    if (qp) (*env)->ReleaseDoubleArrayElements(env, q, qp, JNI_ABORT);
+    return out;
+}
+
 /* ---- ingest --------------------------------------------------------------------------------------- */
 JNIEXPORT jlong JNICALL FN(ingestCreate)(JNIEnv* env, jobject self) {
     zk_ingest* g = NULL;
@@ -298,6 +373,37 @@ JNIEXPORT jint JNICALL FN(storePutDependencies)(JNIEnv* env, jobject self, jlong
     const jint st = zk_store_put_dependencies(STORE(h), startUs, endUs, (const zk_dep_link*)a, (uint64_t)n);
     (*env)->ReleaseLongArrayElements(env, links, a, JNI_ABORT);
     return st;
+}
+
+JNIEXPORT jint JNICALL FN(storePutDependenciesHist)(JNIEnv* env, jobject self, jlong h, jlong startUs, jlong endUs,
+                                                   jlongArray links, jbyteArray snapshot) {
+    const jsize n = (*env)->GetArrayLength(env, links) / 6, nb = (*env)->GetArrayLength(env, snapshot);
+    jlong* a = (*env)->GetLongArrayElements(env, links, NULL);
+    jbyte* p = (*env)->GetByteArrayElements(env, snapshot, NULL);
+    const jint st = a && p ? zk_store_put_dependencies_hist(STORE(h), startUs, endUs, (const zk_dep_link*)a, (uint64_t)n,
+                                                            p, (uint64_t)nb)
+                           : ZK_ERR_CAPACITY;
+    if (a) (*env)->ReleaseLongArrayElements(env, links, a, JNI_ABORT);
+    if (p) (*env)->ReleaseByteArrayElements(env, snapshot, p, JNI_ABORT);
+    return st;
+}
+
+JNIEXPORT jbyteArray JNICALL FN(storeGetLinkHist)(JNIEnv* env, jobject self, jlong h, jboolean hasStart, jlong startUs,
+                                                 jboolean hasEnd, jlong endUs, jlong nowUs, jlongArray counts) {
+    int64_t s = startUs, e = endUs;
+    uint64_t n = 0, records = 0, with_hist = 0;
+    const int64_t* ps = hasStart ? &s : NULL;
+    const int64_t* pe = hasEnd ? &e : NULL;
+    if (zk_store_get_link_hist(STORE(h), ps, pe, nowUs, NULL, 0, &n, NULL, NULL) != ZK_OK) return NULL;
+    void* buf = malloc(n);
+    jbyteArray out = NULL;
+    if (buf && zk_store_get_link_hist(STORE(h), ps, pe, nowUs, buf, n, &n, &records, &with_hist) == ZK_OK) {
+        const jlong c[2] = {(jlong)records, (jlong)with_hist};
+        (*env)->SetLongArrayRegion(env, counts, 0, 2, c);
+        out = blob_out(env, buf, n);
+    }
+    free(buf);
+    return out;
 }
 
 JNIEXPORT jlongArray JNICALL FN(storeGetDependencies)(JNIEnv* env, jobject self, jlong h, jboolean hasStart,

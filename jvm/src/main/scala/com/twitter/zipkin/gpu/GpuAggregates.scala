@@ -56,6 +56,34 @@ class GpuAggregates(
       "storeDependencies")
   }
 
+  /** the record with the link-histogram snapshot of its links (ZkNative.lhSnapshot). `names` are the
+    * service names of the snapshot's ids (the job's dictionary, at least those with a link): the rows are remapped to this store's
+    * ids exactly as the links are. getLinkDurations sums the snapshots of a window. */
+  def storeDependencies(d: Dependencies, linkHist: Array[Byte], names: Map[Int, String], numNames: Int): Future[Unit] = pool {
+    // (an id no row uses may map anywhere: 0)
+    val remapped = ZkNative.lhSnapshotRemap(linkHist, Array.tabulate(numNames)(i => names.get(i).map(services.id).getOrElse(0)))
+    if (remapped == null) throw new IllegalStateException("storeDependencies: malformed link-histogram snapshot")
+    check(ZkNative.storePutDependenciesHist(store, d.startTime.inMicroseconds, d.endTime.inMicroseconds,
+      pack(d.links), remapped), "storeDependencies")
+  }
+
+  /** the duration quantiles of every link between startDate and endDate, from the snapshots stored with
+    * exactly the records getDependencies reads for that window (host only): the p50/p99 its Moments
+    * cannot give. */
+  def getLinkDurations(startDate: Option[Time], endDate: Option[Time] = None,
+                       qs: Seq[Double] = Seq(0.5, 0.99)): Future[Seq[LinkDuration]] = pool {
+    val counts = new Array[Long](2)
+    val snap = ZkNative.storeGetLinkHist(store, startDate.isDefined, startDate.map(_.inMicroseconds).getOrElse(0L),
+      endDate.isDefined, endDate.map(_.inMicroseconds).getOrElse(0L), Time.now.inMicroseconds, counts)
+    val a = if (snap == null) null else ZkNative.lhSnapshotQuantiles(snap, qs.toArray)
+    if (a == null) throw new IllegalStateException("getLinkDurations failed")
+    val w = 3 + 2 * qs.size
+    (0 until a.length / w).map { r =>
+      LinkDuration(services.name(a(r * w).toInt), services.name(a(r * w + 1).toInt), a(r * w + 2),
+        qs.zipWithIndex.map { case (q, i) => q -> ((a(r * w + 3 + i), a(r * w + 3 + qs.size + i))) }.toMap)
+    }
+  }
+
   // zk_dep_link = {u32 parent, u32 child, i64 m0, f64 m1..m4}: 6 x 8 bytes, the first word packs
   // both ids (little-endian: parent in the low half)
   private[this] def pack(links: Seq[DependencyLink]): Array[Long] = {

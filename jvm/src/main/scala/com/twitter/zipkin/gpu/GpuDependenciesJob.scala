@@ -37,7 +37,9 @@
  * (zksketch.h zk_lh_*, numServices^2 x 592 u32 counters in HBM) and, after a run, `linkDurations`
  * holds one LinkDuration per link of the record, in the record's order: for each q the bounds of the
  * histogram bin that holds the nearest-rank quantile of the edge's child durations. A side output:
- * zipkinDependencies.thrift has no field for it, so it travels beside the Dependencies record. (A
+ * zipkinDependencies.thrift has no field for it, so it travels beside the Dependencies record: when
+ * `aggregates` is a GpuAggregates, the histogram's sparse snapshot (ZkNative.lhSnapshot) is stored with
+ * the record, and GpuAggregates.getLinkDurations answers the quantiles over any window of records. (A
  * multi-GPU job reports the rank's own part: the histogram is not exchanged here.)
  */
 package com.twitter.zipkin.gpu
@@ -76,6 +78,7 @@ class GpuDependenciesJob(aggregates: Aggregates, device: Int = 0, strict: Boolea
   @volatile private[this] var durations: Seq[LinkDuration] = Nil
   /** after a run with linkQuantiles: one entry per link of the record, in the record's order */
   def linkDurations: Seq[LinkDuration] = durations
+  @volatile private[this] var snapshot: Option[(Array[Byte], Map[Int, String], Int)] = None
 
   private[this] def accumulate(ctx: Long, c: Columns, n: Long, flags: Int): Unit =
     check(ctx, ZkNative.accumulate(ctx, c.traceId, c.spanId, c.parentId, c.firstTs, c.lastTs, c.serviceId, c.flags,
@@ -97,6 +100,11 @@ class GpuDependenciesJob(aggregates: Aggregates, device: Int = 0, strict: Boolea
       durations = for (c <- 0 until S * S if present(c) != 0)
         yield LinkDuration(names(c / S), names(c % S), cnt(c),
           linkQuantiles.zipWithIndex.map { case (q, i) => q -> ((lo(c * nq + i), hi(c * nq + i))) }.toMap)
+      val blob = ZkNative.lhSnapshot(lh)
+      require(blob != null, "zk_lh_snapshot failed")
+      // (ids with a link are below the dictionary's size; the names are read before the dictionary goes)
+      val known = (0 until S * S).filter(present(_) != 0).flatMap(c => Seq(c / S, c % S)).distinct.map(i => i -> names(i)).toMap
+      snapshot = Some((blob, known, S))
     }
     if (links.isEmpty) None else Some(Dependencies(Time.epoch, Time.now, links)) // :41-42
   }
@@ -140,7 +148,10 @@ class GpuDependenciesJob(aggregates: Aggregates, device: Int = 0, strict: Boolea
 
   /** rank 0 stores the job's record (every rank holds the same one) */
   private[this] def store(d: Option[Dependencies]): Future[Option[Dependencies]] = d match {
-    case Some(deps) if shard.forall(_.rank == 0) => aggregates.storeDependencies(deps).map(_ => d)
+    case Some(deps) if shard.forall(_.rank == 0) => ((aggregates, snapshot) match {
+      case (g: GpuAggregates, Some((blob, names, n))) => g.storeDependencies(deps, blob, names, n)
+      case _ => aggregates.storeDependencies(deps)
+    }).map(_ => d)
     case _ => Future.value(d)
   }
 

@@ -92,6 +92,15 @@ object ZkNative {
   /** every edge at once: lo / hi receive S*S*q.length bin bounds (us), count S*S link counts; cell =
     * parent * S + child, all 0 for an edge without links */
   @native def lhQuantilesAll(lh: Long, q: Array[Double], lo: Array[Long], hi: Array[Long], count: Array[Long]): Int
+  /** the canonical sparse snapshot of the histogram (zk_lh_snapshot: present bins only, compacted on the
+    * device); null on error */
+  @native def lhSnapshot(lh: Long): Array[Byte]
+  /** add a snapshot into the histogram (zk_lh_merge): validated first; ErrCapacity past 2^32-1 links */
+  @native def lhMerge(lh: Long, snapshot: Array[Byte]): Int
+  /** host only: the snapshot with every service id i replaced by map(i), rows re-sorted; null on error */
+  @native def lhSnapshotRemap(snapshot: Array[Byte], map: Array[Int]): Array[Byte]
+  /** host only: per row of the snapshot (parent, child, count, then lo and hi per q); null on error */
+  @native def lhSnapshotQuantiles(snapshot: Array[Byte], q: Array[Double]): Array[Long]
 
   // ---- ingest (zkingest.h) -----------------------------------------------------------------------
   @native def ingestCreate(): Long
@@ -114,6 +123,14 @@ object ZkNative {
     * null on error */
   @native def storeGetDependencies(store: Long, hasStart: Boolean, startUs: Long, hasEnd: Boolean, endUs: Long,
                                    nowUs: Long, times: Array[Long]): Array[Long]
+  /** the record with its link-histogram snapshot attached (ids already the store's); it shares the
+    * record's fate (clobbered / replaced with it) */
+  @native def storePutDependenciesHist(store: Long, startUs: Long, endUs: Long, links: Array[Long],
+                                       snapshot: Array[Byte]): Int
+  /** the sum of the snapshots of exactly the records storeGetDependencies reads for the window;
+    * counts(0..1) receive the records matched and how many carried a snapshot; null on error */
+  @native def storeGetLinkHist(store: Long, hasStart: Boolean, startUs: Long, hasEnd: Boolean, endUs: Long,
+                               nowUs: Long, counts: Array[Long]): Array[Byte]
   @native def storePutTop(store: Long, kind: Int, service: Int, ids: Array[Long]): Int
   @native def storeGetTop(store: Long, kind: Int, service: Int): Array[Long]
 }

@@ -1,6 +1,7 @@
 // fuzz_host.cpp — ASan/UBSan driver for the host-side byte parsers and the store (CPU only).
 //
-// Built by tools/sanitize/Makefile from the product sources zk_ingest.cpp and zk_store.cpp plus the
+// Built by tools/sanitize/Makefile from the product sources zk_ingest.cpp, zk_store.cpp (with
+// zk_lh_snapshot.cpp, whose functions the store's snapshot attachments call) plus the
 // oracle's zk_oracle.c, with -fsanitize=address,undefined and no recovery: any out-of-bounds access,
 // use-after-free, leak or undefined behaviour aborts the run. Input: a corpus file of length-prefixed
 // stored fragments (u32 little-endian length, then the bytes), written by tests/test_sanitize.py from
@@ -91,6 +92,22 @@ std::vector<uint8_t> mutate(const std::vector<uint8_t>& in) {
     return b;
 }
 
+// a one-row link-histogram snapshot (zksketch.h): sub_bits 4, row (parent, child), entries (bin, count) ascending
+std::vector<uint8_t> snapshot(uint32_t parent, uint32_t child) {
+    const uint32_t head[4] = {0x484C4B5Au, 1u, 4u, (41u - 4u) << 4};
+    const uint64_t nent = 1 + rnd() % 4;
+    std::vector<uint64_t> words = {1, nent, 0, rnd() % 3, 0, 0, ((uint64_t)child << 32) | parent, 0};
+    for (uint64_t i = 0; i < nent; ++i) {
+        const uint64_t count = 1 + rnd() % 1000;
+        words.push_back(((100 * i + rnd() % 100) << 32) | count);
+        words[2] += count;
+    }
+    std::vector<uint8_t> b(16 + words.size() * 8);
+    memcpy(b.data(), head, 16);
+    memcpy(b.data() + 16, words.data(), words.size() * 8);
+    return b;
+}
+
 void fuzz_store() {
     for (uint32_t mode = 0; mode < 3; ++mode) {
         zk_store* s = nullptr;
@@ -101,7 +118,17 @@ void fuzz_store() {
                 l = zk_dep_link{(uint32_t)(rnd() % 7), (uint32_t)(rnd() % 7),
                                 zk_moments{(int64_t)(rnd() % 100 + 1), (double)(rnd() % 1000), 1.0, 2.0, 3.0}};
             const int64_t t = (int64_t)(rnd() % 2000000000000ull) - 1000000000;
-            zk_store_put_dependencies(s, t, t + (int64_t)(rnd() % 1000000), links.data(), links.size());
+            if (r % 3 == 0) {
+                zk_store_put_dependencies(s, t, t + (int64_t)(rnd() % 1000000), links.data(), links.size());
+            } else {  // with a snapshot attached: valid (stored) or mutated (refused unless still well-formed)
+                std::vector<uint8_t> snap = snapshot((uint32_t)(rnd() % 4), (uint32_t)(rnd() % 4));
+                if (zk_store_put_dependencies_hist(s, t, t + (int64_t)(rnd() % 1000000), links.data(), links.size(),
+                                                   snap.data(), snap.size()) != ZK_OK)
+                    abort();
+                snap = mutate(snap);
+                zk_store_put_dependencies_hist(s, t + 1, t + 2, links.data(), links.size(),
+                                               snap.empty() ? (const uint8_t*)"" : snap.data(), snap.size());
+            }
             int64_t a = (int64_t)(rnd() % 3000000000000ull) - 1000000000, e = a + (int64_t)(rnd() % 4000000000ull);
             uint64_t n = 0;
             int64_t os, oe;
@@ -109,6 +136,14 @@ void fuzz_store() {
                                       &n, &os, &oe);
             std::vector<zk_dep_link> out(n + 1);
             zk_store_get_dependencies(s, &a, &e, 1500000000000, out.data(), out.size(), &n, &os, &oe);
+            uint64_t hb = 0, recs = 0, with = 0;
+            if (zk_store_get_link_hist(s, (rnd() & 1) ? &a : nullptr, (rnd() & 1) ? &e : nullptr, 1500000000000, nullptr, 0,
+                                       &hb, &recs, &with) != ZK_OK || with > recs || hb < 64)
+                abort();
+            std::vector<uint8_t> hist(hb);
+            if (zk_store_get_link_hist(s, &a, &e, 1500000000000, hist.data(), hist.size() / 2, &hb, &recs, &with) != ZK_OK &&
+                hb <= hist.size() / 2)
+                abort();
             std::vector<uint64_t> ids(rnd() % 8);
             for (auto& x : ids) x = rnd();
             zk_store_put_top(s, (uint32_t)(rnd() % 3), (uint32_t)(rnd() % 5), ids.data(), ids.size());

@@ -333,6 +333,14 @@ _SIGNATURES = [
     ("zk_lh_read", C.c_int, [_P, C.c_uint64, C.c_uint64, _P]),
     ("zk_lh_partial", C.c_int, [_P, C.POINTER(_P), _U64P]),
     ("zk_lh_dropped", C.c_int, [_P, _U64P]),
+    # include/zksketch.h: link-histogram snapshots (device compaction and merge, host-only algebra)
+    ("zk_lh_snapshot", C.c_int, [_P, _P, C.c_uint64, _U64P]),
+    ("zk_lh_snapshot_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zk_lh_merge", C.c_int, [_P, _P, C.c_uint64]),
+    ("zk_lh_snapshot_validate", C.c_int, [_P, C.c_uint64]),
+    ("zk_lh_snapshot_plus", C.c_int, [_P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
+    ("zk_lh_snapshot_remap", C.c_int, [_P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _U64P]),
+    ("zk_lh_snapshot_quantiles", C.c_int, [_P, C.c_uint64, _P, C.c_uint32, _P, _P, _U64P]),
     # include/zkcomm.h: RCCL communicator and the multi-GPU merges
     ("zk_comm_unique_id", C.c_int, [_P, C.c_uint64]),
     ("zk_comm_create", C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(_P)]),
@@ -391,6 +399,12 @@ _SIGNATURES = [
         C.c_int,
         [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, _P, C.c_uint64, _U64P,
          C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    ),
+    ("zk_store_put_dependencies_hist", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_uint64, _P, C.c_uint64]),
+    (
+        "zk_store_get_link_hist",
+        C.c_int,
+        [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, _P, C.c_uint64, _U64P, _U64P, _U64P],
     ),
     ("zk_store_count", C.c_int, [_P, _U64P]),
     ("zk_store_watermark", C.c_int, [_P, C.POINTER(C.c_int64)]),

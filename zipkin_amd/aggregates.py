@@ -549,9 +549,24 @@ class GpuAggregates(Aggregates):
             pass
 
     # -- dependencies -------------------------------------------------------------------------
-    def storeDependencies(self, dependencies: Dependencies) -> None:
+    def _put(self, dependencies: Dependencies, arr, n: int, link_hist) -> None:
+        if link_hist is None:
+            self._check(self._L.zk_store_put_dependencies(self._h, int(dependencies.start_time),
+                                                          int(dependencies.end_time), arr, n))
+        else:
+            self._check(self._L.zk_store_put_dependencies_hist(self._h, int(dependencies.start_time),
+                                                               int(dependencies.end_time), arr, n, link_hist,
+                                                               len(link_hist)))
+
+    def storeDependencies(self, dependencies: Dependencies, link_hist=None) -> None:
+        """link_hist: the link-histogram snapshot of the record's links (LinkHistogram.snapshot(), bytes
+        or a LinkHistogramSnapshot), stored with the record and summed by getLinkDurations. With a
+        job's LinkList its service ids are the job's and are remapped to this store's dictionary exactly
+        as the links are; with plain DependencyLinks they must already be this store's ids."""
         links = dependencies.links
         n = len(links)
+        if link_hist is not None:
+            link_hist = bytes(getattr(link_hist, "blob", link_hist))
         if isinstance(links, LinkList):  # a job's compact record: remap its ids to this store's names
             raw, names = links.compact()
             remap = np.array([self.services.id(x) for x in names] or [0], np.uint32)
@@ -561,15 +576,47 @@ class GpuAggregates(Aggregates):
                 arr = raw.copy()
                 arr["parent"] = remap[raw["parent"]]
                 arr["child"] = remap[raw["child"]]
-            self._check(self._L.zk_store_put_dependencies(self._h, int(dependencies.start_time),
-                                                          int(dependencies.end_time), arr.ctypes.data, n))
+                if link_hist is not None:
+                    from .realtime import LinkHistogramSnapshot
+
+                    link_hist = LinkHistogramSnapshot(link_hist).remap(remap).blob
+            self._put(dependencies, arr.ctypes.data, n, link_hist)
             return
         arr = (_abi.zk_dep_link * max(n, 1))()
         for i, l in enumerate(links):
             arr[i] = _abi.zk_dep_link(self.services.id(l.parent.name), self.services.id(l.child.name),
                                       _to_c(l.duration_moments))
-        self._check(self._L.zk_store_put_dependencies(self._h, int(dependencies.start_time),
-                                                      int(dependencies.end_time), arr, n))
+        self._put(dependencies, arr, n, link_hist)
+
+    def getLinkHistogram(self, startDate: Optional[int], endDate: Optional[int] = None):
+        """(LinkHistogramSnapshot, records, with_hist): the sum of the snapshots stored with exactly the
+        records getDependencies(startDate, endDate) reads, how many records that is and how many of
+        them carried a snapshot (fewer: the histogram does not cover the whole window)."""
+        from .realtime import LinkHistogramSnapshot
+
+        s = C.c_int64(startDate) if startDate is not None else None
+        e = C.c_int64(endDate) if endDate is not None else None
+        sp = C.byref(s) if s is not None else None
+        ep = C.byref(e) if e is not None else None
+        now = int(self.clock())
+        n, rec, wh = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self._L.zk_store_get_link_hist(self._h, sp, ep, now, None, 0, C.byref(n), None, None))
+        buf = (C.c_uint8 * max(1, n.value))()
+        self._check(self._L.zk_store_get_link_hist(self._h, sp, ep, now, buf, n.value, C.byref(n), C.byref(rec),
+                                                   C.byref(wh)))
+        return LinkHistogramSnapshot(bytes(buf)[: n.value]), int(rec.value), int(wh.value)
+
+    def getLinkDurations(self, startDate: Optional[int], endDate: Optional[int] = None,
+                         qs: Sequence[float] = (0.5, 0.99)) -> List["LinkDuration"]:
+        """The duration quantiles of every link between startDate and endDate: one LinkDuration per
+        (parent, child) of the summed snapshots (getLinkHistogram), in (parent id, child id) order --
+        the p50/p99 that getDependencies' Moments cannot give, over the same records. Answered on the
+        host: no device is needed."""
+        snap, _, _ = self.getLinkHistogram(startDate, endDate)
+        lo, hi, cnt = snap.quantiles(qs)
+        return [LinkDuration(self.services.name(int(r["parent"])), self.services.name(int(r["child"])), int(cnt[i]),
+                             {float(q): (int(lo[i, k]), int(hi[i, k])) for k, q in enumerate(qs)})
+                for i, r in enumerate(snap.rows)]
 
     def getDependencies(self, startDate: Optional[int], endDate: Optional[int] = None) -> Dependencies:
         s = C.c_int64(startDate) if startDate is not None else None
@@ -700,6 +747,15 @@ def _link_durations(table, names: Sequence[str], hist, qs: Sequence[float]) -> L
     return out
 
 
+def _store(aggregates, deps: Dependencies, link_hist) -> None:
+    """storeDependencies, with the job's snapshot when it has one (the trait's one-argument form else:
+    a sink that is not a GpuAggregates never sees the second argument)."""
+    if link_hist is None:
+        aggregates.storeDependencies(deps)
+    else:
+        aggregates.storeDependencies(deps, link_hist=link_hist)
+
+
 def links_from_table(table, services: Dictionary) -> "LinkList":
     """The present cells of a finalized host LinkTable as DependencyLinks (zk_link_table_compact),
     kept in the table's form (LinkList) until read."""
@@ -728,7 +784,9 @@ class ZipkinAggregateJob:
     link_quantiles (e.g. (0.5, 0.99)): the job also keeps a per-edge duration histogram on the device
     (realtime.LinkHistogram bound to its context) and link_durations() returns, after run(), the asked
     quantiles of every link -- a side output beside the Dependencies record, whose thrift form has no
-    field for it. run()'s return value does not change.
+    field for it. run()'s return value does not change. With an `aggregates` sink the histogram's sparse
+    snapshot (link_histogram()) is stored with the record, so GpuAggregates.getLinkDurations(start, end)
+    answers the same quantiles over any window of stored records.
 
     The device context is kept between runs (a scheduled job reuses its buffers); close() frees it.
     """
@@ -741,6 +799,7 @@ class ZipkinAggregateJob:
         self.link_quantiles = None if link_quantiles is None else tuple(float(q) for q in link_quantiles)
         self._lh = None
         self._link_durations: List[LinkDuration] = []
+        self._link_hist: Optional[bytes] = None
         self.services = services
         self.device = device
         self.strict = strict
@@ -795,20 +854,26 @@ class ZipkinAggregateJob:
         if self._lh is not None:
             names = [self.services.name(i) for i in range(min(table.num_services, len(self.services)))]
             self._link_durations = _link_durations(table, names, self._lh, self.link_quantiles)
-        return self._publish(table)
+            self._link_hist = self._lh.snapshot()
+        return self._publish(table, self._link_hist)
 
     def link_durations(self) -> List[LinkDuration]:
         """After run() of a job with link_quantiles: one LinkDuration per link of the record, in the
         order of its LinkList."""
         return self._link_durations
 
-    def _publish(self, table) -> Optional[Dependencies]:
+    def link_histogram(self) -> Optional[bytes]:
+        """After run() of a job with link_quantiles: the link-histogram snapshot of the record's links
+        (service ids = the job's), which an `aggregates` sink stores with the record."""
+        return self._link_hist
+
+    def _publish(self, table, link_hist=None) -> Optional[Dependencies]:
         links = links_from_table(table, self.services)
         if not links:
             return None
         deps = Dependencies(0, int(self.clock()), links)  # Time.fromMilliseconds(0), Time.now (:41-42)
         if self.aggregates is not None:
-            self.aggregates.storeDependencies(deps)
+            _store(self.aggregates, deps, link_hist)
         return deps
 
 
@@ -847,7 +912,8 @@ class StoredSpanJob:
     count-min width per service is kv_width or the largest, 4096 (the auto width of <= 256 services).
 
     link_quantiles: as for ZipkinAggregateJob -- run() and run_device() also feed a per-edge duration
-    histogram (max_services^2 x 592 counters of 4 B) and link_durations() returns every link's quantiles.
+    histogram (max_services^2 x 592 counters of 4 B) and link_durations() returns every link's quantiles;
+    with an `aggregates` sink the histogram's snapshot is stored with the record.
     """
 
     def __init__(self, *, device: int = 0, strict: bool = True, aggregates: Optional[Aggregates] = None,
@@ -856,6 +922,7 @@ class StoredSpanJob:
                  link_quantiles: Optional[Sequence[float]] = None):
         self.link_quantiles = None if link_quantiles is None else tuple(float(q) for q in link_quantiles)
         self._link_durations: List[LinkDuration] = []
+        self._link_hist: Optional[bytes] = None
         self.device = device
         self.strict = strict
         self.aggregates = aggregates
@@ -893,6 +960,11 @@ class StoredSpanJob:
         record, in the order of its LinkList."""
         return self._link_durations
 
+    def link_histogram(self) -> Optional[bytes]:
+        """After run() / run_device() of a job with link_quantiles: the link-histogram snapshot of the
+        record's links, which an `aggregates` sink stores with the record."""
+        return self._link_hist
+
     def _finish(self, ctx, names: List[str], hist=None) -> Optional[Dependencies]:
         if len(names) > self.max_services:
             raise _abi.ZkError(_abi.ZK_ERR_SERVICE_RANGE, f"{len(names)} services > max_services {self.max_services}")
@@ -901,6 +973,7 @@ class StoredSpanJob:
         self.stats = ctx.stats()
         if hist is not None:
             self._link_durations = _link_durations(table, names, hist, self.link_quantiles)
+            self._link_hist = hist.snapshot()
         job = ZipkinAggregateJob(self.services, device=self.device, strict=self.strict, clock=self.clock)
         return job._publish(table)
 
@@ -960,7 +1033,7 @@ class StoredSpanJob:
             self.top_annotations = self._tops(dec, anns, len(names))
         if self.aggregates is not None:
             if deps is not None:
-                self.aggregates.storeDependencies(deps)
+                _store(self.aggregates, deps, self._link_hist)
             for name, keys in self.top_kv.items():
                 self.aggregates.storeTopKeyValueAnnotations(name, keys)
             for name, values in self.top_annotations.items():
@@ -1118,7 +1191,7 @@ class StoredSpanJob:
             raise
         if self.aggregates is not None:
             if deps is not None:
-                self.aggregates.storeDependencies(deps)
+                _store(self.aggregates, deps, self._link_hist)
             if indexer:
                 for name, keys in self.top_kv.items():
                     self.aggregates.storeTopKeyValueAnnotations(name, keys)

@@ -25,8 +25,15 @@
 // device-scope atomic each (JoinArgs.lh_hist); spilled traces are rare. Without bucket order (S >
 // 1024: the table itself is then reduced with global atomics, k_link_reduce_atomic) k_lh_lists reads
 // the K1 lists and adds one atomic per link.
+//
+// The table is dense; what leaves it is not. zk_lh_snapshot compacts the non-zero counters into the
+// canonical sparse snapshot of zksketch.h (k_lh_snap_count, three u64 scans, k_lh_snap_write) and
+// zk_lh_merge adds one back (k_lh_merge); the host-only functions over snapshots are in
+// zk_lh_snapshot.cpp. Neither touches the accumulate path above.
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 #include <math.h>
+#include <string.h>
 
 #include <string>
 #include <vector>
@@ -36,6 +43,7 @@
 #include "zk_internal.h"
 #include "zk_launch.h"
 #include "zk_lh_internal.h"
+#include "zk_lh_snapshot.h"
 #include "zk_sketch_internal.h"
 #include "zksketch.h"
 
@@ -213,6 +221,88 @@ void lh_bin_bounds(uint32_t b, uint32_t m, int64_t* lo, int64_t* hi) {
     *hi = *lo + (int64_t)(1ull << (e - m)) - 1;
 }
 
+// ---- snapshots (zksketch.h, zk_lh_snapshot / zk_lh_merge): the present bins only -----------------
+//
+// Count pass, one wave per cell (the shape of k_lh_quantiles): per 64-bin chunk a ballot of the
+// non-zero counters and its popcount. nz[cell] = the cell's non-zero counters, present[cell] = whether
+// it has any, sum[cell] = its links. The host then scans all three in place (inclusive, u64: at large
+// S the entries pass 2^32), which fixes every row's and every entry's position: no atomic anywhere, so
+// the bytes are the same on every run.
+__global__ __launch_bounds__(256) void k_lh_snap_count(const uint32_t* __restrict__ hist, uint64_t cells, uint32_t bins,
+                                                       unsigned long long* __restrict__ nz,
+                                                       unsigned long long* __restrict__ present,
+                                                       unsigned long long* __restrict__ sum) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t cell = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (cell >= cells) return;  // (uniform over the wave)
+    const uint32_t* row = hist + cell * bins;
+    uint32_t cnt = 0;
+    unsigned long long s = 0;
+    for (uint32_t base = 0; base < bins; base += 64) {
+        const uint32_t x = base + lane;
+        const uint32_t v = x < bins ? row[x] : 0u;
+        cnt += (uint32_t)__popcll(__ballot(v != 0u));
+        s += v;
+    }
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (lane == 0) {
+        nz[cell] = cnt;
+        present[cell] = cnt ? 1ull : 0ull;
+        sum[cell] = s;
+    }
+}
+
+// Write pass, one wave per cell; a wave whose cell is absent leaves at once. nz_incl / row_incl are the
+// inclusive scans: the row is row_incl[cell] - 1 and its entries start at nz_incl[cell - 1]. Within a
+// chunk a lane's position is the count of non-zero lanes below it (ballot + mbcnt), after a running
+// count carried across the chunks; one 8-byte store per non-zero counter, lane 0 writes the descriptor.
+// n_rows / n_entries (the scans' totals) bound every store.
+__global__ __launch_bounds__(256) void k_lh_snap_write(const uint32_t* __restrict__ hist, uint64_t cells, uint32_t bins,
+                                                       uint32_t S, const unsigned long long* __restrict__ nz_incl,
+                                                       const unsigned long long* __restrict__ row_incl,
+                                                       LhSnapRow* __restrict__ rows, unsigned long long n_rows,
+                                                       unsigned long long* __restrict__ entries,
+                                                       unsigned long long n_entries) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t cell = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (cell >= cells) return;
+    const unsigned long long e0 = cell ? nz_incl[cell - 1] : 0ull, e1 = nz_incl[cell];
+    if (e1 == e0) return;  // (uniform) no link on this edge
+    const unsigned long long r = row_incl[cell] - 1;
+    if (lane == 0 && r < n_rows) rows[r] = LhSnapRow{(uint32_t)(cell / S), (uint32_t)(cell % S), e0};
+    const uint32_t* row = hist + cell * bins;
+    unsigned long long at = e0;
+    for (uint32_t base = 0; base < bins; base += 64) {
+        const uint32_t x = base + lane;
+        const uint32_t v = x < bins ? row[x] : 0u;
+        const unsigned long long mask = __ballot(v != 0u);
+        const unsigned long long pos = at + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        if (v && pos < n_entries) entries[pos] = ((unsigned long long)x << 32) | v;
+        at += (unsigned long long)__popcll(mask);
+    }
+}
+
+// Merge, one wave per snapshot row: the row's counters loaded, added and stored. Rows are distinct
+// cells and a row's bins are distinct, so no two lanes meet: no atomic. The host validated the blob
+// (bin < bins, parent and child < S, first ascending and within n_entries) before it was copied.
+__global__ __launch_bounds__(256) void k_lh_merge(uint32_t* __restrict__ hist, uint32_t bins, uint32_t S,
+                                                  const LhSnapRow* __restrict__ rows, unsigned long long n_rows,
+                                                  const unsigned long long* __restrict__ entries,
+                                                  unsigned long long n_entries, unsigned long long dropped_more,
+                                                  unsigned long long* __restrict__ dropped) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r == 0 && lane == 0) *dropped += dropped_more;
+    if (r >= n_rows) return;
+    const LhSnapRow row = rows[r];
+    const unsigned long long e1 = r + 1 < n_rows ? rows[r + 1].first : n_entries;
+    uint32_t* dst = hist + ((uint64_t)row.parent * S + row.child) * bins;
+    for (unsigned long long i = row.first + lane; i < e1; i += 64) {
+        const unsigned long long e = entries[i];
+        dst[e >> 32] += (uint32_t)e;
+    }
+}
+
 }  // namespace
 }  // namespace zk
 
@@ -231,6 +321,15 @@ struct zk_lh {
     double* q_dev = nullptr;
     unsigned long long* q_cnt = nullptr;     // [cells]
     uint32_t* q_bin = nullptr;               // [cells][kLhMaxQ]
+    // snapshot / merge scratch, allocated on first use: the three per-cell u64 arrays of the count
+    // pass (scanned in place), the scan's workspace, and the rows + entries of one blob
+    unsigned long long* s_cell = nullptr;    // [3][cells]: nz, present, sum
+    void* s_tmp = nullptr;
+    size_t s_tmp_bytes = 0;
+    uint8_t* s_blob = nullptr;
+    uint64_t s_blob_bytes = 0;
+    hipEvent_t s_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool s_timed = false;
     std::string err;
 };
 
@@ -252,6 +351,43 @@ zk_status check_q(zk_lh* h, const double* q, uint32_t nq, const int64_t* lo, con
     if (nq && (!q || !lo || !hi)) return hfail(h, ZK_ERR_INVALID_ARG, "null array");
     for (uint32_t i = 0; i < nq; ++i)
         if (!(q[i] >= 0.0 && q[i] <= 1.0)) return hfail(h, ZK_ERR_INVALID_ARG, "quantile outside [0, 1]");
+    return ZK_OK;
+}
+
+// the per-cell arrays, the scan's workspace and the events of zk_lh_snapshot, on first use; a refused
+// allocation is ZK_ERR_CAPACITY and changes nothing
+zk_status snap_scratch(zk_lh* h) {
+    if (h->s_cell) return ZK_OK;
+    size_t tb = 0;
+    LH_HIP(h, hipcub::DeviceScan::InclusiveSum(nullptr, tb, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                               (int)h->cells, h->stream));
+    for (hipEvent_t& e : h->s_ev)
+        if (!e) LH_HIP(h, hipEventCreate(&e));
+    void* tmp = nullptr;
+    unsigned long long* cell = nullptr;
+    if (hipMalloc(&tmp, tb ? tb : 8) != hipSuccess || hipMalloc(&cell, h->cells * 24) != hipSuccess) {
+        (void)hipGetLastError();
+        if (tmp) (void)hipFree(tmp);
+        return hfail(h, ZK_ERR_CAPACITY, "no device memory for the snapshot's scratch (24 B per cell)");
+    }
+    h->s_tmp = tmp;
+    h->s_tmp_bytes = tb;
+    h->s_cell = cell;
+    return ZK_OK;
+}
+
+// room for the rows and entries of one blob in HBM (kept, grown when a larger blob comes)
+zk_status snap_blob(zk_lh* h, uint64_t bytes) {
+    if (bytes <= h->s_blob_bytes) return ZK_OK;
+    LH_HIP(h, hipStreamSynchronize(h->stream));
+    uint8_t* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return hfail(h, ZK_ERR_CAPACITY, "no device memory for the snapshot's rows and entries");
+    }
+    if (h->s_blob) (void)hipFree(h->s_blob);
+    h->s_blob = p;
+    h->s_blob_bytes = bytes;
     return ZK_OK;
 }
 
@@ -369,8 +505,11 @@ zk_status zk_lh_destroy(zk_lh* h) {
     if (!h) return ZK_ERR_INVALID_ARG;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->hist, (void*)h->dropped, (void*)h->q_dev, (void*)h->q_cnt, (void*)h->q_bin})
+    for (void* p : {(void*)h->hist, (void*)h->dropped, (void*)h->q_dev, (void*)h->q_cnt, (void*)h->q_bin,
+                    (void*)h->s_cell, h->s_tmp, (void*)h->s_blob})
         if (p) (void)hipFree(p);
+    for (hipEvent_t e : h->s_ev)
+        if (e) (void)hipEventDestroy(e);
     if (h->own) (void)hipStreamDestroy(h->own);
     delete h;
     return ZK_OK;
@@ -488,6 +627,106 @@ zk_status zk_lh_read(zk_lh* h, uint64_t first_cell, uint64_t n_cells, uint32_t* 
     if (n_cells)
         LH_HIP(h, hipMemcpyAsync(out, h->hist + first_cell * h->bins, n_cells * h->bins * 4, hipMemcpyDeviceToHost, h->stream));
     LH_HIP(h, hipStreamSynchronize(h->stream));
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_lh_snapshot(zk_lh* h, void* out, uint64_t cap, uint64_t* bytes) {
+    ZK_GUARD_BEGIN
+    if (!h || !bytes) return ZK_ERR_INVALID_ARG;
+    LH_HIP(h, hipSetDevice(h->device));
+    const zk_status ss = snap_scratch(h);
+    if (ss != ZK_OK) return ss;
+    const uint64_t cells = h->cells;
+    unsigned long long* nz = h->s_cell;
+    unsigned long long* present = h->s_cell + cells;
+    unsigned long long* sum = h->s_cell + 2 * cells;
+    const uint32_t grid = (uint32_t)((cells + 3) / 4);
+    LH_HIP(h, hipEventRecord(h->s_ev[0], h->stream));
+    LH_HIP(h, launch_checked("k_lh_snap_count", k_lh_snap_count, dim3(grid), dim3(256), 0, h->stream,
+                             (const uint32_t*)h->hist, cells, h->bins, nz, present, sum));
+    // inclusive scans in place (u64): entries before and in each cell, rows up to it, links up to it
+    for (unsigned long long* a : {nz, present, sum})
+        LH_HIP(h, hipcub::DeviceScan::InclusiveSum(h->s_tmp, h->s_tmp_bytes, a, a, (int)cells, h->stream));
+    LH_HIP(h, hipEventRecord(h->s_ev[1], h->stream));
+    unsigned long long tot[3] = {0, 0, 0}, dropped = 0;  // entries, rows, links
+    for (int k = 0; k < 3; ++k)
+        LH_HIP(h, hipMemcpyAsync(&tot[k], h->s_cell + (uint64_t)k * cells + cells - 1, 8, hipMemcpyDeviceToHost, h->stream));
+    LH_HIP(h, hipMemcpyAsync(&dropped, h->dropped, 8, hipMemcpyDeviceToHost, h->stream));
+    LH_HIP(h, hipStreamSynchronize(h->stream));
+    const uint64_t body = tot[1] * 16 + tot[0] * 8;
+    *bytes = sizeof(LhSnapHeader) + body;
+    if (!out) return ZK_OK;
+    if (cap < *bytes) return hfail(h, ZK_ERR_CAPACITY, "output capacity smaller than the snapshot");
+    const zk_status bs = snap_blob(h, body);
+    if (bs != ZK_OK) return bs;
+    LhSnapRow* rows = (LhSnapRow*)h->s_blob;
+    unsigned long long* entries = (unsigned long long*)(h->s_blob + tot[1] * 16);
+    if (tot[1])
+        LH_HIP(h, launch_checked("k_lh_snap_write", k_lh_snap_write, dim3(grid), dim3(256), 0, h->stream,
+                                 (const uint32_t*)h->hist, cells, h->bins, h->S, (const unsigned long long*)nz,
+                                 (const unsigned long long*)present, rows, tot[1], entries, tot[0]));
+    LH_HIP(h, hipEventRecord(h->s_ev[2], h->stream));
+    if (body)
+        LH_HIP(h, hipMemcpyAsync((uint8_t*)out + sizeof(LhSnapHeader), h->s_blob, body, hipMemcpyDeviceToHost, h->stream));
+    LH_HIP(h, hipEventRecord(h->s_ev[3], h->stream));
+    LH_HIP(h, hipStreamSynchronize(h->stream));
+    LhSnapHeader hd{};
+    hd.magic = kLhSnapMagic;
+    hd.version = ZK_LH_SNAPSHOT_VERSION;
+    hd.m = h->m;
+    hd.bins = h->bins;
+    hd.rows = tot[1];
+    hd.entries = tot[0];
+    hd.links = tot[2];
+    hd.dropped = dropped;
+    memcpy(out, &hd, sizeof hd);
+    h->s_timed = true;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_lh_snapshot_ms(zk_lh* h, double out[3]) {
+    ZK_GUARD_BEGIN
+    if (!h || !out) return ZK_ERR_INVALID_ARG;
+    if (!h->s_timed) return hfail(h, ZK_ERR_INVALID_ARG, "no snapshot written yet");
+    LH_HIP(h, hipSetDevice(h->device));
+    for (int k = 0; k < 3; ++k) {
+        float ms = 0.f;
+        LH_HIP(h, hipEventElapsedTime(&ms, h->s_ev[k], h->s_ev[k + 1]));
+        out[k] = ms;
+    }
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_lh_merge(zk_lh* h, const void* blob, uint64_t bytes) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    // everything that can refuse the blob comes before the first copy or launch
+    LhSnapView v;
+    if (!lh_snap_view(blob, bytes, &v)) return hfail(h, ZK_ERR_INVALID_ARG, "malformed snapshot");
+    if (v.h.m != h->m) return hfail(h, ZK_ERR_INVALID_ARG, "snapshot and handle differ in sub_bits");
+    for (uint64_t r = 0; r < v.h.rows; ++r) {
+        const LhSnapRow row = v.row(r);
+        if (row.parent >= h->S || row.child >= h->S) return hfail(h, ZK_ERR_SERVICE_RANGE, "snapshot row with a service id >= num_services");
+    }
+    if (v.h.links > kMaxRecordsSinceReset || h->reserved + v.h.links > kMaxRecordsSinceReset)
+        return hfail(h, ZK_ERR_CAPACITY, "link histogram: more than 2^32-1 records and merged links since its reset");
+    if (!v.h.rows && !v.h.dropped) return ZK_OK;
+    LH_HIP(h, hipSetDevice(h->device));
+    const uint64_t body = bytes - sizeof(LhSnapHeader);
+    const zk_status bs = snap_blob(h, body);
+    if (bs != ZK_OK) return bs;
+    if (body)
+        LH_HIP(h, hipMemcpyAsync(h->s_blob, (const uint8_t*)blob + sizeof(LhSnapHeader), body, hipMemcpyHostToDevice, h->stream));
+    const uint32_t grid = v.h.rows ? (uint32_t)((v.h.rows + 3) / 4) : 1u;
+    LH_HIP(h, launch_checked("k_lh_merge", k_lh_merge, dim3(grid), dim3(256), 0, h->stream, h->hist, h->bins, h->S,
+                             (const LhSnapRow*)h->s_blob, (unsigned long long)v.h.rows,
+                             (const unsigned long long*)(h->s_blob + v.h.rows * 16), (unsigned long long)v.h.entries,
+                             (unsigned long long)v.h.dropped, h->dropped));
+    h->reserved += v.h.links;
+    LH_HIP(h, hipStreamSynchronize(h->stream));  // (the blob is borrowed, and s_blob is reused by the next call)
     return ZK_OK;
     ZK_GUARD_END
 }

@@ -24,6 +24,10 @@
 //     writes both kinds into the top-annotation family, so getTopKeyValueAnnotations finds nothing;
 //     getTopAnnotations returns the newest list stored under the first service id >= the asked one
 //     (its scan has a start row and no stop row).
+//   * link-histogram snapshots (zksketch.h; nothing in the reference): a record may carry the sparse
+//     per-link duration histogram of its links. It lives in the record, so it is clobbered or replaced
+//     with it, and zk_store_get_link_hist sums the snapshots of exactly the records getDependencies
+//     reads -- select_records is the one selection both use.
 // Dictionary ids stand in for the strings (the host owns the dictionaries, as for zkagg.h).
 #include <math.h>
 #include <string.h>
@@ -36,6 +40,7 @@
 #include <vector>
 
 #include "zk_guard.h"
+#include "zksketch.h"
 #include "zkstore.h"
 
 namespace {
@@ -45,6 +50,8 @@ constexpr int64_t kDayUs = 86400LL * 1000000LL;
 struct StoredDeps {
     int64_t start, end;
     std::vector<zk_dep_link> links;
+    bool has_hist = false;      // put_dependencies_hist: the record's link-histogram snapshot
+    std::vector<uint8_t> hist;
 };
 
 // algebird-core 0.8.1 Moments.getCombinedMean (STABILITY_CONSTANT = 0.1)
@@ -163,16 +170,21 @@ zk_status zk_store_destroy(zk_store* s) {
 
 const char* zk_store_last_error(const zk_store* s) { return s ? s->err.c_str() : "null store"; }
 
-zk_status zk_store_put_dependencies(zk_store* s, int64_t start_us, int64_t end_us, const zk_dep_link* links,
-                                    uint64_t n) {
-    ZK_GUARD_BEGIN
+static zk_status put_record(zk_store* s, int64_t start_us, int64_t end_us, const zk_dep_link* links, uint64_t n,
+                            const void* blob, uint64_t bytes) {
     if (!s) return ZK_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(s->mu);
     if (n && !links) return sfail(s, ZK_ERR_INVALID_ARG, "null links");
+    if (blob && zk_lh_snapshot_validate(blob, bytes) != ZK_OK)
+        return sfail(s, ZK_ERR_INVALID_ARG, "malformed link-histogram snapshot");
     StoredDeps d;
     d.start = start_us;
     d.end = end_us;
     d.links.assign(links, links + n);
+    if (blob) {
+        d.has_hist = true;
+        d.hist.assign((const uint8_t*)blob, (const uint8_t*)blob + bytes);
+    }
     if (s->mode == ZK_STORE_CASSANDRA)
         s->keyed[cassandra_key(start_us)] = std::move(d);  // removeRow + insert (:111-116,122-136)
     else if (s->mode == ZK_STORE_HBASE)
@@ -180,24 +192,32 @@ zk_status zk_store_put_dependencies(zk_store* s, int64_t start_us, int64_t end_u
     else
         s->rows.push_back(std::move(d));
     return ZK_OK;
+}
+
+zk_status zk_store_put_dependencies(zk_store* s, int64_t start_us, int64_t end_us, const zk_dep_link* links,
+                                    uint64_t n) {
+    ZK_GUARD_BEGIN
+    return put_record(s, start_us, end_us, links, n, nullptr, 0);
     ZK_GUARD_END
 }
 
-zk_status zk_store_get_dependencies(zk_store* s, const int64_t* start_us, const int64_t* end_us, int64_t now_us,
-                                    zk_dep_link* out, uint64_t cap, uint64_t* n_links, int64_t* out_start,
-                                    int64_t* out_end) {
+zk_status zk_store_put_dependencies_hist(zk_store* s, int64_t start_us, int64_t end_us, const zk_dep_link* links,
+                                         uint64_t n, const void* blob, uint64_t bytes) {
     ZK_GUARD_BEGIN
-    if (!s || !n_links) return ZK_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(s->mu);
-    std::vector<zk_dep_link> res;
-    int64_t rs, re;
+    return put_record(s, start_us, end_us, links, n, blob, bytes);
+    ZK_GUARD_END
+}
+
+// The records getDependencies(start, end) reads in the store's mode, in its scan order (the caller
+// holds the lock); *lo / *hi: Anorm's effective window.
+static std::vector<const StoredDeps*> select_records(const zk_store* s, const int64_t* start_us, const int64_t* end_us,
+                                                     int64_t now_us, int64_t* lo_out, int64_t* hi_out) {
+    std::vector<const StoredDeps*> hit;
     if (s->mode == ZK_STORE_CASSANDRA) {
         // every row, column 0 kept unless a given bound is below 0 us (CassandraAggregates.scala:58-61)
-        std::vector<const StoredDeps*> hit;
         const bool keep = !(end_us && 0 > *end_us) && !(start_us && 0 > *start_us);
         if (keep)
             for (const auto& kv : s->keyed) hit.push_back(&kv.second);
-        monoid_sum(hit, &res, &rs, &re);
     } else if (s->mode == ZK_STORE_HBASE) {
         // scan [startRow, stopRow) in row-key order (HBaseAggregates.scala:41-43); a start row past
         // the stop row scans nothing; startRow == stopRow is a get-scan (HBase's Scan.isGetScan:
@@ -205,7 +225,6 @@ zk_status zk_store_get_dependencies(zk_store* s, const int64_t* start_us, const 
         const uint64_t lo_key = hbase_key_ms(start_us ? *start_us / 1000 : INT64_MAX);
         const bool has_stop = end_us != nullptr;
         const uint64_t hi_key = has_stop ? hbase_key_ms(*end_us / 1000) : 0;
-        std::vector<const StoredDeps*> hit;
         if (has_stop && lo_key == hi_key) {
             const auto it = s->keyed.find(lo_key);
             if (it != s->keyed.end()) hit.push_back(&it->second);
@@ -215,17 +234,33 @@ zk_status zk_store_get_dependencies(zk_store* s, const int64_t* start_us, const 
                 hit.push_back(&it->second);
             }
         }
-        monoid_sum(hit, &res, &rs, &re);
     } else {
         const int64_t lo = start_us ? *start_us : now_us - kDayUs;  // AnormAggregates.scala:53-54
         const int64_t hi = end_us ? *end_us : now_us;
         // WHERE start_ts >= {startTs} AND end_ts <= {endTs} ORDER BY dlid DESC (:56-64)
         for (size_t i = s->rows.size(); i-- > 0;) {
             const StoredDeps& d = s->rows[i];
-            if (d.start >= lo && d.end <= hi) res.insert(res.end(), d.links.begin(), d.links.end());
+            if (d.start >= lo && d.end <= hi) hit.push_back(&d);
         }
-        rs = lo;
-        re = hi;
+        *lo_out = lo;
+        *hi_out = hi;
+    }
+    return hit;
+}
+
+zk_status zk_store_get_dependencies(zk_store* s, const int64_t* start_us, const int64_t* end_us, int64_t now_us,
+                                    zk_dep_link* out, uint64_t cap, uint64_t* n_links, int64_t* out_start,
+                                    int64_t* out_end) {
+    ZK_GUARD_BEGIN
+    if (!s || !n_links) return ZK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(s->mu);
+    std::vector<zk_dep_link> res;
+    int64_t rs = 0, re = 0;
+    const std::vector<const StoredDeps*> hit = select_records(s, start_us, end_us, now_us, &rs, &re);
+    if (s->mode == ZK_STORE_ANORM) {  // the rows' links as they are, times = the window
+        for (const StoredDeps* d : hit) res.insert(res.end(), d->links.begin(), d->links.end());
+    } else {
+        monoid_sum(hit, &res, &rs, &re);
     }
     *n_links = res.size();
     if (out_start) *out_start = rs;
@@ -233,6 +268,49 @@ zk_status zk_store_get_dependencies(zk_store* s, const int64_t* start_us, const 
     if (!out) return ZK_OK;
     if (cap < res.size()) return sfail(s, ZK_ERR_CAPACITY, "output capacity smaller than the result");
     if (!res.empty()) memcpy(out, res.data(), res.size() * sizeof(zk_dep_link));
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_store_get_link_hist(zk_store* s, const int64_t* start_us, const int64_t* end_us, int64_t now_us,
+                                 void* out, uint64_t cap, uint64_t* bytes, uint64_t* records, uint64_t* with_hist) {
+    ZK_GUARD_BEGIN
+    if (!s || !bytes) return ZK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(s->mu);
+    int64_t lo = 0, hi = 0;
+    const std::vector<const StoredDeps*> hit = select_records(s, start_us, end_us, now_us, &lo, &hi);
+    // the zk_lh_snapshot_plus of the attachments, folded in scan order (the sum is canonical: any order
+    // gives the same bytes)
+    std::vector<uint8_t> acc;
+    uint64_t carried = 0;
+    for (const StoredDeps* d : hit) {
+        if (!d->has_hist) continue;
+        ++carried;
+        if (carried == 1) {
+            acc = d->hist;
+            continue;
+        }
+        uint64_t need = 0;
+        zk_status st = zk_lh_snapshot_plus(acc.data(), acc.size(), d->hist.data(), d->hist.size(), nullptr, 0, &need);
+        std::vector<uint8_t> next((size_t)need);
+        if (st == ZK_OK)
+            st = zk_lh_snapshot_plus(acc.data(), acc.size(), d->hist.data(), d->hist.size(), next.data(), need, &need);
+        if (st != ZK_OK)
+            return sfail(s, st, st == ZK_ERR_CAPACITY ? "a summed link-histogram counter would pass 2^32-1"
+                                                      : "stored link-histogram snapshots differ in sub_bits");
+        acc.swap(next);
+    }
+    if (!carried) {  // the empty snapshot: header only, the default sub_bits
+        acc.assign(ZK_LH_SNAPSHOT_HEADER, 0);
+        const uint32_t head[4] = {ZK_LH_SNAPSHOT_MAGIC, ZK_LH_SNAPSHOT_VERSION, 4u, (41u - 4u) << 4};
+        memcpy(acc.data(), head, sizeof head);
+    }
+    *bytes = acc.size();
+    if (records) *records = hit.size();
+    if (with_hist) *with_hist = carried;
+    if (!out) return ZK_OK;
+    if (cap < acc.size()) return sfail(s, ZK_ERR_CAPACITY, "output capacity smaller than the snapshot");
+    memcpy(out, acc.data(), acc.size());
     return ZK_OK;
     ZK_GUARD_END
 }

@@ -104,5 +104,10 @@ class IncrementalAggregator:
         self.last_selected = int(sel.sum())
         deps = self.job.run(cols.take(np.flatnonzero(sel)), num_services=num_services)
         rec = Dependencies(lo, end, deps.links if deps is not None else ())
-        self.aggregates.storeDependencies(rec)
+        # a job with link_quantiles: its link-histogram snapshot is stored with the record
+        hist = getattr(self.job, "link_histogram", lambda: None)() if getattr(self.job, "link_quantiles", None) else None
+        if hist is None:
+            self.aggregates.storeDependencies(rec)
+        else:
+            self.aggregates.storeDependencies(rec, link_hist=hist)
         return rec

@@ -388,3 +388,99 @@ class LinkHistogram:
         d = C.c_uint64()
         self._check(self._L.zk_lh_dropped(self._h, C.byref(d)))
         return int(d.value)
+
+    def snapshot(self, as_array: bool = False) -> bytes:
+        """The canonical sparse snapshot of the state (zk_lh_snapshot: the present bins only,
+        compacted on the device): what a store keeps beside a Dependencies record, and what merge(),
+        LinkHistogramSnapshot.plus and a host without a GPU read back. as_array: the uint8 array the
+        library wrote, without the copy into a bytes object."""
+        n = C.c_uint64()
+        self._check(self._L.zk_lh_snapshot(self._h, None, 0, C.byref(n)))
+        buf = np.empty(n.value, np.uint8)
+        self._check(self._L.zk_lh_snapshot(self._h, buf.ctypes.data, n.value, C.byref(n)))
+        return buf[: n.value] if as_array else buf[: n.value].tobytes()
+
+    def snapshot_ms(self) -> tuple[float, float, float]:
+        """Device ms of the last snapshot(): (count pass and scans, write pass, copy to the host)."""
+        out = (C.c_double * 3)()
+        self._check(self._L.zk_lh_snapshot_ms(self._h, out))
+        return float(out[0]), float(out[1]), float(out[2])
+
+    def merge(self, blob) -> None:
+        """Add a snapshot into the table (zk_lh_merge). Refused, with the table unchanged: a malformed
+        blob or another sub_bits (ZK_ERR_INVALID_ARG), a service id >= num_services
+        (ZK_ERR_SERVICE_RANGE), more than 2^32 - 1 records and merged links since reset
+        (ZK_ERR_CAPACITY)."""
+        raw = bytes(blob.blob if isinstance(blob, LinkHistogramSnapshot) else blob)
+        self._check(self._L.zk_lh_merge(self._h, raw, len(raw)))
+
+
+_SNAP_ROW = np.dtype([("parent", "<u4"), ("child", "<u4"), ("first", "<u8")])
+
+
+def _two_phase(call) -> bytes:
+    """A two-phase blob output (size, then bytes) of a host snapshot function."""
+    n = C.c_uint64()
+    st = call(None, 0, C.byref(n))
+    if st == _abi.ZK_OK:
+        buf = (C.c_uint8 * max(1, n.value))()
+        st = call(buf, n.value, C.byref(n))
+    if st != _abi.ZK_OK:
+        raise _abi.ZkError(st, _abi.status_str(st))
+    return bytes(buf)[: n.value]
+
+
+class LinkHistogramSnapshot:
+    """A link-histogram snapshot on the host (include/zksketch.h, zk_lh_snapshot_*): validated on
+    construction (ZK_ERR_INVALID_ARG for a malformed blob) and parsed into numpy views -- the header
+    fields, `rows` (parent, child, first) and `entries` ((bin << 32) | count). plus, remap and quantiles
+    go through the library's host-only calls: no device is needed."""
+
+    def __init__(self, blob):
+        self.blob = bytes(blob)
+        L = _abi.lib()
+        st = L.zk_lh_snapshot_validate(self.blob, len(self.blob))
+        if st != _abi.ZK_OK:
+            raise _abi.ZkError(st, "malformed link-histogram snapshot")
+        head = np.frombuffer(self.blob, "<u4", 4, 0)
+        self.m, self.bins = int(head[2]), int(head[3])
+        n = np.frombuffer(self.blob, "<u8", 4, 16)
+        self.links, self.dropped = int(n[2]), int(n[3])
+        self.rows = np.frombuffer(self.blob, _SNAP_ROW, int(n[0]), 64)
+        self.entries = np.frombuffer(self.blob, "<u8", int(n[1]), 64 + 16 * int(n[0]))
+
+    def __len__(self) -> int:
+        return len(self.rows)
+
+    def __eq__(self, other):
+        return isinstance(other, LinkHistogramSnapshot) and self.blob == other.blob
+
+    def __hash__(self):
+        return hash(self.blob)
+
+    def plus(self, other: "LinkHistogramSnapshot") -> "LinkHistogramSnapshot":
+        """The snapshot of the summed state (ZK_ERR_CAPACITY when a counter would pass 2^32 - 1)."""
+        a, b = self.blob, other.blob
+        L = _abi.lib()
+        return LinkHistogramSnapshot(_two_phase(lambda o, c, n: L.zk_lh_snapshot_plus(a, len(a), b, len(b), o, c, n)))
+
+    def remap(self, ids) -> "LinkHistogramSnapshot":
+        """Every service id i replaced by ids[i], the rows re-sorted."""
+        a = self.blob
+        m = np.ascontiguousarray(ids, dtype=np.uint32)
+        L = _abi.lib()
+        return LinkHistogramSnapshot(_two_phase(
+            lambda o, c, n: L.zk_lh_snapshot_remap(a, len(a), m.ctypes.data, len(m), o, c, n)))
+
+    def quantiles(self, qs=(0.5, 0.99)):
+        """(lo int64[rows, nq], hi int64[rows, nq], count uint64[rows]) in row order: the bin bounds
+        holding each row's nearest-rank quantiles (as LinkHistogram.quantiles_all for the present cells)."""
+        q = np.ascontiguousarray(qs, dtype=np.float64)
+        lo = np.zeros((len(self.rows), len(q)), np.int64)
+        hi = np.zeros((len(self.rows), len(q)), np.int64)
+        cnt = np.zeros(len(self.rows), np.uint64)
+        st = _abi.lib().zk_lh_snapshot_quantiles(self.blob, len(self.blob), q.ctypes.data, len(q), lo.ctypes.data,
+                                                 hi.ctypes.data, cnt.ctypes.data_as(_abi._U64P))
+        if st != _abi.ZK_OK:
+            raise _abi.ZkError(st, _abi.status_str(st))
+        return lo, hi, cnt
