@@ -210,6 +210,44 @@ class zk_lh_config(C.Structure):
     ]
 
 
+ZK_WIN_MAX_WINDOWS = 1024
+ZK_WIN_HOLD_LAST = 1 << 8
+
+
+class zk_win_config(C.Structure):
+    _fields_ = [
+        ("device", C.c_int32),
+        ("num_windows", C.c_uint32),
+        ("stream", C.c_void_p),
+        ("origin_us", C.c_int64),
+        ("window_us", C.c_int64),
+        ("timing", C.c_uint32),
+        ("reserved", C.c_uint32 * 7),
+    ]
+
+
+class zk_win_counts(C.Structure):
+    _fields_ = [
+        (name, C.c_uint64)
+        for name in (
+            "partitioned_runs",
+            "partitioned_records",
+            "before_runs",
+            "before_records",
+            "after_runs",
+            "after_records",
+            "untimed_runs",
+            "untimed_records",
+            "held_runs",
+            "held_records",
+            "held_from",
+        )
+    ] + [("reserved", C.c_uint64 * 5)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
 ZK_RT_WITH_DEPS = 0
 ZK_RT_ONLY = 1
 ZK_RL_ANY_RPC = 0xFFFFFFFF
@@ -412,6 +450,16 @@ _SIGNATURES = [
     ("zk_store_get_top", C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _U64P]),
     ("zk_moments_plus", C.c_int, [C.POINTER(zk_moments), C.POINTER(zk_moments), C.POINTER(zk_moments)]),
     ("zk_link_table_compact", C.c_int, [C.POINTER(zk_link_table), C.c_uint32, _P, C.c_uint64, _U64P]),
+    # include/zkwindow.h: the device trace-time partition
+    ("zk_win_create", C.c_int, [C.POINTER(zk_win_config), C.POINTER(_P)]),
+    ("zk_win_destroy", C.c_int, [_P]),
+    ("zk_win_last_error", C.c_char_p, [_P]),
+    ("zk_win_set_windows", C.c_int, [_P, C.c_int64, C.c_int64, C.c_uint32]),
+    ("zk_win_plan", C.c_int, [_P, C.c_uint64, _U64P, _U64P, _U64P]),
+    ("zk_win_partition", C.c_int, [_P, C.POINTER(zk_span_cols), C.c_uint32, C.POINTER(zk_span_cols), _U64P,
+                                   C.POINTER(zk_win_counts)]),
+    ("zk_win_phase_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zk_win_index", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_uint32, _U32P]),
 ]
 
 SYMBOLS = [s[0] for s in _SIGNATURES]

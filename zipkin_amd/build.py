@@ -30,9 +30,10 @@ SOURCES = [
     "zk_rl.hip",
     "zk_lh.hip",
     "zk_lh_snapshot.cpp",
+    "zk_win.hip",
 ]
 HEADERS = ["zk_internal.h", "zk_cluster.h", "zk_tracegen.h", "zk_sketch_internal.h", "zk_rt_internal.h", "zk_block.h", "zk_launch.h", "zk_comm.h", "zk_rl_internal.h", "zk_lh_internal.h", "zk_lh_snapshot.h"]
-PUBLIC_HEADERS = ["zkagg.h", "zksketch.h", "zkstore.h", "zkingest.h", "zkcomm.h"]
+PUBLIC_HEADERS = ["zkagg.h", "zksketch.h", "zkstore.h", "zkingest.h", "zkcomm.h", "zkwindow.h"]
 LIB = PKG / "libzkagg.so"
 ARCH = os.environ.get("ZK_OFFLOAD_ARCH", "gfx950")
 
