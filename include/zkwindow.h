@@ -6,7 +6,8 @@
  * records over a window) a batch of span fragments has to be split by time first. This pass does that
  * split in HBM: it gives every trace a time and moves the records of a trace-clustered batch into
  * window order, so that every window's slice is again a trace-clustered batch of whole traces that
- * zk_deps_accumulate (zkagg.h) takes with ZK_BATCH_DEVICE_PTRS | ZK_BATCH_TRACE_CLUSTERED.
+ * zk_deps_accumulate (zkagg.h) takes with ZK_BATCH_DEVICE_PTRS | ZK_BATCH_TRACE_CLUSTERED. With the
+ * trace-time table (below) it also takes records in any order and traces cut at a batch edge.
  *
  * Semantics
  *  - A TRACE RUN is a maximal stretch of adjacent records with equal trace_id (the definition the join
@@ -24,6 +25,36 @@
  *    before, after and untimed runs). Inside each of these W + 1 parts the records keep the input's
  *    relative order: a stable partition. So every trace's fragments stay adjacent, and the output
  *    bytes are a function of the input alone.
+ *
+ * The rule above takes a trace's time from ONE run of ONE batch: it needs batches of whole,
+ * trace-clustered traces. For records in any order, and for row-order batches cut wherever a reader's
+ * buffer filled, the handle owns a TRACE-TIME TABLE that holds across batches:
+ *  - zk_win_observe(batch) folds a batch into the table: traceId -> the minimum first_ts over the timed
+ *    fragments of every batch observed since the last zk_win_table_reset.
+ *  - MEMBERSHIP: only timed fragments enter. A traceId is in the table exactly when some observed
+ *    fragment of it was timed, so a stored time of INT64_MAX is a real time and never "none".
+ *  - IDEMPOTENCE: the fold is a minimum; observing a batch again leaves every word of the table as it
+ *    was, and batches may be observed in any order.
+ *  - Layout: open addressing with linear probing in HBM, 16 B per slot {uint64 key, uint64 time}; key =
+ *    traceId, 0 = empty; time = first_ts with the sign bit flipped (unsigned order = signed order), all
+ *    ones in a fresh slot. `slots` is a power of two and the home slot of a traceId is
+ *        zk_mix64(trace_id ^ ZK_WIN_TABLE_SALT) & (slots - 1)
+ *    (zk_mix64: the splitmix64 finalizer, z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) *
+ *    0x94D049BB133111EB, z ^ z >> 31); a probe walks upwards and wraps to slot 0. TraceId 0, a legal id,
+ *    lives in one extra slot at index `slots`, whose key word is a presence flag.
+ *  - SIZING: before anything of a batch is inserted the call counts the batch's trace runs and makes
+ *    sure that slots >= 2 * (traces in the table + runs in the batch), rounded up to a power of two
+ *    (at least 1024). The load so never exceeds 1/2. A trace-clustered batch pays for its traces,
+ *    not its records; an any-order batch, where every record is a run, for its records. The table only
+ *    grows (the old content is rehashed into the new table); a refused allocation is ZK_ERR_CAPACITY
+ *    and changes nothing.
+ *  - zk_win_partition with ZK_WIN_TRACE_TABLE classes every RECORD by its trace's time in the table
+ *    and then partitions exactly as above. The output is the same stable partition, over per-record
+ *    classes, and its bytes are a function of (input, table) alone. For a trace-clustered batch every
+ *    part is again trace-clustered; a trace cut at the end of batch k is the last run of its window's
+ *    part of batch k and its continuation the first run of the same window's part of batch k + 1,
+ *    which is what ZK_BATCH_CONTINUES (zkagg.h) joins. For an any-order batch a part is in any order,
+ *    but every fragment of a trace, from every observed batch, lies in the same window.
  *
  * Conventions are those of zkagg.h: every entry point returns zk_status; a handle is not
  * thread-safe; all device work of a handle is ordered on one HIP stream.
@@ -44,6 +75,14 @@ extern "C" {
    next batch); zk_win_counts.held_from is its first record. Carrying those records over is the
    caller's business: nothing is held in the handle. */
 #define ZK_WIN_HOLD_LAST (1u << 8)
+/* batch flag of zk_win_partition: trace times come from the handle's trace-time table (see above), so
+   the batch need not hold whole traces. ZK_BATCH_TRACE_CLUSTERED is then optional; ZK_WIN_HOLD_LAST
+   together with it is ZK_ERR_INVALID_ARG (nothing needs holding). Observe every batch first: a timed
+   record whose traceId is not in the table goes to the rest as untimed and is counted in
+   zk_win_counts.unobserved_records. */
+#define ZK_WIN_TRACE_TABLE (1u << 9)
+/* the salt of the table's slot function */
+#define ZK_WIN_TABLE_SALT 0xA0761D6478BD642Full
 
 typedef struct zk_win_config {
     int32_t  device;        /* HIP device ordinal */
@@ -63,8 +102,12 @@ typedef struct zk_win_counts {
     uint64_t untimed_runs, untimed_records;           /* no timed fragment */
     uint64_t held_runs, held_records;                 /* ZK_WIN_HOLD_LAST: the last run (else 0) */
     uint64_t held_from;                               /* first held record of the input; n when none */
-    uint64_t reserved[5];
+    uint64_t unobserved_records;                      /* ZK_WIN_TRACE_TABLE: timed records whose traceId the
+                                                         table does not hold (else 0) */
+    uint64_t reserved[4];
 } zk_win_counts;
+/* With ZK_WIN_TRACE_TABLE the *_records keep their meaning, the *_runs count runs (adjacent equal
+   traceIds) by the class the table gives them, held_runs = held_records = 0 and held_from = n. */
 
 typedef struct zk_win zk_win;
 
@@ -82,9 +125,11 @@ zk_status   zk_win_set_windows(zk_win* win, int64_t origin_us, int64_t window_us
 zk_status   zk_win_plan(const zk_win* win, uint64_t n, uint64_t* chunk_records, uint64_t* range_records,
                         uint64_t* ranges);
 /* Partition `in` (n records) into `out` by the handle's windows.
- *   flags    ZK_BATCH_TRACE_CLUSTERED is required (else ZK_ERR_UNSUPPORTED: any-order input is not
- *            taken). ZK_BATCH_DEVICE_PTRS: `in` holds device pointers; without it `in` is host memory,
- *            staged, and the call waits for the staging copy. ZK_WIN_HOLD_LAST: see above.
+ *   flags    ZK_BATCH_TRACE_CLUSTERED is required unless ZK_WIN_TRACE_TABLE is given (else
+ *            ZK_ERR_UNSUPPORTED: without the table any-order input is not taken).
+ *            ZK_BATCH_DEVICE_PTRS: `in` holds device pointers; without it `in` is host memory,
+ *            staged, and the call waits for the staging copy. ZK_WIN_HOLD_LAST, ZK_WIN_TRACE_TABLE:
+ *            see above.
  *   out      always seven DEVICE columns of capacity in->n (out->n is ignored); it must not overlap
  *            `in` (ZK_ERR_INVALID_ARG). A refused call leaves it unwritten.
  *   offsets  host array of W + 2 entries: window w is out[offsets[w], offsets[w + 1]), the rest is
@@ -98,9 +143,38 @@ zk_status   zk_win_plan(const zk_win* win, uint64_t n, uint64_t* chunk_records, 
 zk_status   zk_win_partition(zk_win* win, const zk_span_cols* in, uint32_t flags, const zk_span_cols* out,
                              uint64_t* offsets, zk_win_counts* counts);
 /* Device time of the passes of the last zk_win_partition, from HIP events, in ms: the time pass, the
-   resolve, the histogram, the scan, the scatter, the final gather. Needs zk_win_config.timing (without it
-   no event is recorded); ZK_ERR_INVALID_ARG without it or before the first partition. */
+   resolve, the histogram, the scan, the scatter, the final gather. With ZK_WIN_TRACE_TABLE slot 0 is the
+   table lookup and slot 1 is 0. Needs zk_win_config.timing (without it no event is recorded);
+   ZK_ERR_INVALID_ARG without it or before the first partition. */
 zk_status   zk_win_phase_ms(zk_win* win, double out[6]);
+
+/* ---- the trace-time table. Every call refuses a NULL handle or argument with ZK_ERR_INVALID_ARG
+   before any device is touched; errors go to zk_win_last_error. ---- */
+/* Fold a batch into the table. Only trace_id, first_ts and flags of `in` are read. flags:
+   ZK_BATCH_DEVICE_PTRS as in zk_win_partition (a host batch is staged, 20 B per record, and the call
+   waits for its staging copy); ZK_BATCH_TRACE_CLUSTERED is accepted and changes nothing (runs are
+   found either way: one table update per run and row of 64 records). The call synchronises once, to
+   read the run count it sizes the table by (see SIZING; growing synchronises once more). The inserts are
+   queued on the handle's stream behind that: DEVICE columns must stay as they are until the handle's
+   next synchronising call (zk_win_table_info, zk_win_table_lookup, zk_win_partition, zk_win_observe).
+   n == 0 is ZK_OK. */
+zk_status   zk_win_observe(zk_win* win, const zk_span_cols* in, uint32_t flags);
+/* Empty the table; the allocation (slots) is kept. */
+zk_status   zk_win_table_reset(zk_win* win);
+/* Grow the table to at least 2 * traces slots now. A hint: it never shrinks the table and the content
+   is kept. */
+zk_status   zk_win_table_reserve(zk_win* win, uint64_t traces);
+/* slots (0 before the first allocation), traceIds in the table, bytes of HBM the table holds. Any of the
+   three pointers may be NULL. Synchronises. */
+zk_status   zk_win_table_info(zk_win* win, uint64_t* slots, uint64_t* traces, uint64_t* bytes);
+/* The table's answer for n traceIds (host memory, or device with ZK_BATCH_DEVICE_PTRS): t and found are
+   HOST arrays of n entries; found[i] = 1 and t[i] = the trace's time when trace_ids[i] is in the table,
+   else found[i] = 0 and t[i] is unspecified. Synchronises. */
+zk_status   zk_win_table_lookup(zk_win* win, const uint64_t* trace_ids, uint64_t n, uint32_t flags, int64_t* t,
+                                uint8_t* found);
+/* Device time in ms of the last zk_win_observe: the run count, the sizing step (the count's copy and,
+   when the table grew, the rehash), the inserts. Needs zk_win_config.timing; waits for the inserts. */
+zk_status   zk_win_observe_ms(zk_win* win, double out[3]);
 /* The window rule above on the host (no HIP): *w = the window of trace time t, or num_windows when t is
    before or after. ZK_ERR_INVALID_ARG for window_us <= 0, num_windows 0 or > ZK_WIN_MAX_WINDOWS. */
 zk_status   zk_win_index(int64_t t, int64_t origin_us, int64_t window_us, uint32_t num_windows, uint32_t* w);

@@ -212,6 +212,8 @@ class zk_lh_config(C.Structure):
 
 ZK_WIN_MAX_WINDOWS = 1024
 ZK_WIN_HOLD_LAST = 1 << 8
+ZK_WIN_TRACE_TABLE = 1 << 9
+ZK_WIN_TABLE_SALT = 0xA0761D6478BD642F
 
 
 class zk_win_config(C.Structure):
@@ -241,11 +243,14 @@ class zk_win_counts(C.Structure):
             "held_runs",
             "held_records",
             "held_from",
+            "unobserved_records",
         )
-    ] + [("reserved", C.c_uint64 * 5)]
+    ] + [("reserved", C.c_uint64 * 4)]
 
-    def as_dict(self) -> dict:
-        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+    def as_dict(self, table: bool = False) -> dict:
+        """The counts of a partition; unobserved_records only for a table-mode one (it is 0 otherwise)."""
+        skip = ("reserved",) if table else ("reserved", "unobserved_records")
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k not in skip}
 
 
 ZK_RT_WITH_DEPS = 0
@@ -460,6 +465,12 @@ _SIGNATURES = [
                                    C.POINTER(zk_win_counts)]),
     ("zk_win_phase_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_win_index", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_uint32, _U32P]),
+    ("zk_win_observe", C.c_int, [_P, C.POINTER(zk_span_cols), C.c_uint32]),
+    ("zk_win_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zk_win_table_reset", C.c_int, [_P]),
+    ("zk_win_table_reserve", C.c_int, [_P, C.c_uint64]),
+    ("zk_win_table_info", C.c_int, [_P, _U64P, _U64P, _U64P]),
+    ("zk_win_table_lookup", C.c_int, [_P, _U64P, C.c_uint64, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8)]),
 ]
 
 SYMBOLS = [s[0] for s in _SIGNATURES]

@@ -32,6 +32,17 @@
 //
 // HBM traffic per record: 20 B read by the time pass (traceId, first_ts, flags), 2 B written and 4 B
 // read of win[], 48 B read and 48 B written by the scatter.
+//
+// Table mode (ZK_WIN_TRACE_TABLE), for records in any order and traces cut at a batch edge: a trace's
+// time comes from a traceId-keyed table in HBM that zk_win_observe fills from every batch first.
+//   k_wt_runs      the batch's run starts; the host sizes the table by them before anything is inserted
+//   k_wt_observe   one table update per (run, row of 64 records): a probe, then at most one CAS on the
+//                  key and one 64-bit atomic minimum on the time
+//   k_wt_rehash    the old table's keys into a grown one; k_wt_clear empties a table
+//   k_wt_lookup    stands in for k_win_time and k_win_resolve: win[i] from the table for every record;
+//                  every range is left without an entering or a leaving run, so the passes from
+//                  k_win_hist on run as they are
+//   k_wt_query     zk_win_table_lookup
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <string.h>
@@ -40,6 +51,7 @@
 
 #include "zk_guard.h"
 #include "zk_launch.h"
+#include "zk_tracegen.h"
 #include "zkwindow.h"
 
 namespace zk {
@@ -602,6 +614,274 @@ __global__ __launch_bounds__(kWinWG) void k_win_final(const unsigned long long* 
     if (t == 8) res[W + 2 + 8] = (unsigned long long)gstat[5];
 }
 
+// ---- the trace-time table (ZK_WIN_TRACE_TABLE) ---------------------------------------------------
+// traceId -> minimum timed first_ts over every observed batch: open addressing, linear probing, 16 B
+// per slot {key, time}; key 0 = empty, time = first_ts with the sign bit flipped, all ones when the
+// slot is made. slots is a power of two; traceId 0 lives in the extra slot at index `slots`, its key
+// word a presence flag. The host keeps the load at or below 1/2 (it sizes the table from k_wt_runs'
+// count BEFORE anything is inserted), so a probe always meets an empty slot; every probe loop is
+// bounded by `slots` all the same and reports to tstat[kTsFull] instead of spinning.
+//
+// Times only fall and keys never change once set, so whatever a plain (possibly stale, possibly torn)
+// 16-B load returns, its time word is an upper bound of the slot's time and a non-zero key is the
+// slot's key for good: "stored time <= ours: skip" is safe, an empty-looking slot is settled by the
+// CAS, and the atomics (device scope, executed at the memory side on a hipMalloc'd table) never see
+// a cache.
+constexpr unsigned long long kWinTableSalt = ZK_WIN_TABLE_SALT;
+constexpr uint64_t kWtMinSlots = 1024;
+constexpr uint64_t kWtMaxSlots = 1ull << 40;
+constexpr int kWtWG = 256;
+constexpr uint32_t kWtMaxGrid = 4096;
+enum { kTsTraces = 0, kTsRuns = 1, kTsFull = 2, kTsWords = 4 };
+
+struct alignas(16) WtSlot {
+    unsigned long long key, time;
+};
+
+__device__ inline WtSlot wt_load(const WtSlot* p) {
+    const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(p);
+    return WtSlot{v.x, v.y};
+}
+
+__device__ inline unsigned long long wt_home(unsigned long long id, unsigned long long slots) {
+    return zk_mix64(id ^ kWinTableSalt) & (slots - 1ull);
+}
+
+__global__ __launch_bounds__(kWtWG) void k_wt_clear(WtSlot* __restrict__ tab, unsigned long long count) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * kWtWG;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * kWtWG + threadIdx.x; i < count; i += stride)
+        *reinterpret_cast<ulonglong2*>(tab + i) = ulonglong2{0ull, kKeyNone};
+}
+
+// the batch's run starts, into tstat[kTsRuns] (zeroed by the host before)
+__global__ __launch_bounds__(kWtWG) void k_wt_runs(const unsigned long long* __restrict__ tid, unsigned long long n,
+                                                   unsigned long long* __restrict__ tstat) {
+    __shared__ unsigned long long s_sum;
+    const int t = threadIdx.x;
+    if (t == 0) s_sum = 0ull;
+    __syncthreads();
+    const unsigned long long stride = (unsigned long long)gridDim.x * kWtWG;
+    unsigned long long c = 0;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * kWtWG + t; i < n; i += stride)
+        c += i == 0 || tid[i - 1] != tid[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
+    if (lane_id() == 0 && c) atomicAdd(&s_sum, c);
+    __syncthreads();
+    if (t == 0 && s_sum) atomicAdd(&tstat[kTsRuns], s_sum);
+}
+
+// the old table's keys into the grown one: keys are unique, so the thread that claims a key is the
+// only writer of its time
+__global__ __launch_bounds__(kWtWG) void k_wt_rehash(const WtSlot* __restrict__ old, unsigned long long old_slots,
+                                                     WtSlot* __restrict__ tab, unsigned long long slots,
+                                                     unsigned long long* __restrict__ tstat) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * kWtWG;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * kWtWG + threadIdx.x; i <= old_slots; i += stride) {
+        const WtSlot v = wt_load(old + i);
+        if (v.key == 0ull) continue;
+        if (i == old_slots) {  // traceId 0
+            *reinterpret_cast<ulonglong2*>(tab + slots) = ulonglong2{1ull, v.time};
+            continue;
+        }
+        unsigned long long s = wt_home(v.key, slots), tries = 0;
+        for (; tries < slots; ++tries) {
+            if (atomicCAS(&tab[s].key, 0ull, v.key) == 0ull) {
+                tab[s].time = v.time;
+                break;
+            }
+            s = (s + 1ull) & (slots - 1ull);
+        }
+        if (tries == slots) atomicAdd(&tstat[kTsFull], 1ull);
+    }
+}
+
+// time[id] = min(time[id], kmin), id entering the table when it is new; true when this call claimed it
+__device__ inline bool wt_update(WtSlot* __restrict__ tab, unsigned long long slots, unsigned long long id,
+                                 unsigned long long kmin, unsigned long long* __restrict__ tstat) {
+    const unsigned long long want = id ? id : 1ull;
+    unsigned long long s = id ? wt_home(id, slots) : slots;
+    for (unsigned long long tries = 0; tries < slots; ++tries) {
+        WtSlot* p = tab + s;
+        const WtSlot v = wt_load(p);
+        unsigned long long k = v.key;
+        bool claimed = false;
+        if (k == 0ull) {
+            k = atomicCAS(&p->key, 0ull, want);
+            claimed = k == 0ull;
+            if (claimed) k = want;
+        }
+        if (k == want) {
+            if (v.time > kmin) atomicMin(&p->time, kmin);
+            return claimed;
+        }
+        s = (s + 1ull) & (slots - 1ull);
+    }
+    atomicAdd(&tstat[kTsFull], 1ull);
+    return false;
+}
+
+__device__ inline bool wt_find(const WtSlot* __restrict__ tab, unsigned long long slots, unsigned long long id,
+                               unsigned long long* time) {
+    if (slots == 0ull) return false;
+    if (id == 0ull) {
+        const WtSlot v = wt_load(tab + slots);
+        *time = v.time;
+        return v.key != 0ull;
+    }
+    unsigned long long s = wt_home(id, slots);
+    for (unsigned long long tries = 0; tries < slots; ++tries) {
+        const WtSlot v = wt_load(tab + s);
+        if (v.key == id) {
+            *time = v.time;
+            return true;
+        }
+        if (v.key == 0ull) return false;
+        s = (s + 1ull) & (slots - 1ull);
+    }
+    return false;
+}
+
+// the row's pieces of runs: lanes [s, e] around this lane with equal traceId (lane 0 starts a piece
+// whatever came before the row), and the minimum timed key over them in lane s (k_win_time's scheme)
+struct RowPiece {
+    uint32_t s;
+    bool any_timed;
+    unsigned long long kmin;
+};
+
+__device__ inline RowPiece row_piece(unsigned long long mask, bool timed, unsigned long long key) {
+    const uint32_t lane = lane_id();
+    const unsigned long long mm = mask & (~0ull >> (63 - lane));
+    const unsigned long long above = lane == 63 ? 0ull : mask & (~0ull << (lane + 1));
+    RowPiece p;
+    p.s = mm ? 63u - (uint32_t)__clzll((long long)mm) : 0u;
+    const uint32_t e = above ? (uint32_t)__ffsll((long long)above) - 2u : 63u;
+    const unsigned long long seg = (~0ull >> (63 - e)) & (~0ull << p.s);
+    p.any_timed = (__ballot(timed) & seg) != 0ull;
+    p.kmin = key;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long o = __shfl_down(p.kmin, off);
+        if (lane + off <= e && o < p.kmin) p.kmin = o;
+    }
+    return p;
+}
+
+// one table update per (run, row of 64 records); a wave walks rows
+__global__ __launch_bounds__(kWtWG) void k_wt_observe(const unsigned long long* __restrict__ tid,
+                                                      const long long* __restrict__ ts, const uint32_t* __restrict__ fl,
+                                                      unsigned long long n, WtSlot* __restrict__ tab,
+                                                      unsigned long long slots, unsigned long long* __restrict__ tstat) {
+    const uint32_t lane = lane_id();
+    const unsigned long long waves = (unsigned long long)gridDim.x * (kWtWG / 64);
+    const unsigned long long rows = (n + 63ull) / 64ull;
+    uint32_t claimed = 0;
+    for (unsigned long long row = (unsigned long long)blockIdx.x * (kWtWG / 64) + (threadIdx.x >> 6); row < rows;
+         row += waves) {
+        const unsigned long long i = row * 64ull + lane;
+        const bool valid = i < n;
+        const unsigned long long id = valid ? tid[i] : 0ull;
+        const unsigned long long prev = valid && lane > 0 ? tid[i - 1] : 0ull;
+        const uint32_t f = valid ? fl[i] : 0u;
+        const long long t = valid ? ts[i] : 0ll;
+        const bool timed = (f & ZK_F_HAS_ANNOTATIONS) != 0u;
+        const unsigned long long mask = __ballot(valid && (lane == 0 || id != prev));
+        const RowPiece p = row_piece(mask, timed, timed ? (unsigned long long)t ^ kSign : kKeyNone);
+        bool c = false;
+        if (valid && lane == p.s && p.any_timed) c = wt_update(tab, slots, id, p.kmin, tstat);
+        claimed += (uint32_t)__popcll(__ballot(c));
+    }
+    if (lane == 0 && claimed) atomicAdd(&tstat[kTsTraces], (unsigned long long)claimed);
+}
+
+// table mode's time pass: win[i] = class of record i by its trace's time in the table. The first lane
+// of every row piece probes, the piece takes its answer. Every range is left with no entering and no
+// leaving run, so record_class() is win[i] and the later passes run as they are.
+__global__ __launch_bounds__(kWinWG) void k_wt_lookup(const unsigned long long* __restrict__ tid,
+                                                      const uint32_t* __restrict__ fl, unsigned long long n,
+                                                      unsigned long long range_records, WinRule rule,
+                                                      const WtSlot* __restrict__ tab, unsigned long long slots,
+                                                      uint16_t* __restrict__ win, WinRange* __restrict__ rs,
+                                                      long long* __restrict__ gstat,
+                                                      unsigned long long* __restrict__ unobserved) {
+    __shared__ uint32_t s_c[5];
+    const int t = threadIdx.x;
+    const uint32_t lane = lane_id();
+    const unsigned long long r0 = (unsigned long long)blockIdx.x * range_records;
+    const unsigned long long r1 = r0 + range_records < n ? r0 + range_records : n;
+    if (t < 5) s_c[t] = 0u;
+    __syncthreads();
+    uint32_t c_w = 0, c_b = 0, c_a = 0, c_u = 0, c_x = 0;
+    for (unsigned long long base = r0; base < r1; base += kWinWG) {
+        const unsigned long long i = base + t;
+        const bool valid = i < r1;
+        const unsigned long long id = valid ? tid[i] : 0ull;
+        const unsigned long long prev = valid && i > 0 ? tid[i - 1] : 0ull;
+        const uint32_t f = valid ? fl[i] : 0u;
+        const bool diff = valid && (i == 0 || id != prev);  // a run starts here
+        const unsigned long long mask = __ballot(valid && (lane == 0 || diff));
+        const unsigned long long mm = mask & (~0ull >> (63 - lane));
+        const uint32_t s = mm ? 63u - (uint32_t)__clzll((long long)mm) : 0u;
+        uint32_t cls = 0u;
+        if (valid && lane == s) {
+            unsigned long long key = kKeyNone;
+            const bool found = wt_find(tab, slots, id, &key);
+            cls = win_class(key, found, rule) | (found ? 0u : 0x8000u);
+        }
+        cls = __shfl(cls, (int)s);
+        const bool found = (cls & 0x8000u) == 0u;
+        cls &= 0x7FFFu;
+        if (valid) {
+            win[i] = (uint16_t)cls;
+            if (diff) {
+                c_w += cls < rule.W;
+                c_b += cls == rule.W;
+                c_a += cls == rule.W + 1;
+                c_u += cls == rule.W + 2;
+            }
+            c_x += !found && (f & ZK_F_HAS_ANNOTATIONS) != 0u;
+        }
+    }
+    if (c_w) atomicAdd(&s_c[0], c_w);
+    if (c_b) atomicAdd(&s_c[1], c_b);
+    if (c_a) atomicAdd(&s_c[2], c_a);
+    if (c_u) atomicAdd(&s_c[3], c_u);
+    if (c_x) atomicAdd(&s_c[4], c_x);
+    __syncthreads();
+    if (t == 0) {
+        WinRange o{};
+        o.first_start = r0;
+        for (int c = 0; c < 4; ++c) o.runs[c] = s_c[c];
+        o.pad = s_c[4];  // the range's unobserved records
+        rs[blockIdx.x] = o;
+        if (s_c[4]) atomicAdd(unobserved, (unsigned long long)s_c[4]);
+        if (blockIdx.x == 0) {
+            for (int c = 0; c < 4; ++c) gstat[c] = 0;
+            gstat[4] = (long long)n;  // held_from: nothing is held
+            gstat[5] = 0;
+        }
+    }
+}
+
+// zk_win_table_lookup
+__global__ __launch_bounds__(kWtWG) void k_wt_query(const unsigned long long* __restrict__ ids, unsigned long long n,
+                                                    const WtSlot* __restrict__ tab, unsigned long long slots,
+                                                    long long* __restrict__ t_out, uint8_t* __restrict__ found_out) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * kWtWG;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * kWtWG + threadIdx.x; i < n; i += stride) {
+        unsigned long long key = kKeyNone;
+        const bool found = wt_find(tab, slots, ids[i], &key);
+        t_out[i] = (long long)(key ^ kSign);
+        found_out[i] = found ? 1 : 0;
+    }
+}
+
+uint32_t wt_grid(uint64_t items) {
+    const uint64_t g = (items + kWtWG - 1) / kWtWG;
+    return (uint32_t)(g < 1 ? 1 : g > kWtMaxGrid ? kWtMaxGrid : g);
+}
+
 bool rule_ok(int64_t window_us, uint32_t W) { return window_us > 0 && W >= 1 && W <= ZK_WIN_MAX_WINDOWS; }
 
 void win_plan(uint64_t n, uint64_t* range_records, uint64_t* ranges) {
@@ -631,7 +911,16 @@ struct zk_win {
     hipEvent_t ev[kWinPhases + 1] = {};  // around the passes of the last partition (zk_win_phase_ms)
     bool timing = false;  // zk_win_config.timing: record the events
     bool timed = false;
+    bool timed_table = false;  // the last timed partition ran in table mode
     size_t win_bytes = 0, ranges_bytes = 0, matrix_bytes = 0, tmp_bytes = 0, res_bytes = 0, stage_bytes = 0;
+    // the trace-time table
+    void* table = nullptr;   // WtSlot [slots + 1]
+    void* tstat = nullptr;   // u64 [kTsWords]: traces, the last batch's runs, probe loops that ran out
+    void* query = nullptr;   // zk_win_table_lookup: ids, times, found
+    uint64_t slots = 0;
+    size_t query_bytes = 0;
+    hipEvent_t oev[4] = {};  // around the passes of the last observe (zk_win_observe_ms)
+    bool otimed = false;
     std::string err;
 };
 
@@ -683,6 +972,51 @@ const void* col_ptr(const zk_span_cols* c, int k) {
     }
 }
 
+zk_status ensure_tstat(zk_win* h) {
+    if (h->tstat) return ZK_OK;
+    void* q = nullptr;
+    size_t have = 0;
+    const zk_status st = grow(h, &q, &have, kTsWords * 8, "the table's counters");
+    if (st != ZK_OK) return st;
+    WIN_HIP(h, hipMemsetAsync(q, 0, kTsWords * 8, h->stream));
+    h->tstat = q;
+    return ZK_OK;
+}
+
+// The table at `want` slots or more (a power of two, at least kWtMinSlots): a new table is made and
+// cleared, the old one's keys move into it (k_wt_rehash) and the old one is freed after the stream
+// has drained. rehashed: whether the table grew. A refused allocation changes nothing.
+zk_status ensure_slots(zk_win* h, uint64_t want, bool* rehashed) {
+    if (rehashed) *rehashed = false;
+    if (want <= h->slots && h->table) return ZK_OK;
+    if (want > kWtMaxSlots) return wfail(h, ZK_ERR_CAPACITY, "a trace-time table of more than 2^40 slots");
+    uint64_t slots = kWtMinSlots;
+    while (slots < want) slots <<= 1;
+    zk_status st = ensure_tstat(h);
+    if (st != ZK_OK) return st;
+    void* q = nullptr;
+    size_t have = 0;
+    if ((st = grow(h, &q, &have, (size_t)(slots + 1) * sizeof(WtSlot), "the trace-time table (16 B per slot)")) != ZK_OK)
+        return st;
+    hipError_t e = launch_checked("k_wt_clear", k_wt_clear, dim3(wt_grid(slots + 1)), dim3(kWtWG), 0, h->stream, (WtSlot*)q,
+                                  (unsigned long long)(slots + 1));
+    if (e == hipSuccess && h->table)
+        e = launch_checked("k_wt_rehash", k_wt_rehash, dim3(wt_grid(h->slots + 1)), dim3(kWtWG), 0, h->stream,
+                           (const WtSlot*)h->table, (unsigned long long)h->slots, (WtSlot*)q, (unsigned long long)slots,
+                           (unsigned long long*)h->tstat);
+    if (e == hipSuccess && h->table) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream);
+        (void)hipFree(q);
+        return wfail(h, is_refusal(e) ? ZK_ERR_CAPACITY : ZK_ERR_HIP, std::string("growing the trace-time table: ") + launch_error_str(e));
+    }
+    if (h->table) (void)hipFree(h->table);
+    if (rehashed) *rehashed = h->table != nullptr;
+    h->table = q;
+    h->slots = slots;
+    return ZK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -727,9 +1061,11 @@ zk_status zk_win_destroy(zk_win* h) {
     if (!h) return ZK_ERR_INVALID_ARG;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {h->win, h->ranges, h->matrix, h->tmp, h->res, h->stage})
+    for (void* p : {h->win, h->ranges, h->matrix, h->tmp, h->res, h->stage, h->table, h->tstat, h->query})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->oev)
         if (e) (void)hipEventDestroy(e);
     if (h->own) (void)hipStreamDestroy(h->own);
     delete h;
@@ -769,6 +1105,7 @@ zk_status zk_win_phase_ms(zk_win* h, double out[6]) {
         WIN_HIP(h, hipEventElapsedTime(&ms, h->ev[k], h->ev[k + 1]));
         out[k] = ms;
     }
+    if (h->timed_table) out[1] = 0.0;  // (no resolve in table mode: slot 0 is the lookup)
     return ZK_OK;
     ZK_GUARD_END
 }
@@ -778,10 +1115,14 @@ zk_status zk_win_partition(zk_win* h, const zk_span_cols* in, uint32_t flags, co
     ZK_GUARD_BEGIN
     if (!h) return ZK_ERR_INVALID_ARG;
     if (!in || !out || !offsets) return wfail(h, ZK_ERR_INVALID_ARG, "null argument");
-    if (flags & ~(ZK_BATCH_DEVICE_PTRS | ZK_BATCH_TRACE_CLUSTERED | ZK_WIN_HOLD_LAST))
+    if (flags & ~(ZK_BATCH_DEVICE_PTRS | ZK_BATCH_TRACE_CLUSTERED | ZK_WIN_HOLD_LAST | ZK_WIN_TRACE_TABLE))
         return wfail(h, ZK_ERR_INVALID_ARG, "unknown batch flag");
-    if (!(flags & ZK_BATCH_TRACE_CLUSTERED))
-        return wfail(h, ZK_ERR_UNSUPPORTED, "the window partition takes trace-clustered batches only");
+    const bool table_mode = (flags & ZK_WIN_TRACE_TABLE) != 0;
+    if (table_mode && (flags & ZK_WIN_HOLD_LAST))
+        return wfail(h, ZK_ERR_INVALID_ARG, "ZK_WIN_HOLD_LAST with ZK_WIN_TRACE_TABLE: nothing needs holding");
+    if (!table_mode && !(flags & ZK_BATCH_TRACE_CLUSTERED))
+        return wfail(h, ZK_ERR_UNSUPPORTED,
+                     "without ZK_WIN_TRACE_TABLE the window partition takes trace-clustered batches only");
     const uint64_t n = in->n;
     const uint32_t W = h->rule.W;
     if (n > kWinMaxRecords) return wfail(h, ZK_ERR_UNSUPPORTED, "more than 2^40 records in one batch");
@@ -817,7 +1158,7 @@ zk_status zk_win_partition(zk_win* h, const zk_span_cols* in, uint32_t flags, co
         return st;
     if ((st = grow(h, &h->matrix, &h->matrix_bytes, items * 8, "the window x range counts")) != ZK_OK) return st;
     if ((st = grow(h, &h->tmp, &h->tmp_bytes, tb ? tb : 8, "the scan's workspace")) != ZK_OK) return st;
-    if ((st = grow(h, &h->res, &h->res_bytes, (ZK_WIN_MAX_WINDOWS + 2 + kResTail) * 8, "the result words")) != ZK_OK)
+    if ((st = grow(h, &h->res, &h->res_bytes, (ZK_WIN_MAX_WINDOWS + 2 + kResTail + 1) * 8, "the result words")) != ZK_OK)
         return st;
     WinCols ic{};
     if (dev_in) {
@@ -851,12 +1192,21 @@ zk_status zk_win_partition(zk_win* h, const zk_span_cols* in, uint32_t flags, co
     for (hipEvent_t& e : h->ev)
         if (timing && !e) WIN_HIP(h, hipEventCreate(&e));
     h->timed = false;
+    unsigned long long* unobserved = res + W + 2 + kResTail;  // (after what k_win_final writes)
+    if (table_mode) WIN_HIP(h, hipMemsetAsync(unobserved, 0, 8, h->stream));
     if (timing) WIN_HIP(h, hipEventRecord(h->ev[0], h->stream));
-    WIN_HIP(h, launch_checked("k_win_time", k_win_time, dim3(ranges), dim3(kWinWG), 0, h->stream, ic.trace_id, ic.first_ts,
-                              ic.flags, (unsigned long long)n, (unsigned long long)rr, h->rule, win, rs));
-    if (timing) WIN_HIP(h, hipEventRecord(h->ev[1], h->stream));
-    WIN_HIP(h, launch_checked("k_win_resolve", k_win_resolve, dim3(1), dim3(kWinWG), 0, h->stream, rs, ranges,
-                              (unsigned long long)n, h->rule, hold, gstat));
+    if (table_mode) {
+        WIN_HIP(h, launch_checked("k_wt_lookup", k_wt_lookup, dim3(ranges), dim3(kWinWG), 0, h->stream, ic.trace_id, ic.flags,
+                                  (unsigned long long)n, (unsigned long long)rr, h->rule, (const WtSlot*)h->table,
+                                  (unsigned long long)h->slots, win, rs, gstat, unobserved));
+        if (timing) WIN_HIP(h, hipEventRecord(h->ev[1], h->stream));
+    } else {
+        WIN_HIP(h, launch_checked("k_win_time", k_win_time, dim3(ranges), dim3(kWinWG), 0, h->stream, ic.trace_id,
+                                  ic.first_ts, ic.flags, (unsigned long long)n, (unsigned long long)rr, h->rule, win, rs));
+        if (timing) WIN_HIP(h, hipEventRecord(h->ev[1], h->stream));
+        WIN_HIP(h, launch_checked("k_win_resolve", k_win_resolve, dim3(1), dim3(kWinWG), 0, h->stream, rs, ranges,
+                                  (unsigned long long)n, h->rule, hold, gstat));
+    }
     if (timing) WIN_HIP(h, hipEventRecord(h->ev[2], h->stream));
     WIN_HIP(h, launch_checked("k_win_hist", k_win_hist, dim3(ranges), dim3(kWinWG), 0, h->stream, (const uint16_t*)win, rs,
                               (unsigned long long)n, (unsigned long long)rr, W, ranges, (const long long*)gstat, M));
@@ -870,10 +1220,11 @@ zk_status zk_win_partition(zk_win* h, const zk_span_cols* in, uint32_t flags, co
     WIN_HIP(h, launch_checked("k_win_final", k_win_final, dim3(1), dim3(kWinWG), 0, h->stream, (const unsigned long long*)M,
                               ranges, W, (const WinRange*)rs, (const long long*)gstat, res));
     if (timing) WIN_HIP(h, hipEventRecord(h->ev[6], h->stream));
-    unsigned long long host[ZK_WIN_MAX_WINDOWS + 2 + kResTail];
-    WIN_HIP(h, hipMemcpyAsync(host, res, (size_t)(W + 2 + kResTail) * 8, hipMemcpyDeviceToHost, h->stream));
+    unsigned long long host[ZK_WIN_MAX_WINDOWS + 2 + kResTail + 1];
+    WIN_HIP(h, hipMemcpyAsync(host, res, (size_t)(W + 2 + kResTail + 1) * 8, hipMemcpyDeviceToHost, h->stream));
     WIN_HIP(h, hipStreamSynchronize(h->stream));  // (also: the staging copies have read the host batch)
     h->timed = timing;
+    h->timed_table = table_mode;
     for (uint32_t w = 0; w < W + 2; ++w) offsets[w] = host[w];
     const unsigned long long* tail = host + W + 2;
     cz.partitioned_runs = tail[0];
@@ -887,7 +1238,144 @@ zk_status zk_win_partition(zk_win* h, const zk_span_cols* in, uint32_t flags, co
     cz.held_from = tail[7];
     cz.held_runs = tail[8];
     cz.held_records = n - tail[7];
+    cz.unobserved_records = table_mode ? tail[kResTail] : 0;
     if (counts) *counts = cz;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_win_observe(zk_win* h, const zk_span_cols* in, uint32_t flags) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (!in) return wfail(h, ZK_ERR_INVALID_ARG, "null argument");
+    if (flags & ~(ZK_BATCH_DEVICE_PTRS | ZK_BATCH_TRACE_CLUSTERED)) return wfail(h, ZK_ERR_INVALID_ARG, "unknown batch flag");
+    const uint64_t n = in->n;
+    if (n > kWinMaxRecords) return wfail(h, ZK_ERR_UNSUPPORTED, "more than 2^40 records in one batch");
+    if (n == 0) return ZK_OK;
+    if (!in->trace_id || !in->first_ts || !in->flags) return wfail(h, ZK_ERR_INVALID_ARG, "null column");
+    WIN_HIP(h, hipSetDevice(h->device));
+    zk_status st = ensure_tstat(h);
+    if (st != ZK_OK) return st;
+    const unsigned long long* tid = (const unsigned long long*)in->trace_id;
+    const long long* ts = (const long long*)in->first_ts;
+    const uint32_t* fl = in->flags;
+    if (!(flags & ZK_BATCH_DEVICE_PTRS)) {
+        // a host batch: the three columns the table reads, staged (each 256-B aligned)
+        const size_t a8 = (n * 8 + 255) / 256 * 256, a4 = (n * 4 + 255) / 256 * 256;
+        if ((st = grow(h, &h->stage, &h->stage_bytes, 2 * a8 + a4, "staging a host batch (20 B per record)")) != ZK_OK)
+            return st;
+        uint8_t* s = (uint8_t*)h->stage;
+        WIN_HIP(h, hipMemcpyAsync(s, in->trace_id, n * 8, hipMemcpyHostToDevice, h->stream));
+        WIN_HIP(h, hipMemcpyAsync(s + a8, in->first_ts, n * 8, hipMemcpyHostToDevice, h->stream));
+        WIN_HIP(h, hipMemcpyAsync(s + 2 * a8, in->flags, n * 4, hipMemcpyHostToDevice, h->stream));
+        tid = (const unsigned long long*)s;
+        ts = (const long long*)(s + a8);
+        fl = (const uint32_t*)(s + 2 * a8);
+    }
+    unsigned long long* tstat = (unsigned long long*)h->tstat;
+    const bool timing = h->timing;
+    for (hipEvent_t& e : h->oev)
+        if (timing && !e) WIN_HIP(h, hipEventCreate(&e));
+    h->otimed = false;
+    WIN_HIP(h, hipMemsetAsync(tstat + kTsRuns, 0, 8, h->stream));
+    if (timing) WIN_HIP(h, hipEventRecord(h->oev[0], h->stream));
+    WIN_HIP(h, launch_checked("k_wt_runs", k_wt_runs, dim3(wt_grid(n)), dim3(kWtWG), 0, h->stream, tid, (unsigned long long)n,
+                              tstat));
+    if (timing) WIN_HIP(h, hipEventRecord(h->oev[1], h->stream));
+    unsigned long long host[kTsWords];
+    WIN_HIP(h, hipMemcpyAsync(host, tstat, sizeof host, hipMemcpyDeviceToHost, h->stream));
+    WIN_HIP(h, hipStreamSynchronize(h->stream));  // the call's one synchronisation (also: the staging copies are done)
+    if (host[kTsFull]) return wfail(h, ZK_ERR_HIP, "the trace-time table ran full (the sizing rule was broken)");
+    if (host[kTsRuns] == 0 || host[kTsRuns] > n) return wfail(h, ZK_ERR_HIP, "run count out of range");
+    // load <= 1/2 whatever the batch holds: every run might be a new trace
+    if ((st = ensure_slots(h, 2 * (host[kTsTraces] + host[kTsRuns]), nullptr)) != ZK_OK) return st;
+    if (timing) WIN_HIP(h, hipEventRecord(h->oev[2], h->stream));
+    const uint64_t rows = (n + 63) / 64;
+    WIN_HIP(h, launch_checked("k_wt_observe", k_wt_observe, dim3(wt_grid(rows * 64)), dim3(kWtWG), 0,
+                              h->stream, tid, ts, fl, (unsigned long long)n, (WtSlot*)h->table, (unsigned long long)h->slots,
+                              tstat));
+    if (timing) WIN_HIP(h, hipEventRecord(h->oev[3], h->stream));
+    h->otimed = timing;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_win_observe_ms(zk_win* h, double out[3]) {
+    ZK_GUARD_BEGIN
+    if (!h || !out) return ZK_ERR_INVALID_ARG;
+    if (!h->otimed) return wfail(h, ZK_ERR_INVALID_ARG, "no timed observe has run (zk_win_config.timing)");
+    WIN_HIP(h, hipSetDevice(h->device));
+    WIN_HIP(h, hipEventSynchronize(h->oev[3]));
+    for (int k = 0; k < 3; ++k) {
+        float ms = 0.f;
+        WIN_HIP(h, hipEventElapsedTime(&ms, h->oev[k], h->oev[k + 1]));
+        out[k] = ms;
+    }
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_win_table_reset(zk_win* h) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (!h->table) return ZK_OK;
+    WIN_HIP(h, hipSetDevice(h->device));
+    WIN_HIP(h, launch_checked("k_wt_clear", k_wt_clear, dim3(wt_grid(h->slots + 1)), dim3(kWtWG), 0, h->stream,
+                              (WtSlot*)h->table, (unsigned long long)(h->slots + 1)));
+    WIN_HIP(h, hipMemsetAsync(h->tstat, 0, kTsWords * 8, h->stream));
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_win_table_reserve(zk_win* h, uint64_t traces) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (traces > kWtMaxSlots / 2) return wfail(h, ZK_ERR_CAPACITY, "a trace-time table of more than 2^40 slots");
+    WIN_HIP(h, hipSetDevice(h->device));
+    return ensure_slots(h, 2 * traces, nullptr);
+    ZK_GUARD_END
+}
+
+zk_status zk_win_table_info(zk_win* h, uint64_t* slots, uint64_t* traces, uint64_t* bytes) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    unsigned long long host[kTsWords] = {};
+    if (h->tstat) {
+        WIN_HIP(h, hipSetDevice(h->device));
+        WIN_HIP(h, hipMemcpyAsync(host, h->tstat, sizeof host, hipMemcpyDeviceToHost, h->stream));
+        WIN_HIP(h, hipStreamSynchronize(h->stream));
+        if (host[kTsFull]) return wfail(h, ZK_ERR_HIP, "the trace-time table ran full (the sizing rule was broken)");
+    }
+    if (slots) *slots = h->slots;
+    if (traces) *traces = host[kTsTraces];
+    if (bytes) *bytes = h->table ? (h->slots + 1) * sizeof(WtSlot) : 0;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_win_table_lookup(zk_win* h, const uint64_t* trace_ids, uint64_t n, uint32_t flags, int64_t* t, uint8_t* found) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (flags & ~ZK_BATCH_DEVICE_PTRS) return wfail(h, ZK_ERR_INVALID_ARG, "unknown flag");
+    if (n > kWinMaxRecords) return wfail(h, ZK_ERR_UNSUPPORTED, "more than 2^40 ids in one call");
+    if (n == 0) return ZK_OK;
+    if (!trace_ids || !t || !found) return wfail(h, ZK_ERR_INVALID_ARG, "null argument");
+    WIN_HIP(h, hipSetDevice(h->device));
+    const bool dev = (flags & ZK_BATCH_DEVICE_PTRS) != 0;
+    const size_t a8 = (n * 8 + 255) / 256 * 256;
+    zk_status st = grow(h, &h->query, &h->query_bytes, 2 * a8 + n, "the lookup's ids and answers (17 B per id)");
+    if (st != ZK_OK) return st;
+    uint8_t* q = (uint8_t*)h->query;
+    const unsigned long long* ids = (const unsigned long long*)trace_ids;
+    if (!dev) {
+        WIN_HIP(h, hipMemcpyAsync(q, trace_ids, n * 8, hipMemcpyHostToDevice, h->stream));
+        ids = (const unsigned long long*)q;
+    }
+    WIN_HIP(h, launch_checked("k_wt_query", k_wt_query, dim3(wt_grid(n)), dim3(kWtWG), 0, h->stream, ids, (unsigned long long)n,
+                              (const WtSlot*)h->table, (unsigned long long)h->slots, (long long*)(q + a8), q + 2 * a8));
+    WIN_HIP(h, hipMemcpyAsync(t, q + a8, n * 8, hipMemcpyDeviceToHost, h->stream));
+    WIN_HIP(h, hipMemcpyAsync(found, q + 2 * a8, n, hipMemcpyDeviceToHost, h->stream));
+    WIN_HIP(h, hipStreamSynchronize(h->stream));
     return ZK_OK;
     ZK_GUARD_END
 }

@@ -81,19 +81,74 @@ class WindowPartition:
         self._check(self._L.zk_win_phase_ms(self._h, out))
         return dict(zip(self.PHASES, out))
 
-    def partition(self, cols, *, hold_last: bool = False, out: Optional[DeviceColumns] = None, clustered: bool = True):
-        """Partition one trace-clustered batch (host SpanColumns or DeviceColumns) by window.
+    OBSERVE_PHASES = ("runs", "grow", "insert")
+
+    def observe(self, cols, *, sync: bool = True) -> None:
+        """Fold a batch (host SpanColumns or DeviceColumns, any order) into the handle's trace-time
+        table (zk_win_observe): traceId -> the smallest first_ts over its timed fragments, over every
+        batch observed since reset_table(). Observing a batch again changes nothing. sync=False
+        leaves the inserts queued on the handle's stream: device columns must then stay as they are
+        until the next call that synchronises (table_info, trace_times, partition, observe)."""
+        import torch
+
+        flags = 0
+        ab = cols.abi()
+        if isinstance(cols, DeviceColumns):
+            flags |= _abi.ZK_BATCH_DEVICE_PTRS
+            torch.cuda.current_stream(self.device).synchronize()  # (torch may still be writing the batch)
+        self._check(self._L.zk_win_observe(self._h, C.byref(ab), flags))
+        if sync:
+            self.table_info()
+
+    def observe_ms(self) -> dict:
+        """Device time (ms) of the passes of the last observe (zk_win_observe_ms; timing=True)."""
+        out = (C.c_double * len(self.OBSERVE_PHASES))()
+        self._check(self._L.zk_win_observe_ms(self._h, out))
+        return dict(zip(self.OBSERVE_PHASES, out))
+
+    def reset_table(self) -> None:
+        """Empty the trace-time table; its allocation is kept (zk_win_table_reset)."""
+        self._check(self._L.zk_win_table_reset(self._h))
+
+    def reserve(self, traces: int) -> None:
+        """Grow the table to at least 2 * traces slots now (zk_win_table_reserve); never shrinks."""
+        self._check(self._L.zk_win_table_reserve(self._h, traces))
+
+    def table_info(self) -> dict:
+        """{"slots", "traces", "bytes"} of the trace-time table (zk_win_table_info); synchronises."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self._L.zk_win_table_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"slots": int(a.value), "traces": int(b.value), "bytes": int(c.value)}
+
+    def trace_times(self, ids):
+        """(times int64, found bool) of the table for an array of traceIds (zk_win_table_lookup);
+        times[i] means nothing where found[i] is False."""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64))
+        t = np.zeros(len(ids), np.int64)
+        f = np.zeros(len(ids), np.uint8)
+        self._check(self._L.zk_win_table_lookup(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint64)), len(ids), 0,
+                                                t.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                f.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return t, f.astype(bool)
+
+    def partition(self, cols, *, hold_last: bool = False, out: Optional[DeviceColumns] = None, clustered: bool = True,
+                  table: bool = False):
+        """Partition one batch (host SpanColumns or DeviceColumns) by window: a trace-clustered batch
+        of whole traces, or with table=True (every batch observed before) any batch, clustered or not.
 
         Returns (out, offsets, counts): `out` the records in window order then the rest (DeviceColumns
         of the batch's size, allocated unless given; out.n = the records written), `offsets` a uint64
         array of num_windows + 2 entries (window w is out[offsets[w]:offsets[w + 1]], the rest
         out[offsets[W]:offsets[W + 1]]), `counts` the zk_win_counts as a dict. hold_last leaves the
-        batch's last run out (counts["held_from"] is its first record). The call is synchronous."""
+        batch's last run out (counts["held_from"] is its first record). With table=True the counts also
+        hold "unobserved_records". The call is synchronous."""
         import torch
 
         flags = _abi.ZK_BATCH_TRACE_CLUSTERED if clustered else 0
         if hold_last:
             flags |= _abi.ZK_WIN_HOLD_LAST
+        if table:
+            flags |= _abi.ZK_WIN_TRACE_TABLE
         if isinstance(cols, DeviceColumns):
             ab = cols.abi()
             flags |= _abi.ZK_BATCH_DEVICE_PTRS
@@ -112,7 +167,7 @@ class WindowPartition:
         self._check(self._L.zk_win_partition(self._h, C.byref(ab), flags, C.byref(ob),
                                              offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(cnt)))
         out.n = int(offsets[-1])
-        return out, offsets, cnt.as_dict()
+        return out, offsets, cnt.as_dict(table)
 
 
 def window_slice(out: DeviceColumns, a: int, b: int) -> DeviceColumns:
@@ -131,6 +186,24 @@ def window_slice(out: DeviceColumns, a: int, b: int) -> DeviceColumns:
     for k, _ in COLUMNS:
         getattr(c, k).copy_(getattr(v, k))
     torch.cuda.current_stream(out.trace_id.device).synchronize()
+    return c
+
+
+def _concat_slices(slices) -> DeviceColumns:
+    """The records of [(partitioned batch, a, b)] back to back in fresh device columns (one slice that
+    window_slice would take in place is used in place)."""
+    import torch
+
+    if len(slices) == 1:
+        return window_slice(*slices[0])
+    dev = slices[0][0].trace_id.device
+    c = DeviceColumns(sum(b - a for _, a, b in slices), device=str(dev))
+    at = 0
+    for p, a, b in slices:
+        for k, _ in COLUMNS:
+            getattr(c, k)[at:at + b - a].copy_(getattr(p, k)[a:b])
+        at += b - a
+    torch.cuda.current_stream(dev).synchronize()
     return c
 
 
@@ -174,11 +247,21 @@ def _timed_min_max(cols):
 class WindowedAggregateJob:
     """ZipkinAggregateJob per time window: one Dependencies record per window instead of one for all.
 
-    run(batches) takes host SpanColumns or DeviceColumns batches, each trace-clustered and holding
-    whole traces (ZipkinAggregateJob's order="rows" input without cut traces). Any-order input and
-    traces cut at a batch edge are NOT taken: cluster such input first, or carry a cut trace over with
-    WindowPartition.partition(hold_last=True). A trace belongs to the window of its trace time, the
-    smallest first_ts of its fragments that carry annotations.
+    run(batches) takes host SpanColumns or DeviceColumns batches. A trace belongs to the window of its
+    trace time, the smallest first_ts of its fragments that carry annotations. `order` says what the
+    batches promise:
+      "whole"  (default) each batch is trace-clustered and holds whole traces. The trace time comes from
+               the batch itself; a trace that recurs in a later batch is ZK_ERR_NOT_CLUSTERED (verify).
+      "rows"   each batch is trace-clustered, but the input is cut into batches anywhere, also inside a
+               trace (what a streaming reader of row-per-trace storage feeds).
+      "any"    records in any order; a trace's fragments may lie in several batches.
+    "rows" and "any" take the trace time from the partition's trace-time table: run() resets it,
+    observes every batch, then partitions every batch with table=True (a ValueError if a batch's
+    records were not all observed). For "rows" a window's slices are accumulated in batch order with
+    clustered=True, continues=True: a cut trace ends one slice and begins the next, and the dependency
+    path joins it. For "any" a window's slices of all batches are concatenated in HBM and accumulated
+    once with clustered=False (the group join; nothing merges unclustered batches across accumulate
+    calls) and without verification, which needs trace runs.
 
     origin_us=None: the job reads the smallest and largest timed first_ts of the batches, sets origin =
     floor(min / window_us) * window_us and the number of windows from the largest; with origin_us given
@@ -200,7 +283,10 @@ class WindowedAggregateJob:
 
     def __init__(self, services, *, window_us: int, origin_us: Optional[int] = None, max_windows: int = 1024,
                  device: int = 0, strict: bool = True, aggregates=None, verify: bool = True,
-                 link_quantiles: Optional[Sequence[float]] = None):
+                 link_quantiles: Optional[Sequence[float]] = None, order: str = "whole"):
+        if order not in ("whole", "rows", "any"):
+            raise ValueError('order is "whole", "rows" or "any"')
+        self.order = order
         if window_us <= 0:
             raise ValueError("window_us must be positive")
         if not 1 <= max_windows <= _abi.ZK_WIN_MAX_WINDOWS:
@@ -271,7 +357,16 @@ class WindowedAggregateJob:
 
                 self._lh = LinkHistogram(S, device=self.device)
                 self._lh.bind(self._ctx)
-        parts = [self._win.partition(b) for b in batches]
+        if self.order == "whole":
+            parts = [self._win.partition(b) for b in batches]
+        else:
+            self._win.reset_table()
+            for b in batches:
+                self._win.observe(b)
+            parts = [self._win.partition(b, table=True, clustered=self.order == "rows") for b in batches]
+            missed = sum(c["unobserved_records"] for _, _, c in parts)
+            if missed:
+                raise ValueError(f"{missed} timed records of traces the trace-time table does not hold")
         self.rest = {k: sum(c[k] for _, _, c in parts) for k in
                      ("before_runs", "before_records", "after_runs", "after_records", "untimed_runs", "untimed_records")}
         self.stats, self.link_histograms = {}, {}
@@ -283,8 +378,14 @@ class WindowedAggregateJob:
             ctx.reset()
             if self._lh is not None:
                 self._lh.reset()
-            for p, a, b in slices:
-                ctx.accumulate(window_slice(p, a, b), clustered=True, verify=self.verify)
+            if self.order == "whole":
+                for p, a, b in slices:
+                    ctx.accumulate(window_slice(p, a, b), clustered=True, verify=self.verify)
+            elif self.order == "rows":
+                for p, a, b in slices:
+                    ctx.accumulate(window_slice(p, a, b), clustered=True, continues=True, verify=self.verify)
+            else:
+                ctx.accumulate(_concat_slices(slices), clustered=False, verify=False)
             table = ctx.finalize()
             self.stats[w] = ctx.stats()
             links = links_from_table(table, self.services)
