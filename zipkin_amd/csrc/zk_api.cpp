@@ -52,7 +52,7 @@ struct zk_ctx {
     uint64_t* links = nullptr;
     uint32_t* link_count = nullptr;
     uint64_t link_slots = 0;  // capacity of `links` in u64
-    uint64_t sorted_slots = 0;  // capacity of `sorted` in u64
+    uint64_t sorted_bytes = 0;  // capacity of `sorted`
     uint32_t link_lists = 0;  // capacity of `link_count`
     uint32_t col_off_lists = 0;  // capacity of `col_off` in lists (x nb)
     uint32_t cus = 256;
@@ -61,7 +61,7 @@ struct zk_ctx {
     uint32_t* hist = nullptr;
     uint32_t* col_off = nullptr;
     uint64_t* bucket_base = nullptr;
-    uint64_t* sorted = nullptr;
+    void* sorted = nullptr;  // K2's bucket-ordered copy: compact words, or 8-byte links
     // host-pointer input staging
     void* stage = nullptr;
     uint64_t stage_cap = 0;
@@ -161,8 +161,9 @@ zk_status ensure_links(zk_ctx* c, uint32_t grid, uint64_t stride, uint64_t n) {
     const uint64_t slots = (uint64_t)grid * stride;
     // K2's bucket-sorted copy holds every link once: at most one per record
     const uint64_t sorted_slots = n + 64 < slots ? n + 64 : slots;
+    const uint64_t sorted_bytes = sorted_slots * (reduce_compact(grid, stride) ? sizeof(uint32_t) : sizeof(uint64_t));
     const bool set_ok = slots <= c->link_slots && grid <= c->link_lists;
-    const bool scratch_ok = !c->nb || (sorted_slots <= c->sorted_slots && grid <= c->col_off_lists);
+    const bool scratch_ok = !c->nb || (sorted_bytes <= c->sorted_bytes && grid <= c->col_off_lists);
     if (set_ok && scratch_ok) return ZK_OK;
     if (!set_ok) {  // the link lists
         hipFree(c->links);
@@ -180,17 +181,17 @@ zk_status ensure_links(zk_ctx* c, uint32_t grid, uint64_t stride, uint64_t n) {
         c->link_lists = grid;
     }
     if (!scratch_ok) {  // K2/K3's scratch
-        const uint64_t ss = sorted_slots > c->sorted_slots ? sorted_slots : c->sorted_slots;
+        const uint64_t sb = sorted_bytes > c->sorted_bytes ? sorted_bytes : c->sorted_bytes;
         const uint32_t gl = grid > c->col_off_lists ? grid : c->col_off_lists;
         hipFree(c->col_off);
         hipFree(c->sorted);
         c->col_off = nullptr;
         c->sorted = nullptr;
-        c->sorted_slots = 0;
+        c->sorted_bytes = 0;
         c->col_off_lists = 0;
         ZK_HIP(c, hipMalloc(&c->col_off, (uint64_t)gl * c->nb * sizeof(uint32_t)));
-        ZK_HIP(c, hipMalloc(&c->sorted, ss * sizeof(uint64_t)));
-        c->sorted_slots = ss;
+        ZK_HIP(c, hipMalloc(&c->sorted, sb));
+        c->sorted_bytes = sb;
         c->col_off_lists = gl;
         if (!c->bucket_base) ZK_HIP(c, hipMalloc(&c->bucket_base, (c->nb + 1) * sizeof(uint64_t)));
     }
@@ -660,6 +661,7 @@ static ReduceArgs reduce_args(zk_ctx* c, uint32_t grid, uint64_t stride) {
     r.sorted = c->sorted;
     r.table = c->table;
     r.cells = (uint64_t)c->S * c->S;
+    r.compact = reduce_compact(grid, stride) ? 1u : 0u;
     return r;
 }
 

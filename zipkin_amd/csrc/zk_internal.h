@@ -159,6 +159,26 @@ void join_geometry(uint64_t n, uint32_t cus, uint32_t* grid, uint64_t* per_wg, u
 hipError_t launch_link_reduce(const uint64_t* links, const uint32_t* counts, uint64_t stride, uint64_t tiles,
                               uint64_t* table, hipStream_t s);
 // partitioned reduce (no global atomics): hist -> offsets -> bucket-sorted links -> LDS reduce
+//
+// The compact word of `sorted`. In bucket order a link's bucket is its position
+// (bucket b = [bucket_base[b], bucket_base[b + 1])), so only the cell inside the bucket is kept:
+//   short link, d < 2^21:         (cell_local << 21) | d, cell_local = cell - (b << cb_shift) < 2^10;
+//   long link, 2^21 <= d < 2^40:  kCompactEscape | g, g = list * stride + offset: the link's slot in the
+//                                 K1 lists, which keep the full (cell << 40) | d until the next join;
+//   kCompactPad:                  a reader's lane past the end of its range, never a stored word
+//                                 (g < kCompactSlotLimit - 1).
+// The lists of a batch with kCompactSlotLimit slots or more keep the 8-byte (cell << 40) | d words.
+#ifndef ZK_COMPACT_SLOT_LIMIT
+#define ZK_COMPACT_SLOT_LIMIT 0x7FFFFFFFull  // (a -D lowers it: the 8-byte path on small batches)
+#endif
+constexpr uint64_t kCompactSlotLimit = ZK_COMPACT_SLOT_LIMIT;
+static_assert(kCompactSlotLimit <= 0x7FFFFFFFull, "an escape holds the slot in 31 bits, all ones is the pad");
+constexpr uint32_t kCompactDurBits = 21;
+constexpr uint32_t kCompactDurMask = (1u << kCompactDurBits) - 1;
+constexpr uint32_t kCompactEscape = 0x80000000u;
+constexpr uint32_t kCompactPad = 0xFFFFFFFFu;
+// whether the reduce over `lists` K1 lists of `stride` slots uses the compact word
+bool reduce_compact(uint32_t lists, uint64_t stride);
 struct ReduceArgs {
     const uint64_t* links;   // per-workgroup lists from K1
     const uint32_t* counts;
@@ -168,14 +188,16 @@ struct ReduceArgs {
     uint32_t nb, cb_shift;
     uint32_t* col_off;       // [nb][lists] exclusive offsets within each bucket
     uint64_t* bucket_base;   // [nb + 1]
-    uint64_t* sorted;        // links grouped by bucket
+    void* sorted;            // links grouped by bucket: u32 compact words, or u64 links (compact = 0)
     uint64_t* table;
     uint64_t cells;
+    uint32_t compact;        // reduce_compact(lists, stride)
 };
 hipError_t launch_partitioned_reduce(const ReduceArgs& r, hipStream_t s);
 // bucket geometry for S services (nb = 0: use the atomic reduce)
 void bucket_geometry(uint32_t S, uint32_t* nb, uint32_t* cb_shift);
 uint64_t reduce_scatter_dyn_lds(uint32_t S);  // K2's dynamic LDS for S services (0: atomic reduce)
+uint32_t scatter_lists_per_wg(uint32_t lists);  // K1 lists one K2 workgroup walks as one stream
 hipError_t launch_spill(const JoinArgs& a, uint32_t spill_wgs, hipStream_t s);
 uint64_t spill_scratch_bytes_per_wg(uint32_t max_trace);
 hipError_t launch_finalize(const uint64_t* table, uint32_t S, const zk_link_table* out,

@@ -96,3 +96,13 @@ extern "C" uint64_t zk_internal_dyn_lds(uint32_t which, uint32_t S) {
     }
     return 0;
 }
+
+// internal: the link reduce's geometry for a clustered batch of n records on a device with `cus` compute
+// units -- K1's lists and their stride (join_geometry), K2's lists per workgroup, and whether `sorted`
+// takes the compact word -- for tests that size a batch by it
+extern "C" void zk_internal_reduce_geometry(uint64_t n, uint32_t cus, uint32_t* lists, uint64_t* per_wg, uint64_t* stride,
+                                            uint32_t* k2_lists_per_wg, uint32_t* compact) {
+    zk::join_geometry(n, cus, lists, per_wg, stride);
+    *k2_lists_per_wg = zk::scatter_lists_per_wg(*lists);
+    *compact = zk::reduce_compact(*lists, *stride) ? 1u : 0u;
+}

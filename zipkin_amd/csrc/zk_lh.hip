@@ -9,8 +9,9 @@
 //
 // k_lh_tiles runs after the link reduce and reads the bucket-ordered copy of the batch's links K2
 // left behind (ReduceArgs.sorted, bucket b = cells [b << cb_shift, (b + 1) << cb_shift) at
-// [bucket_base[b], bucket_base[b + 1])). A bucket's rows (512 cells x 592 bins x 4 B = 1.2 MB at m = 4)
-// do not fit the 160 KiB of LDS, so a bucket is tiled by cell sub-range: T = 2^tshift cells per tile,
+// [bucket_base[b], bucket_base[b + 1]); 4-byte compact words, zk_internal.h: a long link's word is its
+// slot in the K1 lists, which hold the full link until the next join). A bucket's rows (512 cells x
+// 592 bins x 4 B = 1.2 MB at m = 4) do not fit the 160 KiB of LDS, so a bucket is tiled by cell sub-range: T = 2^tshift cells per tile,
 // the largest power of two whose T x bins counters fit (lh_tile_shift: 128 cells at m = 2 and 3, 64
 // at 4, 32 at 5, 16 at 6, 8 at 7). One workgroup per (bucket, tile) walks the bucket's links, counts
 // those of its own cells with LDS atomics and then adds the non-zero counters to the rows in HBM with
@@ -36,6 +37,7 @@
 #include <string.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "zk_comm.h"
@@ -58,7 +60,8 @@ constexpr uint32_t kLhMaxQ = 8;  // quantiles per k_lh_quantiles pass
 constexpr uint32_t kLhTargetWGs = 512;  // (bucket, tile) pairs below this are split by link range
 
 struct LhArgs {
-    const uint64_t* sorted;       // the batch's links in bucket order
+    const void* sorted;           // the batch's links in bucket order: compact words, or 8-byte links
+    const uint64_t* links;        // the K1 lists (a compact escape's full link)
     const uint64_t* bucket_base;  // [nb + 1]
     uint32_t cb_shift;
     uint64_t cells;
@@ -69,8 +72,13 @@ struct LhArgs {
     uint32_t splits;              // workgroups per (bucket, tile)
 };
 
+template <bool COMPACT>
 __global__ __launch_bounds__(kLhWG) void k_lh_tiles(LhArgs a) {
     extern __shared__ uint32_t s_h[];  // [T][bins]
+    using W = typename std::conditional<COMPACT, uint32_t, uint64_t>::type;
+    using L = uint64_t;                   // one load
+    constexpr int WPL = COMPACT ? 2 : 1;  // words per load
+    const L* const units = static_cast<const L*>(a.sorted);
     const int tid = threadIdx.x;
     // XCD-aware order (dispatch puts block i on XCD i % 8): the blocks of one XCD take consecutive
     // work items, so the tiles of one bucket read its links through one L2
@@ -88,28 +96,57 @@ __global__ __launch_bounds__(kLhWG) void k_lh_tiles(LhArgs a) {
     const uint32_t words = T * a.bins;
     for (uint32_t x = tid; x < words; x += kLhWG) s_h[x] = 0u;
     const uint64_t cell0 = (uint64_t)b << a.cb_shift;
-    // (a link is never all ones here: bucket order exists for S <= 1024 only, cell < 2^20)
-    uint64_t nxt[kLhU];
+    // (an 8-byte link is never all ones here: bucket order exists for S <= 1024 only, cell < 2^20;
+    // nor is a compact word: zk_internal.h)
+    auto count = [&](W w) {
+        uint32_t c;
+        uint64_t d;
+        if constexpr (COMPACT) {
+            if (w & kCompactEscape) {  // (the cell of a long link is in the lists only)
+                const uint64_t x = a.links[w & ~kCompactEscape];
+                c = (uint32_t)((x >> 40) - cell0);
+                d = x & (kMaxDuration - 1);
+            } else {
+                c = w >> kCompactDurBits;
+                d = w & kCompactDurMask;
+            }
+        } else {
+            c = (uint32_t)((w >> 40) - cell0);
+            d = w & (kMaxDuration - 1);
+        }
+        if ((c >> a.tshift) != sub) return;  // another tile's cell (sub < nsub bounds c to the bucket)
+        atomicAdd(&s_h[(c & (T - 1)) * a.bins + rt_bin(d, a.m)], 1u);
+    };
+    // one 8-byte load is one link, or an aligned pair of compact words (as many bytes per load and in
+    // flight either way: with one word per load the kernel ran 0.64-0.68 ms against 0.62 ms); the words
+    // of the first and last pair outside [p0, p1) are skipped by their index
+    const uint64_t u0 = p0 / WPL, u1 = (p1 + WPL - 1) / WPL;
+    L nxt[kLhU];
 #pragma unroll
     for (int k = 0; k < kLhU; ++k) {
-        const uint64_t i = p0 + tid + (uint64_t)k * kLhWG;
-        nxt[k] = i < p1 ? a.sorted[i] : ~0ull;
+        const uint64_t u = u0 + tid + (uint64_t)k * kLhWG;
+        nxt[k] = u < u1 ? units[u] : ~(L)0;
     }
     __syncthreads();
-    for (uint64_t base = p0; base < p1; base += (uint64_t)kLhWG * kLhU) {
-        uint64_t v[kLhU];
+    for (uint64_t base = u0; base < u1; base += (uint64_t)kLhWG * kLhU) {
+        L v[kLhU];
 #pragma unroll
         for (int k = 0; k < kLhU; ++k) {
             v[k] = nxt[k];
-            const uint64_t i = base + (uint64_t)kLhWG * kLhU + tid + (uint64_t)k * kLhWG;
-            nxt[k] = i < p1 ? a.sorted[i] : ~0ull;
+            const uint64_t u = base + (uint64_t)kLhWG * kLhU + tid + (uint64_t)k * kLhWG;
+            nxt[k] = u < u1 ? units[u] : ~(L)0;
         }
 #pragma unroll
         for (int k = 0; k < kLhU; ++k) {
-            if (v[k] == ~0ull) continue;
-            const uint32_t c = (uint32_t)((v[k] >> 40) - cell0);
-            if ((c >> a.tshift) != sub) continue;  // another tile's cell (sub < nsub bounds c to the bucket)
-            atomicAdd(&s_h[(c & (T - 1)) * a.bins + rt_bin(v[k] & (kMaxDuration - 1), a.m)], 1u);
+            if (v[k] == ~(L)0) continue;
+            if constexpr (COMPACT) {
+                const uint64_t i = (base + tid + (uint64_t)k * kLhWG) * 2;
+                const uint32_t w0 = (uint32_t)v[k], w1 = (uint32_t)(v[k] >> 32);
+                if (i >= p0) count(w0);
+                if (i + 1 < p1) count(w1);
+            } else {
+                count(v[k]);
+            }
         }
     }
     __syncthreads();
@@ -421,6 +458,7 @@ hipError_t lh_accumulate(zk_lh* h, const ReduceArgs& r) {
     }
     LhArgs a{};
     a.sorted = r.sorted;
+    a.links = r.links;
     a.bucket_base = r.bucket_base;
     a.cb_shift = r.cb_shift;
     a.cells = h->cells;
@@ -432,7 +470,8 @@ hipError_t lh_accumulate(zk_lh* h, const ReduceArgs& r) {
     const uint32_t pairs = r.nb * a.nsub;
     a.splits = pairs >= kLhTargetWGs ? 1u : (kLhTargetWGs + pairs - 1) / pairs;
     const size_t lds = ((size_t)h->bins << a.tshift) * 4;
-    return launch_checked("k_lh_tiles", k_lh_tiles, dim3(pairs * a.splits), dim3(kLhWG), lds, h->stream, a);
+    return r.compact ? launch_checked("k_lh_tiles", k_lh_tiles<true>, dim3(pairs * a.splits), dim3(kLhWG), lds, h->stream, a)
+                     : launch_checked("k_lh_tiles", k_lh_tiles<false>, dim3(pairs * a.splits), dim3(kLhWG), lds, h->stream, a);
 }
 
 uint64_t lh_reserved(const zk_lh* h) { return h->reserved; }

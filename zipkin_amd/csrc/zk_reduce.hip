@@ -6,13 +6,19 @@
 // of a lane group own one link and add the 15 limbs of one 128-byte cell, so a wave instruction
 // issues four contiguous 128-B cell updates instead of 64 scattered 8-B ones (measured 5.7x faster,
 // profiles/r01_atomics_microbench.txt).
+#include <type_traits>
+
 #include "zk_block.h"
 #include "zk_internal.h"
 #include "zk_launch.h"
 
-constexpr int kK2U = 8;      // links per thread per K2 chunk
+#ifndef ZK_K2U
+#define ZK_K2U 8
+#endif
+constexpr int kK2U = ZK_K2U;  // links per thread per K2 chunk
 constexpr int kK2WG = 1024;  // K2 workgroup: 8192-link chunks (512 threads: 0.236 -> 0.199 ms on C2)
-constexpr int kK3U = 4;      // links per thread per K3 iteration (the next iteration's links prefetched)
+constexpr int kK3U = 4;      // links per thread per K3 iteration (the next iteration's links prefetched; 8 of
+                             // the 4-byte words, the same bytes in flight: 135.4 against 135.6 us, no gain)
 
 namespace zk {
 namespace {
@@ -95,8 +101,13 @@ __global__ __launch_bounds__(1024) void k_bucket_base(uint64_t* __restrict__ bas
 // in an LDS carry until the next chunk completes it: every line of the output is written whole,
 // from one workgroup, within one chunk (the per-link version wrote 64 scattered 8-byte words per
 // store instruction, at ~2.3x write amplification in WRITE_SIZE).
-constexpr int kScatterLine = 8;  // links per 64-byte line (128-byte lines: WRITE_SIZE 571 -> 396 MB, but
-                                 // their LDS carry halves the resident workgroups: 1.4x slower)
+constexpr int kScatterLineBytes = 64;  // one line of `sorted`: 16 compact words (zk_internal.h), or 8 links of
+                                       // 8 bytes. The line stays 64 B whatever the word, so the per-bucket LDS
+                                       // carry (nb x 64 B) and the resident workgroups stay (128-byte lines:
+                                       // WRITE_SIZE 571 -> 396 MB at 8-byte words, but their carry halves the
+                                       // resident workgroups: 1.4x slower). With compact words K2 writes 254 MB
+                                       // for 192 MB of words (436 for 383 MB at 8 bytes) and takes 0.189 against
+                                       // 0.202 ms: DESIGN.md §7 "The compact word", profiles/link_pack/
 // One workgroup walks LPW consecutive K1 lists as one stream: within every bucket, list w+1's range
 // follows list w's (col_off is an exclusive scan over lists), so the per-bucket cursors and line
 // carries run on across the list boundaries and K2's grid stays ~256 workgroups (one per CU)
@@ -105,17 +116,27 @@ constexpr int kScatterLine = 8;  // links per 64-byte line (128-byte lines: WRIT
 constexpr int kScatterMaxLPW = 16;
 constexpr uint32_t kScatterGrid = 256;  // (512 workgroups: 0.211 ms; 4096-link chunks at two workgroups
                                         // per CU: 0.229 ms, at one: 0.250 ms -- ab_k2_grid.txt)
-template <int U, int WG>
+// COMPACT: the output word is the 4-byte compact word of zk_internal.h, made when a chunk's links
+// leave their registers for the LDS staging (the element's list and offset give a long link's slot);
+// the staging is then 4 bytes per link beside a 2-byte bucket tag, which the write-out loop places by.
+template <int U, int WG, bool COMPACT>
 __global__ __launch_bounds__(WG) void k_link_scatter(ReduceArgs r, uint32_t lpw) {
     constexpr int C = WG * U;
+    using W = typename std::conditional<COMPACT, uint32_t, uint64_t>::type;
+    constexpr uint32_t kScatterLine = kScatterLineBytes / sizeof(W);  // words per line
     __shared__ uint32_t s_pre[kScatterMaxLPW + 4];  // exclusive prefix of the group's list counts (+ ~0 pads)
     __shared__ uint32_t s_cur[kMaxBuckets];   // output position of each bucket's first pending link
     __shared__ uint32_t s_hist[kMaxBuckets];  // links of the chunk per bucket
     __shared__ uint32_t s_off[kMaxBuckets];   // exclusive offsets in the sorted chunk
     __shared__ uint32_t s_cc[kMaxBuckets];    // carried links per bucket (< kScatterLine)
-    __shared__ uint64_t s_sorted[C];
+    __shared__ uint2 s_ld[kMaxBuckets];       // per bucket: x the chunk's write limit, y the output position of
+                                              // the sorted chunk's element 0 (one 8-byte read per link)
+    __shared__ W s_sorted[C];
+    __shared__ uint16_t s_tag[COMPACT ? C : 1];  // bucket of each staged compact word
     __shared__ uint32_t s_tmp[32];
-    extern __shared__ __attribute__((aligned(16))) uint64_t s_carry[];  // [nb][kScatterLine]
+    extern __shared__ __attribute__((aligned(16))) uint64_t s_carry_raw[];
+    W* const s_carry = reinterpret_cast<W*>(s_carry_raw);  // [nb][kScatterLine]
+    W* const out = static_cast<W*>(r.sorted);
     // XCD-aware order (dispatch puts block i on XCD i % 8): the blocks of one XCD take consecutive
     // list groups, so the per-bucket ranges of neighbouring lists (which share their boundary
     // lines) are written through one L2. Same box, clustered C2 (profiles/r03/ab_k2_xcd.txt): K2
@@ -152,6 +173,12 @@ __global__ __launch_bounds__(WG) void k_link_scatter(ReduceArgs r, uint32_t lpw)
         q = q < nl - 1 ? q : nl - 1;  // an empty group (c == 0) reads element 0 of its last list
         return r.links + (uint64_t)(w + q) * r.stride + (i - pre[q]);
     };
+    // the slot of element i (< c) in the K1 lists, for a long link's escape word (rare: a walk)
+    auto escape_of = [&](uint32_t i) -> uint32_t {
+        uint32_t q = 0;
+        while (q + 1 < nl && i >= s_pre[q + 1]) ++q;
+        return kCompactEscape | (uint32_t)((uint64_t)(w + q) * r.stride + (i - s_pre[q]));
+    };
     // the links of the chunk starting at element b0 into dst. Lists hold ~C links or more, so a
     // chunk nearly always meets at most two list boundaries: its elements are then placed with two
     // compares against the (uniform) bounds after its first list, found by a walk that only moves
@@ -187,15 +214,25 @@ __global__ __launch_bounds__(WG) void k_link_scatter(ReduceArgs r, uint32_t lpw)
     for (uint32_t base = 0; base < c; base += C) {
         const uint32_t cnt = (c - base) < (uint32_t)C ? (c - base) : (uint32_t)C;
         const bool last = base + C >= c;
-        uint64_t v[U];
+        uint64_t raw[U];
+        W v[U];
         uint32_t bk[U], rank[U];
 #pragma unroll
-        for (int k = 0; k < U; ++k) v[k] = nxt[k];
+        for (int k = 0; k < U; ++k) raw[k] = nxt[k];
         load_chunk(nxt, base + C);  // next chunk in flight
 #pragma unroll
         for (int k = 0; k < U; ++k) {
-            bk[k] = (uint32_t)((v[k] >> 40) >> r.cb_shift);
-            rank[k] = (tid + WG * k < (int)cnt) ? atomicAdd(&s_hist[bk[k]], 1u) : 0u;
+            const uint32_t cell = (uint32_t)(raw[k] >> 40);
+            bk[k] = cell >> r.cb_shift;
+            const bool in = tid + WG * k < (int)cnt;
+            if constexpr (COMPACT) {
+                const uint64_t d = raw[k] & (kMaxDuration - 1);
+                v[k] = ((cell - (bk[k] << r.cb_shift)) << kCompactDurBits) | (uint32_t)d;
+                if (in && d > kCompactDurMask) v[k] = escape_of(base + tid + WG * k);  // its slot: < kCompactSlotLimit - 1
+            } else {
+                v[k] = raw[k];
+            }
+            rank[k] = in ? atomicAdd(&s_hist[bk[k]], 1u) : 0u;
         }
         __syncthreads();
         {
@@ -211,51 +248,58 @@ __global__ __launch_bounds__(WG) void k_link_scatter(ReduceArgs r, uint32_t lpw)
 #pragma unroll
             for (int q = 0; q < BPT; ++q) {
                 const uint32_t bin = tid * BPT + q;
-                if (bin < r.nb) s_off[bin] = ex;
+                if (bin < r.nb) {
+                    s_off[bin] = ex;
+                    // the bucket's write limit for this chunk: whole lines only, but never below the
+                    // bucket's own first pending position (the line's head may belong to the previous
+                    // workgroup's range of this bucket); and where sorted element i of the chunk goes
+                    const uint32_t pos = s_cur[bin], cc = s_cc[bin];
+                    const uint32_t end = pos + cc + h[q];
+                    s_ld[bin] = make_uint2(last ? end : max(pos, end & ~(uint32_t)(kScatterLine - 1)),
+                                           pos + cc - ex);  // (mod 2^32) dest = s_ld[b].y + i
+                }
                 ex += h[q];
             }
         }
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < U; ++k)
-            if (tid + WG * k < (int)cnt) s_sorted[s_off[bk[k]] + rank[k]] = v[k];
-        // carried links: write those whose line the chunk completes, shift the rest down
-        for (uint32_t b = tid; b < r.nb; b += WG) {
-            const uint32_t cc = s_cc[b], pos = s_cur[b];
-            const uint32_t end = pos + cc + s_hist[b];
-            const uint32_t lim = last ? end : max(pos, end & ~(uint32_t)(kScatterLine - 1));
-            uint64_t* cb = s_carry + (uint64_t)b * kScatterLine;
-            for (uint32_t k = 0; k < cc; ++k) {
-                const uint32_t dest = pos + k;
-                if (dest < lim)
-                    r.sorted[dest] = cb[k];
-                else
-                    cb[dest - lim] = cb[k];  // dest - lim <= k: ascending order is safe
+            if (tid + WG * k < (int)cnt) {
+                const uint32_t at_ = s_off[bk[k]] + rank[k];
+                s_sorted[at_] = v[k];
+                if constexpr (COMPACT) s_tag[at_] = (uint16_t)bk[k];
             }
+        // carried links, one thread per carry slot (a line's carried words leave side by side): a
+        // bucket's carried links lie before the next line boundary after its pending position, so
+        // the chunk either completes their line (lim beyond all of them: written now) or leaves lim
+        // at the pending position (they stay where they are in the carry)
+        for (uint32_t x = tid; x < r.nb * kScatterLine; x += WG) {
+            const uint32_t b = x / kScatterLine, k = x % kScatterLine;
+            const uint32_t dest = s_cur[b] + k;
+            if (k < s_cc[b] && dest < s_ld[b].x) out[dest] = s_carry[x];
         }
         __syncthreads();
-        for (uint32_t i = tid; i < cnt; i += WG) {
-            const uint64_t x = s_sorted[i];
-            const uint32_t b = (uint32_t)((x >> 40) >> r.cb_shift);
-            const uint32_t pos = s_cur[b], cc = s_cc[b];
-            const uint32_t end = pos + cc + s_hist[b];
-            const uint32_t lim = last ? end : max(pos, end & ~(uint32_t)(kScatterLine - 1));
-            const uint32_t dest = pos + cc + (i - s_off[b]);
-            if (dest < lim)
-                r.sorted[dest] = x;
-            else
-                s_carry[(uint64_t)b * kScatterLine + (dest - lim)] = x;
-        }
-        __syncthreads();
+        // the cursors move on (nothing below reads them; the next chunk's histogram needs the zeros)
         for (uint32_t b = tid; b < r.nb; b += WG) {
-            const uint32_t pos = s_cur[b];
-            const uint32_t end = pos + s_cc[b] + s_hist[b];
-            // never below the bucket's own first pending position: the line's head may belong to
-            // the previous workgroup's range of this bucket
-            const uint32_t lim = last ? end : max(pos, end & ~(uint32_t)(kScatterLine - 1));
+            const uint32_t end = s_cur[b] + s_cc[b] + s_hist[b];
+            const uint32_t lim = s_ld[b].x;
             s_cur[b] = lim;
             s_cc[b] = end - lim;
             s_hist[b] = 0u;
+        }
+        for (uint32_t i = tid; i < cnt; i += WG) {
+            const W x = s_sorted[i];
+            uint32_t b;
+            if constexpr (COMPACT)
+                b = s_tag[i];
+            else
+                b = (uint32_t)((x >> 40) >> r.cb_shift);
+            const uint2 ld = s_ld[b];
+            const uint32_t lim = ld.x, dest = ld.y + i;
+            if (dest < lim)
+                out[dest] = x;
+            else
+                s_carry[(uint64_t)b * kScatterLine + (dest - lim)] = x;
         }
         __syncthreads();
     }
@@ -366,10 +410,13 @@ struct RunSums {
 // cell's run in registers -- no atomics and no LDS accumulator -- and finally adds its limbs to
 // the table with plain stores (the workgroup owns the bucket; atomics only when a small bucket
 // count is split over several workgroups).
-template <int CB_SHIFT, int P>
+// COMPACT: `sorted` holds compact words (zk_internal.h); a long link's word is its slot in the K1 lists.
+template <int CB_SHIFT, int P, bool COMPACT>
 __global__ __launch_bounds__(1 << CB_SHIFT) void k_bucket_reduce(ReduceArgs r, uint32_t splits) {
     constexpr int CB = 1 << CB_SHIFT, WG = CB, C = P * WG;
     static_assert(WG <= 1024, "one thread per cell");
+    using W = typename std::conditional<COMPACT, uint32_t, uint64_t>::type;
+    const W* const sorted = static_cast<const W*>(r.sorted);
     __shared__ uint32_t s_tmp[32];
     __shared__ uint32_t s_hist[CB];
     __shared__ uint32_t s_off[CB];
@@ -385,27 +432,40 @@ __global__ __launch_bounds__(1 << CB_SHIFT) void k_bucket_reduce(ReduceArgs r, u
     uint64_t lim[15];
 #pragma unroll
     for (int q = 0; q < 15; ++q) lim[q] = 0;
-    uint64_t nxt[P];
+    W nxt[P];
 #pragma unroll
     for (int k = 0; k < P; ++k) {
         const uint64_t i = s0 + tid + (uint64_t)k * WG;
-        nxt[k] = r.sorted[i < s1 ? i : 0];
+        nxt[k] = sorted[i < s1 ? i : 0];
     }
     __syncthreads();
     for (uint64_t base = s0; base < s1; base += C) {
         const int cnt = (int)((s1 - base) < (uint64_t)C ? (s1 - base) : (uint64_t)C);
-        uint64_t v[P];
+        W v[P];
+        uint64_t d[P];
         uint32_t cl[P], rank[P];
 #pragma unroll
         for (int k = 0; k < P; ++k) {
             v[k] = nxt[k];
             const uint64_t i = base + C + tid + (uint64_t)k * WG;
-            nxt[k] = r.sorted[i < s1 ? i : 0];  // next chunk in flight during this one
+            nxt[k] = sorted[i < s1 ? i : 0];  // next chunk in flight during this one
         }
 #pragma unroll
         for (int k = 0; k < P; ++k) {
-            cl[k] = (uint32_t)((v[k] >> 40) - cell0);
-            rank[k] = (tid + k * WG < cnt) ? atomicAdd(&s_hist[cl[k]], 1u) : 0u;
+            const bool in = tid + k * WG < cnt;
+            uint64_t full;
+            if constexpr (COMPACT) {
+                full = ((uint64_t)(v[k] >> kCompactDurBits) << 40) | (v[k] & kCompactDurMask);  // cell_local, d
+                if (in && (v[k] & kCompactEscape)) {
+                    const uint64_t x = r.links[v[k] & ~kCompactEscape];
+                    full = x - (cell0 << 40);
+                }
+            } else {
+                full = v[k] - (cell0 << 40);
+            }
+            cl[k] = in ? (uint32_t)(full >> 40) : 0u;
+            d[k] = full & (kMaxDuration - 1);
+            rank[k] = in ? atomicAdd(&s_hist[cl[k]], 1u) : 0u;
         }
         __syncthreads();
         const uint32_t h = s_hist[tid];
@@ -415,7 +475,7 @@ __global__ __launch_bounds__(1 << CB_SHIFT) void k_bucket_reduce(ReduceArgs r, u
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < P; ++k)
-            if (tid + k * WG < cnt) s_d[s_off[cl[k]] + rank[k]] = v[k] & (kMaxDuration - 1);
+            if (tid + k * WG < cnt) s_d[s_off[cl[k]] + rank[k]] = d[k];
         __syncthreads();
         RunSums run;
         run.clear();
@@ -458,9 +518,15 @@ __global__ __launch_bounds__(1 << CB_SHIFT) void k_bucket_reduce(ReduceArgs r, u
 // least one link, so with < 2^32 links since reset those limbs stay < 2^64; the top limb receives
 // floor(S / 2^(32 top)) <= sum over the flush's links of (floor(d^k / 2^(32 top)) + 1) <= 2^32 per
 // link (tests/test_reduce_bounds.py checks these bounds against the limb layout at d = 2^40 - 1).
-template <int CB_SHIFT, int WG>
+// COMPACT: `sorted` holds compact words (zk_internal.h): a short word is the six-atomic link as it
+// stands, an escape fetches the full link from its slot in the K1 lists.
+template <int CB_SHIFT, int WG, bool COMPACT>
 __global__ __launch_bounds__(WG) void k_bucket_lds_reduce_wide(ReduceArgs r, uint32_t splits) {
     constexpr int CB = 1 << CB_SHIFT;
+    using W = typename std::conditional<COMPACT, uint32_t, uint64_t>::type;
+    constexpr int KU = kK3U;
+    constexpr W kPad = ~(W)0;  // (an 8-byte link is never all ones: cell < 2^20 here)
+    const W* const sorted = static_cast<const W*>(r.sorted);
     static_assert(CB == WG, "one thread per cell at the flush");
     constexpr int ROWS = 12;  // 0 m0, 1 S1, 2-3 S2, 4-6 S3, 7-10 S4, 11 packed m0|S1
     constexpr int RS = CB + 1;
@@ -480,26 +546,38 @@ __global__ __launch_bounds__(WG) void k_bucket_lds_reduce_wide(ReduceArgs r, uin
     for (uint64_t s0 = p0; s0 < p1 || s0 == p0; s0 += kSub) {
         const uint64_t s1 = (s0 + kSub < p1) ? s0 + kSub : p1;
         for (int x = tid; x < ROWS * RS; x += WG) s_t[x] = 0ull;
-        uint64_t nxt[kK3U];
+        W nxt[KU];
 #pragma unroll
-        for (int k = 0; k < kK3U; ++k) {
+        for (int k = 0; k < KU; ++k) {
             const uint64_t i = s0 + tid + (uint64_t)k * WG;
-            nxt[k] = i < s1 ? r.sorted[i] : ~0ull;
+            nxt[k] = i < s1 ? sorted[i] : kPad;
         }
         __syncthreads();
-        for (uint64_t base = s0; base < s1; base += (uint64_t)WG * kK3U) {
-            uint64_t v[kK3U];
+        for (uint64_t base = s0; base < s1; base += (uint64_t)WG * KU) {
+            W v[KU];
 #pragma unroll
-            for (int k = 0; k < kK3U; ++k) {
+            for (int k = 0; k < KU; ++k) {
                 v[k] = nxt[k];
-                const uint64_t i = base + (uint64_t)WG * kK3U + tid + (uint64_t)k * WG;
-                nxt[k] = i < s1 ? r.sorted[i] : ~0ull;
+                const uint64_t i = base + (uint64_t)WG * KU + tid + (uint64_t)k * WG;
+                nxt[k] = i < s1 ? sorted[i] : kPad;
             }
 #pragma unroll
-            for (int k = 0; k < kK3U; ++k) {
-                if (v[k] == ~0ull) continue;
-                const uint32_t c = (uint32_t)((v[k] >> 40) - cell0);
-                const uint64_t d = v[k] & (kMaxDuration - 1);
+            for (int k = 0; k < KU; ++k) {
+                if (v[k] == kPad) continue;
+                uint32_t c;
+                uint64_t d;
+                if constexpr (COMPACT) {
+                    c = v[k] >> kCompactDurBits;
+                    d = v[k] & kCompactDurMask;
+                    if (v[k] & kCompactEscape) {
+                        const uint64_t x = r.links[v[k] & ~kCompactEscape];
+                        c = (uint32_t)((x >> 40) - cell0);
+                        d = x & (kMaxDuration - 1);
+                    }
+                } else {
+                    c = (uint32_t)((v[k] >> 40) - cell0);
+                    d = v[k] & (kMaxDuration - 1);
+                }
                 unsigned long long* t = s_t + c;
 #define ZK_K3W_ADD(q, x)                                            \
     do {                                                            \
@@ -625,8 +703,31 @@ void bucket_geometry(uint32_t S, uint32_t* nb, uint32_t* cb_shift) {
 uint64_t reduce_scatter_dyn_lds(uint32_t S) {
     uint32_t nb = 0, sh = 0;
     bucket_geometry(S, &nb, &sh);
-    return (uint64_t)nb * kScatterLine * 8;  // K2's per-bucket line carry
+    return (uint64_t)nb * kScatterLineBytes;  // K2's per-bucket line carry
 }
+
+// ~kScatterGrid K2 workgroups: a K1 grid larger than that is walked LPW lists per workgroup
+uint32_t scatter_lists_per_wg(uint32_t lists) {
+    const uint32_t lpw = (lists + kScatterGrid - 1) / kScatterGrid;
+    return lpw > (uint32_t)kScatterMaxLPW ? (uint32_t)kScatterMaxLPW : lpw;
+}
+
+bool reduce_compact(uint32_t lists, uint64_t stride) { return (uint64_t)lists * stride < kCompactSlotLimit; }
+
+namespace {
+template <bool COMPACT>
+hipError_t launch_scatter_reduce(const ReduceArgs& r, uint32_t k2_grid, uint32_t lpw, uint32_t splits, hipStream_t s) {
+    const hipError_t e = launch_checked("k_link_scatter", k_link_scatter<kK2U, kK2WG, COMPACT>, dim3(k2_grid), dim3(kK2WG),
+                                        (size_t)r.nb * kScatterLineBytes, s, r, lpw);
+    if (e != hipSuccess) return e;
+    // buckets of 512 cells (S <= 724): the LDS-atomic K3; of 1024 cells: the counting-sort K3
+    if (r.cb_shift == 9)
+        return launch_checked("k_bucket_lds_reduce_wide<9>", k_bucket_lds_reduce_wide<9, 512, COMPACT>,
+                              dim3(r.nb * splits), dim3(512), 0, s, r, splits);
+    return launch_checked("k_bucket_reduce<10>", k_bucket_reduce<10, 4, COMPACT>, dim3(r.nb * splits), dim3(1024), 0, s, r,
+                          splits);
+}
+}  // namespace
 
 hipError_t launch_partitioned_reduce(const ReduceArgs& r, hipStream_t s) {
     if (!r.nb || !r.lists) return hipSuccess;
@@ -635,19 +736,11 @@ hipError_t launch_partitioned_reduce(const ReduceArgs& r, hipStream_t s) {
     if (e != hipSuccess) return e;
     e = launch_checked("k_bucket_base", k_bucket_base, dim3(1), dim3(1024), 0, s, r.bucket_base, r.nb);
     if (e != hipSuccess) return e;
-    // ~kScatterGrid K2 workgroups: a K1 grid larger than that is walked LPW lists per workgroup
-    uint32_t lpw = (r.lists + kScatterGrid - 1) / kScatterGrid;
-    if (lpw > (uint32_t)kScatterMaxLPW) lpw = kScatterMaxLPW;
+    const uint32_t lpw = scatter_lists_per_wg(r.lists);
     const uint32_t k2_grid = (r.lists + lpw - 1) / lpw;
-    e = launch_checked("k_link_scatter", k_link_scatter<kK2U, kK2WG>, dim3(k2_grid), dim3(kK2WG),
-                       (size_t)r.nb * kScatterLine * 8, s, r, lpw);
-    if (e != hipSuccess) return e;
     const uint32_t splits = r.nb >= 256 ? 1u : (512u + r.nb - 1) / r.nb;
-    // buckets of 512 cells (S <= 724): the LDS-atomic K3; of 1024 cells: the counting-sort K3
-    if (r.cb_shift == 9)
-        return launch_checked("k_bucket_lds_reduce_wide<9>", k_bucket_lds_reduce_wide<9, 512>, dim3(r.nb * splits),
-                              dim3(512), 0, s, r, splits);
-    return launch_checked("k_bucket_reduce<10>", k_bucket_reduce<10, 4>, dim3(r.nb * splits), dim3(1024), 0, s, r, splits);
+    return r.compact ? launch_scatter_reduce<true>(r, k2_grid, lpw, splits, s)
+                     : launch_scatter_reduce<false>(r, k2_grid, lpw, splits, s);
 }
 
 hipError_t launch_link_reduce(const uint64_t* links, const uint32_t* counts, uint64_t stride, uint64_t tiles,
