@@ -114,8 +114,25 @@ zk_status zk_ingest_string(const zk_ingest* ing, uint64_t hash, char* buf, uint6
  * above; the indexer items through zk_ingest_dev_spans_items). Its service dictionary lives on the device: a batch's new names get ids
  * in the order of their hash-table slots (not in order of first appearance; names whose hashes
  * collide in the table may swap ids between runs), names are compared byte for byte. At most `max_services` distinct names
- * (ZK_ERR_SERVICE_RANGE past that). Thrift nesting deeper than 16 levels inside skipped fields is
- * treated as undecodable. Results are synchronous with respect to the host (the call waits). */
+ * (ZK_ERR_SERVICE_RANGE past that). Results are synchronous with respect to the host (the call waits).
+ *
+ * Wire forms (both decoders, every path and build of the device decoder; tests/thriftref.py restates
+ * them). A known field is a (field id, wire type) pair; a known id with another type is skipped by
+ * its wire type like an unknown one. The last occurrence of a scalar field wins; parent_id stays set
+ * once seen. Every field-6 / field-8 list of structs is appended to what earlier such lists gave
+ * (Scrooge would keep the last list only); one with another element type is skipped element by
+ * element. Within an annotation every host struct marks the host present, and a later one keeps the
+ * earlier service name unless it carries its own; within an endpoint the last service_name wins, and
+ * an absent or empty one is "Unknown service name". An annotation without a value field is valid
+ * (its item string is ""), one without a timestamp has timestamp 0. Bytes after the Span's STOP are
+ * ignored. A negative string length or container count, a value of an unknown type code (a container
+ * of zero elements reads none) and a short read make the fragment undecodable. Validation applies to
+ * decodable bytes only, in this order: no name; then per annotation in order, timestamp <= 0, then a
+ * present, empty value.
+ * Nesting inside one skipped value is the one point where the decoders differ: the device decoder
+ * allows at most 16 containers (struct, map, set, list) open at once and treats a 17th as undecodable;
+ * the host decoder allows a value inside at most 64 containers (so 64 containers around a scalar, and
+ * a 65th only if it is empty) and treats anything deeper as undecodable. */
 typedef struct zk_ingest_dev zk_ingest_dev;
 zk_status   zk_ingest_dev_create(int32_t device, void* stream, uint32_t max_services, zk_ingest_dev** out);
 zk_status   zk_ingest_dev_destroy(zk_ingest_dev* ing);

@@ -284,8 +284,8 @@ bool read_span(Rd& r, SpanT* s) {
             const uint8_t et = r.u8();
             const int32_t n = r.i32();
             if (!r.ok || n < 0 || et != T_STRUCT) {
-                if (r.ok && n >= 0) {  // a list of something else: skip it
-                    for (int32_t k = 0; r.ok && k < n; ++k) r.skip(et);
+                if (r.ok && n >= 0) {  // a list of something else: skip it (its elements sit inside the list)
+                    for (int32_t k = 0; r.ok && k < n; ++k) r.skip(et, 1);
                     continue;
                 }
                 return false;

@@ -206,11 +206,15 @@ struct DRdT {
         p += l;
         return true;
     }
-    // skip one value of type t; nested containers/structs iteratively up to a fixed depth
-    __device__ void skip(uint8_t t) {
+    // skip one value of type t; nested containers/structs iteratively up to a fixed depth: at most
+    // kSkipDepth containers open at once inside one skipped value (zkingest.h "Wire forms"). open: the
+    // containers of that value which the caller has opened itself (it walks a skipped list's or
+    // struct's elements inline and comes here for what they hold).
+    static constexpr int kSkipDepth = 16;
+    __device__ void skip(uint8_t t, int open = 0) {
         // explicit stack: (type, remaining) for containers; structs use remaining = -1
-        uint8_t st_t[16], st_k[16], st_v[16];
-        int32_t st_n[16];
+        uint8_t st_t[kSkipDepth], st_k[kSkipDepth], st_v[kSkipDepth];
+        int32_t st_n[kSkipDepth];
         int sp = 0;
         uint8_t cur = t;
         for (;;) {
@@ -232,7 +236,7 @@ struct DRdT {
                 case T_MAP:
                 case T_SET:
                 case T_LIST: {
-                    if (sp == 16) {
+                    if (sp + open == kSkipDepth) {
                         ok = false;
                         return;
                     }
@@ -291,14 +295,15 @@ using DRd = DRdT<const uint8_t*>;
 // The generic skip out of line (nested containers are rare in stored spans): keeps its stack and
 // switch out of the decoders' register budget. DRd travels by value, so nothing goes to scratch.
 template <class P>
-__device__ __noinline__ DRdT<P> skip_call(DRdT<P> r, uint8_t t) {
-    r.skip(t);
+__device__ __noinline__ DRdT<P> skip_call(DRdT<P> r, uint8_t t, int open) {
+    r.skip(t, open);
     return r;
 }
 
 // skip one value: fixed-width fields and strings inline, anything else through skip_call
+// (open: as DRdT::skip)
 template <class P>
-__device__ __forceinline__ void skip_flat(DRdT<P>& r, uint8_t t) {
+__device__ __forceinline__ void skip_flat(DRdT<P>& r, uint8_t t, int open = 0) {
     uint32_t w = 0;
     switch (t) {
         case T_BOOL:
@@ -316,25 +321,31 @@ __device__ __forceinline__ void skip_flat(DRdT<P>& r, uint8_t t) {
             r.p += l;
             return;
         }
-        default: r = skip_call(r, t); return;
+        default: r = skip_call(r, t, open); return;
     }
     if (r.need(w)) r.p += w;
 }
 
-// skip a struct whose fields are flat or flat structs (BinaryAnnotation with its Endpoint host)
+// skip a struct whose fields are flat or flat structs (BinaryAnnotation with its Endpoint host),
+// an element of a list of structs. host_fid: 3 / 4 when the list is field 6 / 8, so the element
+// (an Annotation / BinaryAnnotation) and its host are known structs and each of their unknown fields
+// is a skipped value of its own; 0 when the whole list is one skipped value, and the list, this
+// struct and a struct inside it are its open containers.
 template <class P>
-__device__ __forceinline__ void skip_struct2(DRdT<P>& r) {
+__device__ __forceinline__ void skip_struct2(DRdT<P>& r, int host_fid) {
+    const int open = host_fid ? 0 : 2;
     for (;;) {
         uint8_t t;
         int16_t fid;
         if (!r.field(&t, &fid)) return;
         if (t != T_STRUCT) {
-            skip_flat(r, t);
+            skip_flat(r, t, open);
             continue;
         }
+        const int inner = (host_fid && fid == host_fid) ? 0 : open + 1;
         uint8_t u;
         int16_t uid;
-        while (r.field(&u, &uid)) skip_flat(r, u);
+        while (r.field(&u, &uid)) skip_flat(r, u, inner);
         if (!r.ok) return;
     }
 }
@@ -647,8 +658,8 @@ __device__ __forceinline__ int parse_record(const IngArgs& a, uint64_t i, P src,
                 r.ok = false;
                 break;
             }
-            if (et != T_STRUCT) {
-                for (int32_t q = 0; r.ok && q < cntl; ++q) skip_flat(r, et);
+            if (et != T_STRUCT) {  // skipped by its wire type: the list is the value's first container
+                for (int32_t q = 0; r.ok && q < cntl; ++q) skip_flat(r, et, 1);
                 continue;
             }
             for (int32_t q = 0; r.ok && q < cntl; ++q) {
@@ -703,9 +714,9 @@ __device__ __forceinline__ int parse_record(const IngArgs& a, uint64_t i, P src,
                 break;
             }
             if (et == T_STRUCT)
-                for (int32_t q = 0; r.ok && q < cntl; ++q) skip_struct2(r);
+                for (int32_t q = 0; r.ok && q < cntl; ++q) skip_struct2(r, fid == 8 ? 4 : 0);
             else
-                for (int32_t q = 0; r.ok && q < cntl; ++q) skip_flat(r, et);
+                for (int32_t q = 0; r.ok && q < cntl; ++q) skip_flat(r, et, 1);
         } else {
             skip_flat(r, t);
         }
@@ -1504,14 +1515,16 @@ struct GItemIter {
             uint8_t t;
             int16_t fid;
             if (!r.field(&t, &fid)) return false;
-            if (fid == list_id && t == T_LIST) {
+            if ((fid == 6 || fid == 8) && t == T_LIST) {
                 const uint8_t et = r.u8();
                 const int32_t c = r.i32();
                 if (!r.ok || c < 0) return false;
-                if (et == T_STRUCT)
+                if (et == T_STRUCT && fid == list_id)
                     left = c;
+                else if (et == T_STRUCT)  // the other list: known structs, as parse_record walks them
+                    for (int32_t q = 0; r.ok && q < c; ++q) skip_struct2(r, fid == 6 ? 3 : 4);
                 else
-                    for (int32_t q = 0; r.ok && q < c; ++q) skip_flat(r, et);
+                    for (int32_t q = 0; r.ok && q < c; ++q) skip_flat(r, et, 1);
             } else {
                 skip_flat(r, t);
             }
