@@ -7,6 +7,7 @@ from ._abi import ZkError, ZkLibraryError  # noqa: F401
 from .columns import BYTES_PER_RECORD, DeviceColumns, SpanColumns, tracegen_host, tracegen_params  # noqa: F401
 from .context import DepsContext, LinkTable  # noqa: F401
 from .realtime import LinkHistogram, LinkHistogramSnapshot  # noqa: F401
+from .durations import TraceDurationIndex, TraceIdDuration, merge_top  # noqa: F401
 from .windows import WindowedAggregateJob, WindowPartition  # noqa: F401
 from . import table  # noqa: F401
 
@@ -23,5 +24,8 @@ __all__ = [
     "LinkHistogramSnapshot",
     "WindowPartition",
     "WindowedAggregateJob",
+    "TraceDurationIndex",
+    "TraceIdDuration",
+    "merge_top",
     "BYTES_PER_RECORD",
 ]

@@ -253,6 +253,23 @@ class zk_win_counts(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k not in skip}
 
 
+ZK_TD_TABLE_SALT = 0xE7037ED1A0B428DB
+ZK_TD_MAX_TOP = 4096
+ZK_TD_TIMESTAMP_DESC = 0  # the ordinals of the query service's Order enum
+ZK_TD_TIMESTAMP_ASC = 1
+ZK_TD_DURATION_ASC = 2
+ZK_TD_DURATION_DESC = 3
+
+
+class zk_td_config(C.Structure):
+    _fields_ = [
+        ("device", C.c_int32),
+        ("timing", C.c_uint32),
+        ("stream", C.c_void_p),
+        ("reserved", C.c_uint32 * 8),
+    ]
+
+
 ZK_RT_WITH_DEPS = 0
 ZK_RT_ONLY = 1
 ZK_RL_ANY_RPC = 0xFFFFFFFF
@@ -471,6 +488,20 @@ _SIGNATURES = [
     ("zk_win_table_reserve", C.c_int, [_P, C.c_uint64]),
     ("zk_win_table_info", C.c_int, [_P, _U64P, _U64P, _U64P]),
     ("zk_win_table_lookup", C.c_int, [_P, _U64P, C.c_uint64, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8)]),
+    # include/zkduration.h: the trace duration index
+    ("zk_td_create", C.c_int, [C.POINTER(zk_td_config), C.POINTER(_P)]),
+    ("zk_td_destroy", C.c_int, [_P]),
+    ("zk_td_last_error", C.c_char_p, [_P]),
+    ("zk_td_observe", C.c_int, [_P, C.POINTER(zk_span_cols), C.c_uint32]),
+    ("zk_td_reset", C.c_int, [_P]),
+    ("zk_td_reserve", C.c_int, [_P, C.c_uint64]),
+    ("zk_td_info", C.c_int, [_P, _U64P, _U64P, _U64P]),
+    ("zk_td_lookup", C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                               C.POINTER(C.c_uint8)]),
+    ("zk_td_top", C.c_int, [_P, C.c_uint32, C.c_int64, C.c_int64, C.c_uint32, _U64P, C.POINTER(C.c_int64),
+                            C.POINTER(C.c_int64), _U32P, _U64P]),
+    ("zk_td_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zk_td_top_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
 ]
 
 SYMBOLS = [s[0] for s in _SIGNATURES]

@@ -788,14 +788,19 @@ class ZipkinAggregateJob:
     snapshot (link_histogram()) is stored with the record, so GpuAggregates.getLinkDurations(start, end)
     answers the same quantiles over any window of stored records.
 
+    durations (a durations.TraceDurationIndex): every batch is also observed into it, before it is
+    accumulated, so that after run() the index answers getTracesDuration and top() for the job's
+    traces. The job neither resets nor closes it; the default None leaves every path as it is.
+
     The device context is kept between runs (a scheduled job reuses its buffers); close() frees it.
     """
 
     def __init__(self, services: Dictionary, *, device: int = 0, strict: bool = True,
                  aggregates: Optional[Aggregates] = None, clock=now_us, order: str = "any", verify: bool = True,
-                 link_quantiles: Optional[Sequence[float]] = None):
+                 link_quantiles: Optional[Sequence[float]] = None, durations=None):
         if order not in ("rows", "any"):
             raise ValueError("order is 'rows' or 'any'")
+        self.durations = durations  # a durations.TraceDurationIndex, or None
         self.link_quantiles = None if link_quantiles is None else tuple(float(q) for q in link_quantiles)
         self._lh = None
         self._link_durations: List[LinkDuration] = []
@@ -844,6 +849,8 @@ class ZipkinAggregateJob:
         ctx = self._context(num_services or max(1, len(self.services)))
         rows = self.order == "rows"
         for b in batches:
+            if self.durations is not None:
+                self.durations.observe(b, sync=True)
             ctx.accumulate(b, clustered=rows, continues=rows, verify=self.verify)
         return ctx
 
