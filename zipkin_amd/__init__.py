@@ -8,6 +8,7 @@ from .columns import BYTES_PER_RECORD, DeviceColumns, SpanColumns, tracegen_host
 from .context import DepsContext, LinkTable  # noqa: F401
 from .realtime import LinkHistogram, LinkHistogramSnapshot  # noqa: F401
 from .durations import TraceDurationIndex, TraceIdDuration, merge_top  # noqa: F401
+from .nameindex import IndexedTraceId, TraceNameIndex, merge_trace_ids  # noqa: F401
 from .windows import WindowedAggregateJob, WindowPartition  # noqa: F401
 from . import table  # noqa: F401
 
@@ -27,5 +28,8 @@ __all__ = [
     "TraceDurationIndex",
     "TraceIdDuration",
     "merge_top",
+    "TraceNameIndex",
+    "IndexedTraceId",
+    "merge_trace_ids",
     "BYTES_PER_RECORD",
 ]

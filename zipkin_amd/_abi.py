@@ -270,6 +270,24 @@ class zk_td_config(C.Structure):
     ]
 
 
+ZK_IX_NO_CLIENT = 0xFFFFFFFF
+ZK_IX_ANY_NAME = 0xFFFFFFFF
+ZK_IX_MAX_LIMIT = 4096
+ZK_IX_MAX_SEGMENTS = 64
+ZK_IX_MAX_SERVICES = 4096
+
+
+class zk_ix_config(C.Structure):
+    _fields_ = [
+        ("device", C.c_int32),
+        ("num_services", C.c_uint32),
+        ("client_service", C.c_uint32),
+        ("timing", C.c_uint32),
+        ("stream", C.c_void_p),
+        ("reserved", C.c_uint32 * 8),
+    ]
+
+
 ZK_RT_WITH_DEPS = 0
 ZK_RT_ONLY = 1
 ZK_RL_ANY_RPC = 0xFFFFFFFF
@@ -502,6 +520,20 @@ _SIGNATURES = [
                             C.POINTER(C.c_int64), _U32P, _U64P]),
     ("zk_td_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_td_top_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    # include/zkindex.h: the trace-id index by service and span name
+    ("zk_ix_create", C.c_int, [C.POINTER(zk_ix_config), C.POINTER(_P)]),
+    ("zk_ix_destroy", C.c_int, [_P]),
+    ("zk_ix_last_error", C.c_char_p, [_P]),
+    ("zk_ix_observe", C.c_int, [_P, C.POINTER(zk_span_cols), C.c_uint32]),
+    ("zk_ix_reset", C.c_int, [_P]),
+    ("zk_ix_compact", C.c_int, [_P]),
+    ("zk_ix_info", C.c_int, [_P, _U64P, _U64P, _U64P]),
+    ("zk_ix_service_counts", C.c_int, [_P, _U64P]),
+    ("zk_ix_trace_ids", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int64, C.c_uint32, _U64P, C.POINTER(C.c_int64), _U32P,
+                                  _U64P]),
+    ("zk_ix_span_names", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint16), C.c_uint32, _U32P]),
+    ("zk_ix_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zk_ix_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
 ]
 
 SYMBOLS = [s[0] for s in _SIGNATURES]
