@@ -64,6 +64,8 @@ extern "C" {
                                       span-name dictionary (at most max_span_names names); one made by
                                       zk_ingest_dev_create returns ZK_ERR_UNSUPPORTED for this flag. Its
                                       ids are NOT the host decoder's: see zk_ingest_dev_create_names. */
+#define ZK_INGEST_NO_CLIENT_RULE 8u /* zk_ingest_spans_indexed: emit the entries of a client-side span of the
+                                      service called "client" too (shouldIndex off) */
 /* Both decoders (host zk_ingest_spans, device zk_ingest_dev_spans) reject a Snappy fragment whose
  * header announces more than ZK_INGEST_MAX_FRAGMENT bytes, or more than the format can expand its
  * payload to (a 3-byte copy emits at most 64 bytes: < ZK_SNAPPY_MAX_EXPANSION x), before any
@@ -96,6 +98,41 @@ const char* zk_ingest_last_error(const zk_ingest* ing);
 zk_status zk_ingest_spans(zk_ingest* ing, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
                           uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
                           zk_ingest_items* items);
+
+/* caller buffers for the entries of the annotation index (zkannindex.h): five parallel columns */
+typedef struct zk_ingest_index_items {
+    uint32_t* service;   /* the item's own host: its service id */
+    uint64_t* key;       /* zk_hash_string of a time annotation's value / a binary annotation's key */
+    uint64_t* val;       /* 0 for a time annotation; zk_index_value_hash(value) for a binary annotation */
+    int64_t*  ts;        /* the annotation's own timestamp / the span's last timestamp */
+    uint64_t* trace_id;
+    uint64_t  cap;       /* entries the arrays hold */
+    uint64_t  n;         /* out (decoder) / in (zk_ax_observe): entries */
+} zk_ingest_index_items;
+
+/* zk_ingest_spans (records, rejection and dictionaries as that call's, for the same flags; like its items,
+ * the entries' hosts enter the service dictionary: ids in order of first appearance, a record's own
+ * service before its entries' hosts) that also writes the span indexer's annotation entries
+ * (CassieSpanStore.scala:214-244) to the HOST columns of `ix`. A span gives entries when it is accepted, has at least one annotation and passes shouldIndex
+ * (SpanStore.scala:67-68, evaluated exactly: its entries are dropped when some annotation's value is
+ * "cs" or "cr" AND some annotation's host service name, ASCII-lowercased, is "client";
+ * ZK_INGEST_NO_CLIENT_RULE switches that off):
+ *   - time entries: the annotations whose value is not cs/cr/sr/ss, grouped by value; each group's
+ *     minimum by Annotation.compare (the difference of the timestamps truncated to 32 bits; the first of
+ *     equals), if it has a host: (host service, hash(value), 0, its own timestamp, traceId);
+ *   - binary entries: every binary annotation with a host: (host service, hash(key),
+ *     zk_index_value_hash(value), the span's last timestamp, traceId). An absent value hashes as "".
+ * Entries are in record order; within a record the time entries come first, by first occurrence of
+ * their value, then the binary entries in order; the same for any thread count. `service` is the
+ * dictionary id of the item's own host ("Unknown service name" when absent or empty).
+ * ix->cap too small: ZK_ERR_CAPACITY; the records and the first cap entries are written and ix->n = cap.
+ * ix and its five columns must not be NULL (ZK_ERR_INVALID_ARG). */
+zk_status zk_ingest_spans_indexed(zk_ingest* ing, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
+                                  uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
+                                  zk_ingest_index_items* ix);
+/* the value hash of the annotation index: zk_hash_string(s, len) | 1, so it is never 0 (0 asks for any
+   value, and marks a time-annotation entry) */
+uint64_t  zk_index_value_hash(const char* s, uint64_t len);
 
 /* the service dictionary */
 zk_status zk_ingest_num_services(const zk_ingest* ing, uint32_t* n);

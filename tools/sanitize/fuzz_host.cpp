@@ -7,7 +7,8 @@
 // stored fragments (u32 little-endian length, then the bytes), written by tests/test_sanitize.py from
 // the thrift encoder. Every fragment is decoded as is, Snappy-compressed by the corpus writer's
 // choice, and under deterministic mutations (bit flips, truncation, splices, hostile Snappy headers),
-// through both codecs, strict and lenient, with the indexer items on.
+// through both codecs, strict and lenient, with the indexer items on, and once more through
+// zk_ingest_spans_indexed with a short entry buffer.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -55,6 +56,17 @@ uint64_t decode(zk_ingest* g, const Batch& b, uint32_t codec, uint32_t flags) {
     const uint8_t* p = b.buf.empty() ? (const uint8_t*)"" : b.buf.data();
     zk_ingest_spans(g, p, b.off.data(), n, codec, flags, &out, &nout, &nrej, &it);
     if (nout > n) abort();
+    // the same batch through the annotation index's item source (zk_ingest_spans_indexed), with room
+    // for fewer entries than a batch of annotated spans makes, with and without the client rule
+    const uint64_t icap = n + 2;
+    std::vector<uint32_t> is(icap);
+    std::vector<uint64_t> ik(icap), iv(icap), itid(icap);
+    std::vector<int64_t> its(icap);
+    zk_ingest_index_items ix{is.data(), ik.data(), iv.data(), its.data(), itid.data(), icap, 0};
+    uint64_t nout2 = 0, nrej2 = 0;
+    zk_ingest_spans_indexed(g, p, b.off.data(), n, codec, flags | ((n & 1) ? ZK_INGEST_NO_CLIENT_RULE : 0u), &out, &nout2, &nrej2,
+                            &ix);
+    if (nout2 > n || ix.n > icap) abort();
     return nout;
 }
 

@@ -9,6 +9,7 @@ from .context import DepsContext, LinkTable  # noqa: F401
 from .realtime import LinkHistogram, LinkHistogramSnapshot  # noqa: F401
 from .durations import TraceDurationIndex, TraceIdDuration, merge_top  # noqa: F401
 from .nameindex import IndexedTraceId, TraceNameIndex, merge_trace_ids  # noqa: F401
+from .annindex import AnnotationItems, DeviceAnnotationItems, TraceAnnotationIndex, get_trace_ids, trace_ids_intersect  # noqa: F401
 from .windows import WindowedAggregateJob, WindowPartition  # noqa: F401
 from . import table  # noqa: F401
 
@@ -31,5 +32,10 @@ __all__ = [
     "TraceNameIndex",
     "IndexedTraceId",
     "merge_trace_ids",
+    "TraceAnnotationIndex",
+    "AnnotationItems",
+    "DeviceAnnotationItems",
+    "get_trace_ids",
+    "trace_ids_intersect",
     "BYTES_PER_RECORD",
 ]

@@ -288,6 +288,22 @@ class zk_ix_config(C.Structure):
     ]
 
 
+ZK_AX_ANY_VALUE = 0
+ZK_AX_MAX_LIMIT = 4096
+ZK_AX_MAX_SEGMENTS = 64
+ZK_AX_MAX_SERVICES = 4096
+
+
+class zk_ax_config(C.Structure):
+    _fields_ = [
+        ("device", C.c_int32),
+        ("num_services", C.c_uint32),
+        ("timing", C.c_uint32),
+        ("stream", C.c_void_p),
+        ("reserved", C.c_uint32 * 8),
+    ]
+
+
 ZK_RT_WITH_DEPS = 0
 ZK_RT_ONLY = 1
 ZK_RL_ANY_RPC = 0xFFFFFFFF
@@ -306,11 +322,24 @@ class zk_ingest_items(C.Structure):
     ]
 
 
+class zk_ingest_index_items(C.Structure):
+    _fields_ = [
+        ("service", C.c_void_p),
+        ("key", C.c_void_p),
+        ("val", C.c_void_p),
+        ("ts", C.c_void_p),
+        ("trace_id", C.c_void_p),
+        ("cap", C.c_uint64),
+        ("n", C.c_uint64),
+    ]
+
+
 ZK_CODEC_THRIFT = 0
 ZK_CODEC_SNAPPY_THRIFT = 1
 ZK_INGEST_STRICT = 1
 ZK_INGEST_ONE_THREAD = 2
 ZK_INGEST_SPAN_NAMES = 4
+ZK_INGEST_NO_CLIENT_RULE = 8
 
 
 class zk_moments(C.Structure):
@@ -438,6 +467,13 @@ _SIGNATURES = [
         [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(zk_span_cols), _U64P, _U64P,
          C.POINTER(zk_ingest_items)],
     ),
+    (
+        "zk_ingest_spans_indexed",
+        C.c_int,
+        [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(zk_span_cols), _U64P, _U64P,
+         C.POINTER(zk_ingest_index_items)],
+    ),
+    ("zk_index_value_hash", C.c_uint64, [C.c_char_p, C.c_uint64]),
     ("zk_ingest_num_services", C.c_int, [_P, _U32P]),
     ("zk_ingest_service_id", C.c_int, [_P, C.c_char_p, C.c_uint64, _U32P]),
     ("zk_ingest_service_name", C.c_int, [_P, C.c_uint32, C.c_char_p, C.c_uint64, _U64P]),
@@ -534,6 +570,19 @@ _SIGNATURES = [
     ("zk_ix_span_names", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint16), C.c_uint32, _U32P]),
     ("zk_ix_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_ix_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    # include/zkannindex.h: the trace-id index by annotation
+    ("zk_ax_create", C.c_int, [C.POINTER(zk_ax_config), C.POINTER(_P)]),
+    ("zk_ax_destroy", C.c_int, [_P]),
+    ("zk_ax_last_error", C.c_char_p, [_P]),
+    ("zk_ax_observe", C.c_int, [_P, C.POINTER(zk_ingest_index_items), C.c_uint32]),
+    ("zk_ax_reset", C.c_int, [_P]),
+    ("zk_ax_compact", C.c_int, [_P]),
+    ("zk_ax_info", C.c_int, [_P, _U64P, _U64P, _U64P]),
+    ("zk_ax_service_counts", C.c_int, [_P, _U64P]),
+    ("zk_ax_trace_ids", C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int64, C.c_uint32, _U64P,
+                                  C.POINTER(C.c_int64), _U32P, _U64P]),
+    ("zk_ax_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zk_ax_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
 ]
 
 SYMBOLS = [s[0] for s in _SIGNATURES]

@@ -203,6 +203,8 @@ struct Ann {
 struct BinAnn {
     const char* key = nullptr;
     uint32_t key_len = 0;
+    const char* value = nullptr;  // (read for the annotation index only)
+    uint32_t value_len = 0;
     Host host;
 };
 struct SpanT {
@@ -258,6 +260,8 @@ void read_binary_annotation(Rd& r, BinAnn* b) {
         const int16_t id = r.i16();
         if (id == 1 && t == T_STRING)
             r.str(&b->key, &b->key_len);
+        else if (id == 2 && t == T_STRING)
+            r.str(&b->value, &b->value_len);
         else if (id == 4 && t == T_STRUCT)
             read_endpoint(r, &b->host);
         else
@@ -376,11 +380,19 @@ struct Decoded {
     int32_t svc_name;  // -1: no service
     uint32_t kv0, kv_n, ann0, ann_n;
     int32_t span_name;  // ZK_INGEST_SPAN_NAMES: index into DecodeRange::span_names, -1: no name (id 0)
+    uint32_t ix0 = 0, ix_n = 0;  // zk_ingest_spans_indexed: the record's entries in DecodeRange::ix
+};
+// an entry of the annotation index before its service id is known
+struct IxItem {
+    Item key;      // the host's name, the key string and its hash
+    uint64_t val;  // 0: a time annotation
+    int64_t ts;
 };
 struct DecodeRange {
     uint64_t lo = 0, hi = 0;
     std::vector<Decoded> recs;
     std::vector<Item> kv, ann;
+    std::vector<IxItem> ix;
     std::vector<std::string> names, strs;
     std::unordered_map<std::string, int32_t> name_ix;
     std::unordered_map<uint64_t, uint32_t> str_ix;
@@ -427,8 +439,17 @@ struct DecodeRange {
     }
 };
 
+// "client", whatever its case (Span.serviceNames lowercases; only ASCII letters can fold to these six)
+bool is_client_name(const Host& h) {
+    if (!h.svc || h.svc_len != 6) return false;
+    for (int k = 0; k < 6; ++k)
+        if ((h.svc[k] | 0x20) != "client"[k]) return false;
+    return true;
+}
+
+// want_ix: 0 no index entries, 1 with the shouldIndex rule, 2 without it
 void decode_range(const uint8_t* buf, const uint64_t* offsets, uint32_t codec, bool strict, bool want_kv,
-                  bool want_ann, bool want_names, DecodeRange* d) {
+                  bool want_ann, bool want_names, int want_ix, DecodeRange* d) {
     std::vector<uint8_t> scratch;
     SpanT s;
     std::vector<const Ann*> distinct;
@@ -490,8 +511,10 @@ void decode_range(const uint8_t* buf, const uint64_t* offsets, uint32_t codec, b
         uint32_t cnt[4] = {0, 0, 0, 0};  // cs, cr, sr, ss
         const Host* srv = nullptr;
         const Host* cli = nullptr;
+        bool client_host = false;  // some annotation's host is the service "client"
         for (size_t q = 0; q < s.anns.size(); ++q) {
             const Ann& a = s.anns[q];
+            if (want_ix == 1 && a.host.present && is_client_name(a.host)) client_host = true;
             if (q == 0 || a.ts < first) first = a.ts;
             if (q == 0 || a.ts > last) last = a.ts;
             if (is_core(a.value, a.value_len)) {
@@ -517,12 +540,15 @@ void decode_range(const uint8_t* buf, const uint64_t* offsets, uint32_t codec, b
                     s.anns.empty() ? 0 : first, s.anns.empty() ? 0 : last, f, svc,
                     (uint32_t)d->kv.size(), 0u, (uint32_t)d->ann.size(), 0u,
                     want_names ? d->span_name(s.name, s.name_len) : -1};
+        rec.ix0 = (uint32_t)d->ix.size();
         // ---- indexer items: only spans with a last annotation (CassieSpanStore.scala:214-218) ----
         if (!s.anns.empty()) {
             if (want_kv)
                 for (const BinAnn& b : s.banns)  // :235-241 one per binary annotation with a host
                     if (b.host.present) d->kv.push_back(d->item(b.host, b.key, b.key_len));
-            if (want_ann) {
+            // shouldIndex (SpanStore.scala:67-68): not (isClientSide && serviceNames contains "client")
+            const bool ix_on = want_ix && !(want_ix == 1 && (cnt[0] | cnt[1]) && client_host);
+            if (want_ann || ix_on) {
                 // :222-233 non-core annotations grouped by value; the group's min (Annotation.compare:
                 // (a.timestamp - b.timestamp).toInt, Annotation.scala:36-38; min keeps the first of
                 // equals) yields one item if it has a host
@@ -542,11 +568,20 @@ void decode_range(const uint8_t* buf, const uint64_t* offsets, uint32_t codec, b
                     if (!seen) distinct.push_back(&a);
                 }
                 for (const Ann* a : distinct)
-                    if (a->host.present) d->ann.push_back(d->item(a->host, a->value, a->value_len));
+                    if (a->host.present) {
+                        const Item it = d->item(a->host, a->value, a->value_len);
+                        if (want_ann) d->ann.push_back(it);
+                        if (ix_on) d->ix.push_back(IxItem{it, 0ull, a->ts});
+                    }
             }
+            if (ix_on)
+                for (const BinAnn& b : s.banns)  // :235-241 (key, Some(value)) and (key, None) as one entry
+                    if (b.host.present)
+                        d->ix.push_back(IxItem{d->item(b.host, b.key, b.key_len), zk_index_value_hash(b.value, b.value_len), last});
         }
         rec.kv_n = (uint32_t)d->kv.size() - rec.kv0;
         rec.ann_n = (uint32_t)d->ann.size() - rec.ann0;
+        rec.ix_n = (uint32_t)d->ix.size() - rec.ix0;
         d->recs.push_back(rec);
     }
 }
@@ -712,13 +747,17 @@ zk_status zk_ingest_destroy(zk_ingest* g) {
 
 const char* zk_ingest_last_error(const zk_ingest* g) { return g ? g->err.c_str() : "null decoder"; }
 
-zk_status zk_ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
-                          uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
-                          zk_ingest_items* items) {
+uint64_t zk_index_value_hash(const char* s, uint64_t len) { return zk_hash_string(s, len) | 1ull; }
+
+// zk_ingest_spans (ix == nullptr) and zk_ingest_spans_indexed (items == nullptr)
+static zk_status ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
+                              uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
+                              zk_ingest_items* items, zk_ingest_index_items* ix) {
     ZK_GUARD_BEGIN
     if (!g || !n_out || !n_rejected) return ZK_ERR_INVALID_ARG;
     *n_out = *n_rejected = 0;
     if (items) items->kv_n = items->ann_n = 0;
+    if (ix) ix->n = 0;
     if (n == 0) return ZK_OK;
     if (!buf || !offsets || !out || !out->trace_id || !out->span_id || !out->parent_id || !out->first_ts ||
         !out->last_ts || !out->service_id || !out->flags)
@@ -731,6 +770,7 @@ zk_status zk_ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* offs
     const bool want_kv = items && items->kv_service && items->kv_key;
     const bool want_ann = items && items->ann_service && items->ann_value;
     const bool want_names = (flags & ZK_INGEST_SPAN_NAMES) != 0;
+    const int want_ix = !ix ? 0 : (flags & ZK_INGEST_NO_CLIENT_RULE) ? 2 : 1;
     // Phase 1, in parallel over contiguous fragment ranges: decode and validate every fragment into
     // a thread-local list (names copied into the thread's own table). Phase 2, in input order on
     // this thread: assign service ids and span-name ids (in order of first appearance, exactly as a
@@ -745,7 +785,7 @@ zk_status zk_ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* offs
         d.lo = n * t / T;
         d.hi = n * (t + 1) / T;
         try {
-            decode_range(buf, offsets, codec, strict, want_kv, want_ann, want_names, &d);
+            decode_range(buf, offsets, codec, strict, want_kv, want_ann, want_names, want_ix, &d);
         } catch (...) {
             d.err_index = d.lo;
             d.err_status = ZK_ERR_CAPACITY;
@@ -818,6 +858,20 @@ zk_status zk_ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* offs
                 keep(it);
                 ++items->ann_n;
             }
+            for (uint32_t q = r.ix0; q < r.ix0 + r.ix_n; ++q) {
+                if (ix->n >= ix->cap) {
+                    item_overflow = true;
+                    continue;
+                }
+                const IxItem& it = d.ix[q];
+                ix->service[ix->n] = id_of(it.key.name);
+                ix->key[ix->n] = it.key.hash;
+                ix->val[ix->n] = it.val;
+                ix->ts[ix->n] = it.ts;
+                ix->trace_id[ix->n] = r.tid;
+                keep(it.key);
+                ++ix->n;
+            }
         }
         *n_rejected += d.rejected;
         if (d.err_index != UINT64_MAX) {  // the first error of the batch (ranges are in input order)
@@ -832,6 +886,19 @@ zk_status zk_ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* offs
     }
     return ZK_OK;
     ZK_GUARD_END
+}
+
+zk_status zk_ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
+                          uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
+                          zk_ingest_items* items) {
+    return ingest_spans(g, buf, offsets, n, codec, flags, out, n_out, n_rejected, items, nullptr);
+}
+
+zk_status zk_ingest_spans_indexed(zk_ingest* g, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
+                                  uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
+                                  zk_ingest_index_items* ix) {
+    if (!ix || !ix->service || !ix->key || !ix->val || !ix->ts || !ix->trace_id) return ZK_ERR_INVALID_ARG;
+    return ingest_spans(g, buf, offsets, n, codec, flags, out, n_out, n_rejected, nullptr, ix);
 }
 
 zk_status zk_ingest_num_services(const zk_ingest* g, uint32_t* n) {

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "zk_guard.h"
+#include "zk_hist.h"
 #include "zk_ix_select.h"
 #include "zk_launch.h"
 #include "zkindex.h"
@@ -45,7 +46,6 @@ constexpr uint32_t kIxHistGrid = 1024;         // k_ix_count, k_ix_hist: every w
 constexpr uint32_t kIxScatterPerWG = 16384;    // k_ix_scatter: records per workgroup at least (S atomics each)
 constexpr uint32_t kIxCap = ZK_IX_MAX_LIMIT;   // the most entries the select brings to the host
 constexpr uint64_t kIxMaxEntries = 0xFFFFFFFFull;
-constexpr int kPeel = 4;
 constexpr int kCntItems = 4;                   // the counting loops: records per thread and step
 constexpr uint32_t kCntTile = kIxWG * kCntItems;
 // the select's counters (those of zk_td.hip): matched, certain entries appended, then what a round
@@ -81,12 +81,6 @@ static_assert(sizeof(IxEntry) == 16 && sizeof(IxSlice) == 32, "entry and slice l
 static_assert(kSelWords * 8 <= kSelHistAt && kSelCertainAt % 16 == 0 && kSelSlicesAt % 8 == 0 && kSelNamesAt % 4 == 0,
               "the scratch block's layout");
 
-__device__ inline uint32_t lane_id() { return threadIdx.x & 63; }
-
-__device__ inline uint32_t rank_in(unsigned long long mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
 // the INDEXED predicate of zkindex.h
 __device__ inline bool ix_indexed(uint32_t f, uint32_t svc, uint32_t client) {
     if (!(f & ZK_F_HAS_ANNOTATIONS) || !(f & (ZK_F_SVC_CLIENT | ZK_F_SVC_SERVER))) return false;
@@ -97,46 +91,6 @@ __device__ inline bool ix_indexed(uint32_t f, uint32_t svc, uint32_t client) {
 uint32_t ix_grid(uint64_t items, uint32_t cap = kIxMaxGrid) {
     const uint64_t g = (items + kIxWG - 1) / kIxWG;
     return (uint32_t)(g < 1 ? 1 : g > cap ? cap : g);
-}
-
-// s_hist[bin] += 1 for every lane with todo. A batch of few services puts most of a wave into one bin
-// and LDS atomics on one address serialise: the wave first peels off, up to kPeel times, the lanes that
-// share the lowest active lane's bin and adds their number once; the rest add one each. Every lane of
-// the wave calls it.
-__device__ inline void hist_add(uint32_t* s_hist, bool todo, uint32_t bin) {
-    for (int r = 0; r < kPeel; ++r) {
-        const unsigned long long m = __ballot(todo);
-        if (!m) break;
-        const int lead = __ffsll((long long)m) - 1;
-        const uint32_t lb = __shfl(bin, lead);
-        const unsigned long long same = __ballot(todo && bin == lb);
-        if ((int)lane_id() == lead) atomicAdd(&s_hist[lb], (uint32_t)__popcll(same));
-        if (bin == lb) todo = false;
-    }
-    if (todo) atomicAdd(&s_hist[bin], 1u);
-}
-
-// the same with the old value back: the lane's own place among the adds to its bin (lanes without todo
-// get nothing meaningful)
-__device__ inline uint32_t hist_rank(uint32_t* s_hist, bool todo, uint32_t bin) {
-    uint32_t rank = 0;
-    for (int r = 0; r < kPeel; ++r) {
-        const unsigned long long m = __ballot(todo);
-        if (!m) break;
-        const int lead = __ffsll((long long)m) - 1;
-        const uint32_t lb = __shfl(bin, lead);
-        const bool mine = todo && bin == lb;
-        const unsigned long long same = __ballot(mine);
-        uint32_t base = 0;
-        if ((int)lane_id() == lead) base = atomicAdd(&s_hist[lb], (uint32_t)__popcll(same));
-        base = __shfl(base, lead);
-        if (mine) {
-            rank = base + rank_in(same);
-            todo = false;
-        }
-    }
-    if (todo) rank = atomicAdd(&s_hist[bin], 1u);
-    return rank;
 }
 
 // ---- observe -------------------------------------------------------------------------------------------

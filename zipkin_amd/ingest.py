@@ -19,6 +19,19 @@ def hash_string(s: str | bytes) -> int:
     return int(_abi.lib().zk_hash_string(b, len(b)))
 
 
+def _pack(blobs):
+    """(buf uint8[total], offsets uint64[n + 1], n) of a sequence of bytes objects or of the packed form."""
+    if isinstance(blobs, tuple) and len(blobs) == 2 and isinstance(blobs[0], np.ndarray):
+        buf = np.ascontiguousarray(blobs[0], dtype=np.uint8)
+        offsets = np.ascontiguousarray(blobs[1], dtype=np.uint64)
+        return (buf if len(buf) else np.zeros(1, np.uint8)), offsets, len(offsets) - 1
+    n = len(blobs)
+    offsets = np.zeros(n + 1, np.uint64)
+    if n:
+        offsets[1:] = np.cumsum([len(b) for b in blobs], dtype=np.uint64)
+    return np.frombuffer(b"".join(blobs) or b"\0", dtype=np.uint8), offsets, n
+
+
 class SpanDecoder:
     def __init__(self):
         self._L = _abi.lib()
@@ -86,6 +99,36 @@ class SpanDecoder:
         kv = (arrs[0][: it.kv_n].copy(), arrs[1][: it.kv_n].copy())
         ann = (arrs[2][: it.ann_n].copy(), arrs[3][: it.ann_n].copy())
         return cols, int(nrej.value), kv, ann
+
+    def decode_indexed(self, blobs, *, snappy: bool = True, strict: bool = True, client_rule: bool = True,
+                       span_names: bool = False, item_cap: int | None = None, one_thread: bool = False):
+        """decode() that also returns the annotation index's entries (zk_ingest_spans_indexed):
+        (SpanColumns, rejected, annindex.AnnotationItems). client_rule=False emits the entries of a
+        client-side span of the service "client" too (ZK_INGEST_NO_CLIENT_RULE). item_cap: the entries to
+        allow for (default 8 per fragment, at least 16); a batch with more raises ZK_ERR_CAPACITY, and
+        the exception's `items` then holds the first item_cap entries."""
+        from .annindex import AnnotationItems
+
+        buf, offsets, n = _pack(blobs)
+        cols = SpanColumns.empty(n)
+        nout, nrej = C.c_uint64(), C.c_uint64()
+        cap = int(item_cap) if item_cap is not None else max(16, 8 * n)
+        items = AnnotationItems.empty(cap)
+        it = items.abi(cap=cap, n=0)
+        codec = _abi.ZK_CODEC_SNAPPY_THRIFT if snappy else _abi.ZK_CODEC_THRIFT
+        flags = (_abi.ZK_INGEST_STRICT if strict else 0) | (_abi.ZK_INGEST_ONE_THREAD if one_thread else 0)
+        flags |= _abi.ZK_INGEST_SPAN_NAMES if span_names else 0
+        flags |= 0 if client_rule else _abi.ZK_INGEST_NO_CLIENT_RULE
+        ab = cols.abi()
+        st = self._L.zk_ingest_spans_indexed(self._h, buf.ctypes.data, offsets.ctypes.data, n, codec, flags,
+                                             C.byref(ab), C.byref(nout), C.byref(nrej), C.byref(it))
+        items = items.take(slice(0, int(it.n)))
+        if st == _abi.ZK_ERR_CAPACITY:
+            e = _abi.ZkError(st, self._L.zk_ingest_last_error(self._h).decode() or _abi.status_str(st))
+            e.items = items
+            raise e
+        self._check(st)
+        return cols.take(slice(0, nout.value)), int(nrej.value), items
 
     @property
     def num_services(self) -> int:
