@@ -62,6 +62,22 @@
  * (8 B) only where the key matched and a value was asked, and at tkey / tid (16 B) only where both
  * matched.
  *
+ * Expiry is zkindex.h's, on the entry's ts: zk_ax_expire(min_ts) removes every entry with ts < min_ts
+ * as signed values (an entry with ts == min_ts stays), by the entry's own timestamp, not by the
+ * wall-clock time it was written (the stated departure from Cassandra's column TTL). For a time
+ * annotation ts is the annotation's own timestamp, for a binary annotation the span's last annotation
+ * timestamp. After the call the handle is indistinguishable, through zk_ax_trace_ids (with matched),
+ * zk_ax_service_counts and the entry count of zk_ax_info, from a fresh handle that observed only the
+ * survivors; a service whose entries all expired has count 0. Equal entries go or stay together. A later
+ * observe of older data enters it again. INT64_MIN removes nothing, INT64_MAX keeps only the entries at
+ * exactly INT64_MAX. The segment rule is zkindex.h's: untouched segments are kept as they are, fully
+ * expired ones are freed, the survivors of all mixed ones go into one new segment; the segment count
+ * never grows; with nothing to remove nothing is rewritten or reallocated. A refused allocation is
+ * ZK_ERR_CAPACITY and leaves the handle exactly as it was. The consistency invariant of zkindex.h holds
+ * here too: an entry's ts is at most its span's last annotation timestamp, which is at most its trace's
+ * end, so with one cutoff on this handle and on the duration index every (trace_id, ts) still returned
+ * has its trace in the duration index.
+ *
  * Conventions are those of zkindex.h: every entry point returns zk_status; a handle is not thread-safe;
  * all device work of a handle is ordered on one HIP stream; nothing is allocated before the first
  * observe. Every call refuses a NULL handle or argument with ZK_ERR_INVALID_ARG before any device is
@@ -106,13 +122,18 @@ const char* zk_ax_last_error(const zk_ax* ax);
    waits for its staging copy. The call synchronises once, to read the per-service counts it sizes the
    segment by (a merge, see Layout, synchronises once more). The scatter is queued on the handle's
    stream behind that: DEVICE columns must stay as they are until the handle's next synchronising call
-   (zk_ax_info, zk_ax_trace_ids, zk_ax_compact, zk_ax_observe). n == 0 is ZK_OK; n >= 2^32 is
-   ZK_ERR_UNSUPPORTED. */
+   (zk_ax_info, zk_ax_trace_ids, zk_ax_compact, zk_ax_expire, zk_ax_observe). n == 0 is ZK_OK;
+   n >= 2^32 is ZK_ERR_UNSUPPORTED. */
 zk_status   zk_ax_observe(zk_ax* ax, const zk_ingest_index_items* items, uint32_t flags);
 /* Empty the index: every segment is freed. */
 zk_status   zk_ax_reset(zk_ax* ax);
 /* Merge all segments into one (see Layout). Fewer than two segments: nothing to do. Synchronises. */
 zk_status   zk_ax_compact(zk_ax* ax);
+/* Remove every entry with ts < min_ts (see Expiry). *removed = the entries removed; may be NULL. Two
+   passes: a count over every segment's tkey column (8 B per entry), one synchronisation to read the
+   survivors per (segment, service), then the rewrite of the mixed segments' survivors (tkey again, and
+   32 B read and 32 B written per survivor). An empty handle is ZK_OK with *removed = 0. Synchronises. */
+zk_status   zk_ax_expire(zk_ax* ax, int64_t min_ts, uint64_t* removed);
 /* entries in the index, segments, bytes of HBM the segments hold. Any of the three pointers may be
    NULL. Synchronises. */
 zk_status   zk_ax_info(zk_ax* ax, uint64_t* entries, uint64_t* segments, uint64_t* bytes);
@@ -136,6 +157,10 @@ zk_status   zk_ax_trace_ids(zk_ax* ax, uint32_t service, uint64_t key, uint64_t 
    counts' copy and, when the segment bound was met, the merge), the scatter. Needs zk_ax_config.timing;
    waits for the scatter. */
 zk_status   zk_ax_observe_ms(zk_ax* ax, double out[3]);
+/* Device time in ms of the last zk_ax_expire that ran its count: the count, the sizing step (the
+   counts' copy and the synchronisation), the rewrite (0 when no segment was mixed). Needs
+   zk_ax_config.timing. */
+zk_status   zk_ax_expire_ms(zk_ax* ax, double out[3]);
 /* Time in ms on the handle's stream of the last zk_ax_trace_ids that ran a pass, from its first pass
    to its last copy (the host's bin choices between the passes included). Needs zk_ax_config.timing. */
 zk_status   zk_ax_query_ms(zk_ax* ax, double* ms);

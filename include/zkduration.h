@@ -33,9 +33,35 @@
  *  - SIZING (the rule of zkwindow.h): before anything of a batch is inserted the call counts the batch's
  *    trace runs (maximal stretches of adjacent records with equal trace_id) and makes sure that
  *    slots >= 2 * (traces in the table + runs in the batch), rounded up to a power of two, at least
- *    1024. The load so never exceeds 1/2. The table only grows (the old content is rehashed into the
- *    new table); a refused allocation is ZK_ERR_CAPACITY and changes nothing.
+ *    1024. The load so never exceeds 1/2. An observe or a reserve only grows the table (the old content
+ *    is rehashed into the new table); a refused allocation is ZK_ERR_CAPACITY and changes nothing.
+ *    zk_td_expire is the ONE operation that may shrink it (see Expiry).
  *  - bytes = (slots + 1) * 24.
+ *
+ * Expiry (the reference's indexTtl: every index column Cassandra writes expires, CassieSpanStore.scala:48)
+ *  - zk_td_expire(min_end) removes every trace whose end < min_end as signed values; a trace with
+ *    end == min_end stays. `end` is used, not `start`, so that a trace still receiving fragments stays.
+ *    TraceId 0, which lives in the extra slot, follows the same rule. EXPIRY IS BY THE TRACE'S OWN END
+ *    TIME, NOT BY THE WALL-CLOCK TIME IT WAS WRITTEN: a stated departure from Cassandra's column TTL,
+ *    which counts from the write. Every answer so stays a function of the observed fragments and the
+ *    cutoffs applied, and stays exactly testable; for spans indexed near the time they end the two rules
+ *    agree.
+ *  - After the call the handle is indistinguishable, through zk_td_lookup, zk_td_top and the trace count
+ *    of zk_td_info, from a fresh handle whose table holds only the survivors, each with the start and
+ *    end it had. It is a one-time cut, not a filter on future input: a later observe of fragments of a
+ *    removed trace enters the trace again, with the times of those fragments alone.
+ *  - INT64_MIN removes nothing; INT64_MAX keeps only the traces whose end is exactly INT64_MAX.
+ *  - WHY A REBUILD: open addressing with linear probing has no delete in place. Emptying a slot cuts the
+ *    probe chain of every key that was displaced past it, and a lookup of such a key would end at the
+ *    hole. So the call counts the survivors (one pass over the table) and, ONLY WHEN SOMETHING EXPIRES,
+ *    inserts them into a fresh table sized by the SIZING rule applied to the survivors: slots = the
+ *    power of two at or above 2 * survivors, at least 1024. The old table is freed after the rebuild is
+ *    complete. The table may so shrink, and a zk_td_reserve hint does not survive the call. With
+ *    nothing to remove the table stays where and as it is: the same slots, the same bytes.
+ *  - A refused allocation is ZK_ERR_CAPACITY and leaves the handle exactly as it was.
+ *  - CONSISTENCY with zkindex.h and zkannindex.h: an indexed fragment is timed, and its entry's
+ *    ts <= last_ts <= the trace's end. With one cutoff c on the three handles, ts >= c implies
+ *    end >= c: every (trace_id, ts) the two trace-id indices still return has its trace here.
  *
  * Top
  *  - zk_td_top takes the traces whose start lies in [start_lo, start_hi], both ends inclusive, and
@@ -95,13 +121,18 @@ const char* zk_td_last_error(const zk_td* td);
    records). The call synchronises once, to read the run count it sizes the table by (see SIZING;
    growing synchronises once more). The inserts are queued on the handle's stream behind that: DEVICE
    columns must stay as they are until the handle's next synchronising call (zk_td_info, zk_td_lookup,
-   zk_td_top, zk_td_observe). n == 0 is ZK_OK. */
+   zk_td_top, zk_td_expire, zk_td_observe). n == 0 is ZK_OK. */
 zk_status   zk_td_observe(zk_td* td, const zk_span_cols* in, uint32_t flags);
 /* Empty the table; the allocation (slots) is kept. */
 zk_status   zk_td_reset(zk_td* td);
 /* Grow the table to at least 2 * traces slots now. A hint: it never shrinks the table and the content
-   is kept. */
+   is kept. It does not survive a zk_td_expire that removes something. */
 zk_status   zk_td_reserve(zk_td* td, uint64_t traces);
+/* Remove every trace whose end < min_end (see Expiry). *removed = the traces removed; may be NULL. One
+   pass over the table counts the survivors (16 B read per slot), one synchronisation reads the count,
+   and when something expires a fresh table is cleared (24 B per slot) and filled from the old one (24 B
+   read per slot, 24 B written per survivor). An empty handle is ZK_OK with *removed = 0. Synchronises. */
+zk_status   zk_td_expire(zk_td* td, int64_t min_end, uint64_t* removed);
 /* slots (0 before the first allocation), traceIds in the table, bytes of HBM the table holds. Any of the
    three pointers may be NULL. Synchronises. */
 zk_status   zk_td_info(zk_td* td, uint64_t* slots, uint64_t* traces, uint64_t* bytes);
@@ -125,6 +156,10 @@ zk_status   zk_td_top(zk_td* td, uint32_t order, int64_t start_lo, int64_t start
 /* Device time in ms of the last zk_td_observe: the run count, the sizing step (the count's copy and,
    when the table grew, the rehash), the inserts. Needs zk_td_config.timing; waits for the inserts. */
 zk_status   zk_td_observe_ms(zk_td* td, double out[3]);
+/* Device time in ms of the last zk_td_expire that ran its count: the count, the sizing step (the
+   count's copy and the synchronisation), the rebuild (0 when nothing expired). Needs
+   zk_td_config.timing. */
+zk_status   zk_td_expire_ms(zk_td* td, double out[3]);
 /* Time in ms on the handle's stream of the last zk_td_top that ran a pass, from its first pass to its
    last copy (the host's bin choices between the passes included). Needs zk_td_config.timing. */
 zk_status   zk_td_top_ms(zk_td* td, double* ms);

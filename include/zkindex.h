@@ -66,6 +66,32 @@
  *    When the candidates differ in no bit they are all the same pair, and the call takes as many of
  *    them as are still wanted and stops.
  *
+ * Expiry (the reference's indexTtl: every index column Cassandra writes expires, CassieSpanStore.scala:48)
+ *  - zk_ix_expire(min_ts) removes every entry with ts < min_ts as signed values; an entry with
+ *    ts == min_ts stays. EXPIRY IS BY THE ENTRY'S OWN TIMESTAMP, NOT BY THE WALL-CLOCK TIME IT WAS
+ *    WRITTEN: a stated departure from Cassandra's column TTL, which counts from the write. Every answer
+ *    so stays a function of the observed multiset and the cutoffs applied, and every query stays exactly
+ *    testable; for spans indexed near the time they end the two rules agree.
+ *  - After the call the handle is indistinguishable, through zk_ix_trace_ids (with matched),
+ *    zk_ix_span_names, zk_ix_service_counts and the entry count of zk_ix_info, from a fresh handle that
+ *    observed only the survivors. NAMES DISAPPEAR WITH THEIR ENTRIES: a span name whose entries all
+ *    expired is no longer a span name of its service, a service whose entries all expired has count 0
+ *    (Cassandra's behaviour too). Equal entries all have one ts: all copies go or all stay.
+ *  - It is a one-time cut, not a filter on future input: a later observe of older data enters it again.
+ *  - INT64_MIN removes nothing; INT64_MAX keeps only the entries at exactly INT64_MAX.
+ *  - Segments: a segment none of whose entries goes is kept UNTOUCHED (not read again, not copied); a
+ *    segment all of whose entries go is freed; the others are MIXED, and the survivors of all mixed
+ *    segments are written, grouped by service, into ONE new segment sized for them, after which the
+ *    mixed segments are freed. The segment count never grows. With nothing to remove nothing is
+ *    rewritten or reallocated: the same segments, the same bytes.
+ *  - A refused allocation is ZK_ERR_CAPACITY and leaves the handle exactly as it was: nothing is freed
+ *    before its replacement is complete.
+ *  - CONSISTENCY with zkduration.h and zkannindex.h: with one cutoff c applied to the three handles fed
+ *    from the same spans, every (trace_id, ts) this index still returns has its trace in the duration
+ *    index: an indexed fragment is timed, its ts = last_ts <= the trace's end, so ts >= c implies
+ *    end >= c, and zk_td_expire goes by end. Sorting trace ids by duration so never loses an id a
+ *    trace-id query returned.
+ *
  * Conventions are those of zkduration.h: every entry point returns zk_status; a handle is not
  * thread-safe; all device work of a handle is ordered on one HIP stream; nothing is allocated before
  * the first observe. Every call refuses a NULL handle or argument with ZK_ERR_INVALID_ARG before any
@@ -113,13 +139,19 @@ const char* zk_ix_last_error(const zk_ix* ix);
    changes nothing. The call synchronises once, to read the per-service counts it sizes the segment by
    (a merge, see Layout, synchronises once more). The scatter is queued on the handle's stream behind
    that: DEVICE columns must stay as they are until the handle's next synchronising call (zk_ix_info,
-   zk_ix_trace_ids, zk_ix_span_names, zk_ix_compact, zk_ix_observe). n == 0 is ZK_OK; n >= 2^32 is
-   ZK_ERR_UNSUPPORTED. */
+   zk_ix_trace_ids, zk_ix_span_names, zk_ix_compact, zk_ix_expire, zk_ix_observe). n == 0 is ZK_OK;
+   n >= 2^32 is ZK_ERR_UNSUPPORTED. */
 zk_status   zk_ix_observe(zk_ix* ix, const zk_span_cols* in, uint32_t flags);
 /* Empty the index: every segment is freed. */
 zk_status   zk_ix_reset(zk_ix* ix);
 /* Merge all segments into one (see Layout). Fewer than two segments: nothing to do. Synchronises. */
 zk_status   zk_ix_compact(zk_ix* ix);
+/* Remove every entry with ts < min_ts (see Expiry). *removed = the entries removed; may be NULL. Two
+   passes: a count over every segment's tkey column (8 B per entry), one synchronisation to read the
+   survivors per (segment, service), then the rewrite of the mixed segments' survivors (tkey again, and
+   18 B read and 18 B written per survivor). Scratch for the plan (4 B per segment and service, twice) is
+   allocated on first use and grown. An empty handle is ZK_OK with *removed = 0. Synchronises. */
+zk_status   zk_ix_expire(zk_ix* ix, int64_t min_ts, uint64_t* removed);
 /* entries in the index, segments, bytes of HBM the segments hold. Any of the three pointers may be
    NULL. Synchronises. */
 zk_status   zk_ix_info(zk_ix* ix, uint64_t* entries, uint64_t* segments, uint64_t* bytes);
@@ -150,6 +182,10 @@ zk_status   zk_ix_span_names(zk_ix* ix, uint32_t service, uint16_t* name_ids, ui
    counts' copy and, when the segment bound was met, the merge), the scatter. Needs zk_ix_config.timing;
    waits for the scatter. */
 zk_status   zk_ix_observe_ms(zk_ix* ix, double out[3]);
+/* Device time in ms of the last zk_ix_expire that ran its count: the count, the sizing step (the
+   counts' copy and the synchronisation), the rewrite (0 when no segment was mixed). Needs
+   zk_ix_config.timing. */
+zk_status   zk_ix_expire_ms(zk_ix* ix, double out[3]);
 /* Time in ms on the handle's stream of the last zk_ix_trace_ids that ran a pass, from its first pass
    to its last copy (the host's bin choices between the passes included). Needs zk_ix_config.timing. */
 zk_status   zk_ix_query_ms(zk_ix* ix, double* ms);

@@ -554,6 +554,8 @@ _SIGNATURES = [
                                C.POINTER(C.c_uint8)]),
     ("zk_td_top", C.c_int, [_P, C.c_uint32, C.c_int64, C.c_int64, C.c_uint32, _U64P, C.POINTER(C.c_int64),
                             C.POINTER(C.c_int64), _U32P, _U64P]),
+    ("zk_td_expire", C.c_int, [_P, C.c_int64, _U64P]),
+    ("zk_td_expire_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_td_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_td_top_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     # include/zkindex.h: the trace-id index by service and span name
@@ -568,6 +570,8 @@ _SIGNATURES = [
     ("zk_ix_trace_ids", C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int64, C.c_uint32, _U64P, C.POINTER(C.c_int64), _U32P,
                                   _U64P]),
     ("zk_ix_span_names", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint16), C.c_uint32, _U32P]),
+    ("zk_ix_expire", C.c_int, [_P, C.c_int64, _U64P]),
+    ("zk_ix_expire_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_ix_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_ix_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     # include/zkannindex.h: the trace-id index by annotation
@@ -581,6 +585,8 @@ _SIGNATURES = [
     ("zk_ax_service_counts", C.c_int, [_P, _U64P]),
     ("zk_ax_trace_ids", C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int64, C.c_uint32, _U64P,
                                   C.POINTER(C.c_int64), _U32P, _U64P]),
+    ("zk_ax_expire", C.c_int, [_P, C.c_int64, _U64P]),
+    ("zk_ax_expire_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_ax_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_ax_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
 ]

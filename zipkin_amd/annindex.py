@@ -106,6 +106,7 @@ class TraceAnnotationIndex:
     string, matched case-insensitively. Annotation and value bytes are matched exactly."""
 
     OBSERVE_PHASES = ("count", "size", "scatter")
+    EXPIRE_PHASES = ("count", "size", "rewrite")
 
     def __init__(self, num_services: int, device: int = 0, timing: bool = False, stream: Optional[int] = None,
                  services: Optional[Sequence[str]] = None):
@@ -151,7 +152,7 @@ class TraceAnnotationIndex:
         """Enter every entry of `items` (AnnotationItems or DeviceAnnotationItems, any order) as one
         segment (zk_ax_observe). Observing a batch again adds its entries again. sync=False leaves the
         scatter queued on the handle's stream: device columns must then stay as they are until the next
-        call that synchronises (info, trace_ids, compact, observe)."""
+        call that synchronises (info, trace_ids, compact, expire, observe)."""
         flags = 0
         ab = items.abi()
         if isinstance(items, DeviceAnnotationItems):
@@ -170,6 +171,15 @@ class TraceAnnotationIndex:
     def compact(self) -> None:
         """Merge all segments into one (zk_ax_compact)."""
         self._check(self._L.zk_ax_compact(self._h))
+
+    def expire(self, min_ts: int) -> int:
+        """Remove every entry with ts < min_ts, by the entry's own timestamp (zk_ax_expire); an entry at
+        min_ts stays. Returns the number removed. Afterwards the index answers as a fresh one that
+        observed only the survivors; segments that lose nothing are kept as they are, the survivors of
+        the others go into one new segment. Synchronises."""
+        n = C.c_uint64()
+        self._check(self._L.zk_ax_expire(self._h, int(min_ts), C.byref(n)))
+        return int(n.value)
 
     def info(self) -> dict:
         """{"entries", "segments", "bytes"} (zk_ax_info); synchronises."""
@@ -248,6 +258,12 @@ class TraceAnnotationIndex:
         out = (C.c_double * len(self.OBSERVE_PHASES))()
         self._check(self._L.zk_ax_observe_ms(self._h, out))
         return dict(zip(self.OBSERVE_PHASES, out))
+
+    def expire_ms(self) -> dict:
+        """Device time (ms) of the passes of the last expire (zk_ax_expire_ms; timing=True)."""
+        out = (C.c_double * len(self.EXPIRE_PHASES))()
+        self._check(self._L.zk_ax_expire_ms(self._h, out))
+        return dict(zip(self.EXPIRE_PHASES, out))
 
     def query_ms(self) -> float:
         """Time (ms) on the handle's stream of the last trace_ids pass (zk_ax_query_ms)."""

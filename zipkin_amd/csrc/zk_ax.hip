@@ -18,17 +18,21 @@
 //   k_ax_scan, k_ax_hist, k_ax_collect   zk_ax_trace_ids' passes: those of zk_ix.hip, over a filter
 //                 that reads key, then val where the key matched and a value was asked, then tkey and
 //                 tid where both matched
+//   k_ax_expire_count, k_ax_expire_rewrite   zk_ax_expire's passes (zk_expire.h, as in zk_ix.hip): the
+//                 survivors per (segment, service) from the tkey column alone, then the survivors of the
+//                 mixed segments into one new segment, the service of an entry from its place
 //
 // Every store is bounded: the scatter and the merge drop a place at or past the segment's size (it
 // cannot arise while the columns stay as they were between the count and the scatter, which the header
 // asks of the caller; a caller that breaks it loses entries and corrupts nothing), the collect drops
-// entries past its lists' capacities.
+// entries past its lists' capacities, the expiry's rewrite a place at or past the new segment's size.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include <string>
 #include <vector>
 
+#include "zk_expire.h"
 #include "zk_guard.h"
 #include "zk_hist.h"
 #include "zk_ix_select.h"
@@ -346,6 +350,35 @@ __global__ __launch_bounds__(kAxWG) void k_ax_collect(const AxSlice* __restrict_
     flush_bits(or_hi, nor_hi, or_lo, nor_lo, sel);
 }
 
+// ---- expiry (zk_expire.h) -----------------------------------------------------------------------------
+static_assert(kExpBins == kAxSvcBins && kExpWG == kAxWG, "zk_expire.h's bins and workgroup are this file's");
+
+__global__ __launch_bounds__(kExpWG) void k_ax_expire_count(const ExpSeg* __restrict__ segs, const ExpItem* __restrict__ items,
+                                                            unsigned long long chunk, uint32_t S, unsigned long long cut,
+                                                            uint32_t* __restrict__ surv) {
+    __shared__ ExpLds lds;
+    exp_count(segs, items, chunk, S, cut, surv, &lds);
+}
+
+// an old segment's entry into the new one: tid, key and val lie behind tkey (Segment's layout); 32 B written
+struct AxPut {
+    AxCols dst;
+    __device__ void operator()(const ExpSeg& sg, unsigned long long i, unsigned long long k, unsigned long long at) const {
+        const unsigned long long col = (sg.n * 8ull + 255ull) / 256ull * 32ull;  // a column, in words
+        dst.p[at] = k;
+#pragma unroll
+        for (int c = 1; c < 4; ++c) dst.p[c * dst.stride + at] = sg.tkey[c * col + i];
+    }
+};
+
+__global__ __launch_bounds__(kExpWG) void k_ax_expire_rewrite(const ExpSeg* __restrict__ segs, const ExpItem* __restrict__ items,
+                                                              unsigned long long chunk, uint32_t S, unsigned long long cut,
+                                                              uint32_t* __restrict__ cursor, unsigned long long total, AxPut put) {
+    __shared__ ExpLds lds;
+    __shared__ uint32_t s_base[kExpBins];
+    exp_rewrite(segs, items, chunk, S, cut, cursor, total, put, &lds, s_base);
+}
+
 struct Segment {
     void* block = nullptr;
     size_t bytes = 0;
@@ -378,16 +411,21 @@ struct zk_ax {
     void* obs = nullptr;                // the observe's counts, cursors and range violations (kObsBytes)
     void* stage = nullptr;              // the five columns of a host batch
     void* mplan = nullptr;              // a merge's offsets and bases, per old segment
+    void* xplan = nullptr;              // an expiry's segments, offsets, work items, survivor counts and cursors
     void* sel = nullptr;                // the select's counters, histogram, certain list, slices (kSelBytes)
     void* list[2] = {nullptr, nullptr}; // the candidate lists, written in turn
-    size_t stage_bytes = 0, mplan_bytes = 0, sel_bytes = 0, list_bytes[2] = {0, 0};
+    size_t stage_bytes = 0, mplan_bytes = 0, xplan_bytes = 0, sel_bytes = 0, list_bytes[2] = {0, 0};
     std::vector<uint32_t> counts_host, cursor_host;  // (a queued copy reads cursor_host: it changes only behind a synchronisation)
     std::vector<uint64_t> mplan_host;
+    std::vector<uint8_t> xplan_host;                 // (an expiry's queued copies read these three: likewise)
+    std::vector<uint32_t> xsurv_host, xcursor_host;
+    std::vector<ExpItem> xitems_host;
     std::vector<AxSlice> slices_host;
     std::vector<IxSpan> spans;
     hipEvent_t oev[4] = {};  // around the passes of the last observe (zk_ax_observe_ms)
     hipEvent_t qev[2] = {};  // around the last query (zk_ax_query_ms)
-    bool otimed = false, qtimed = false;
+    hipEvent_t xev[4] = {};  // around the passes of the last expiry (zk_ax_expire_ms)
+    bool otimed = false, qtimed = false, xtimed = false;
     std::string err;
 };
 
@@ -507,6 +545,130 @@ zk_status plan_slices(zk_ax* h, uint32_t service, uint64_t* total, uint64_t* lon
     return ZK_OK;
 }
 
+// zk_ax_expire behind its argument checks: every entry with tkey < cut goes. The count pass over all
+// segments, the one synchronisation that sizes the rest, then the segments sorted into untouched (no
+// entry goes: not read again), gone (every entry goes: freed) and mixed (their survivors rewritten into
+// ONE new segment, which takes the place of the first of them). Nothing is freed and no bookkeeping
+// changes before the new segment is complete; anything refused leaves the index as it was.
+zk_status expire(zk_ax* h, unsigned long long cut, uint64_t* removed_out) {
+    const uint32_t S = h->S, G = (uint32_t)h->segs.size();
+    const auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+    const auto items_at = [&](uint64_t c) {
+        uint64_t w = 0;
+        for (const Segment& g : h->segs) w += (g.n + c - 1) / c;
+        return w;
+    };
+    uint64_t chunk = kExpPerWG;
+    while (items_at(chunk) > kExpMaxItems + G) chunk *= 2;
+    const uint32_t W = (uint32_t)items_at(chunk);
+    // the plan: the segments, their offsets [G][S + 1], the work items, then what the device writes:
+    // the survivors [G][S] and the new segment's cursors [S]
+    const size_t off_at = al(G * sizeof(ExpSeg)), item_at = off_at + al((size_t)G * (S + 1) * 4);
+    const size_t surv_at = item_at + al((size_t)W * sizeof(ExpItem)), cur_at = surv_at + al((size_t)G * S * 4);
+    zk_status st = grow(h, &h->xplan, &h->xplan_bytes, cur_at + al((size_t)S * 4), "an expiry's plan");
+    if (st != ZK_OK) return st;
+    uint8_t* xp = (uint8_t*)h->xplan;
+    h->xplan_host.assign(surv_at, 0);
+    ExpSeg* hs = (ExpSeg*)h->xplan_host.data();
+    uint32_t* ho = (uint32_t*)(h->xplan_host.data() + off_at);
+    ExpItem* hi = (ExpItem*)(h->xplan_host.data() + item_at);
+    uint32_t w = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        const Segment& sg = h->segs[g];
+        hs[g] = ExpSeg{sg.tkey(), (unsigned long long)sg.n, (const uint32_t*)(xp + off_at) + (size_t)g * (S + 1)};
+        for (uint32_t s = 0; s <= S; ++s) ho[(size_t)g * (S + 1) + s] = (uint32_t)sg.off[s];
+        for (uint64_t c = 0; c * chunk < sg.n; ++c) hi[w++] = ExpItem{g, (uint32_t)c};
+    }
+    const ExpSeg* segs = (const ExpSeg*)xp;
+    const ExpItem* items = (const ExpItem*)(xp + item_at);
+    uint32_t* surv = (uint32_t*)(xp + surv_at);
+    uint32_t* cursor = (uint32_t*)(xp + cur_at);
+    const bool timing = h->timing;
+    for (hipEvent_t& e : h->xev)
+        if (timing && !e) AX_HIP(h, hipEventCreate(&e));
+    AX_HIP(h, hipMemcpyAsync(xp, h->xplan_host.data(), surv_at, hipMemcpyHostToDevice, h->stream));
+    AX_HIP(h, hipMemsetAsync(surv, 0, (size_t)G * S * 4, h->stream));
+    if (timing) AX_HIP(h, hipEventRecord(h->xev[0], h->stream));
+    AX_HIP(h, launch_checked("k_ax_expire_count", k_ax_expire_count, dim3(W), dim3(kExpWG), 0, h->stream, segs, items,
+                             (unsigned long long)chunk, S, cut, surv));
+    if (timing) AX_HIP(h, hipEventRecord(h->xev[1], h->stream));
+    h->xsurv_host.resize((size_t)G * S);
+    AX_HIP(h, hipMemcpyAsync(h->xsurv_host.data(), surv, (size_t)G * S * 4, hipMemcpyDeviceToHost, h->stream));
+    AX_HIP(h, hipStreamSynchronize(h->stream));  // the sizing synchronisation
+    std::vector<uint64_t> keep(G, 0), gone(S, 0);
+    std::vector<uint32_t> mixed;
+    uint64_t removed = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        const Segment& sg = h->segs[g];
+        for (uint32_t s = 0; s < S; ++s) {
+            const uint64_t len = sg.off[s + 1] - sg.off[s], c = h->xsurv_host[(size_t)g * S + s];
+            if (c > len) return xfail(h, ZK_ERR_HIP, "the expiry counted more survivors than a slice holds");
+            keep[g] += c;
+            gone[s] += len - c;
+        }
+        removed += sg.n - keep[g];
+        if (keep[g] != 0 && keep[g] != sg.n) mixed.push_back(g);
+    }
+    if (removed == 0) {  // nothing goes: nothing is rewritten, reallocated or freed
+        if (timing) AX_HIP(h, hipEventRecord(h->xev[2], h->stream));
+        if (timing) AX_HIP(h, hipEventRecord(h->xev[3], h->stream));
+        h->xtimed = timing;
+        return ZK_OK;
+    }
+    Segment m;
+    if (!mixed.empty()) {
+        m.off.assign(S + 1, 0);
+        for (uint32_t s = 0; s < S; ++s) {
+            uint64_t c = 0;
+            for (uint32_t g : mixed) c += h->xsurv_host[(size_t)g * S + s];
+            m.off[s + 1] = m.off[s] + c;
+        }
+        m.n = m.off[S];
+        m.bytes = Segment::bytes_for(m.n);
+        if ((st = alloc(h, &m.block, m.bytes, "the survivors' segment (32 B per entry)")) != ZK_OK) return st;
+        h->xcursor_host.resize(S);
+        for (uint32_t s = 0; s < S; ++s) h->xcursor_host[s] = (uint32_t)m.off[s];
+        h->xitems_host.clear();
+        for (uint32_t g : mixed)
+            for (uint64_t c = 0; c * chunk < h->segs[g].n; ++c) h->xitems_host.push_back(ExpItem{g, (uint32_t)c});
+    }
+    hipError_t e = hipSuccess;
+    if (!mixed.empty()) {
+        e = hipMemcpyAsync(xp + item_at, h->xitems_host.data(), h->xitems_host.size() * sizeof(ExpItem), hipMemcpyHostToDevice,
+                           h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(cursor, h->xcursor_host.data(), (size_t)S * 4, hipMemcpyHostToDevice, h->stream);
+    }
+    if (e == hipSuccess && timing) e = hipEventRecord(h->xev[2], h->stream);
+    if (e == hipSuccess && !mixed.empty())
+        e = launch_checked("k_ax_expire_rewrite", k_ax_expire_rewrite, dim3((uint32_t)h->xitems_host.size()), dim3(kExpWG), 0,
+                           h->stream, segs, items, (unsigned long long)chunk, S, cut, cursor, (unsigned long long)m.n,
+                           AxPut{m.cols()});
+    if (e == hipSuccess && timing) e = hipEventRecord(h->xev[3], h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream);
+        if (m.block) (void)hipFree(m.block);
+        return xfail(h, is_refusal(e) ? ZK_ERR_CAPACITY : ZK_ERR_HIP, std::string("rewriting the survivors: ") + launch_error_str(e));
+    }
+    // the new segment is complete: the gone and the mixed segments leave
+    std::vector<Segment> left;
+    for (uint32_t g = 0; g < G; ++g) {
+        Segment& sg = h->segs[g];
+        if (keep[g] == sg.n) {
+            left.push_back(std::move(sg));
+            continue;
+        }
+        (void)hipFree(sg.block);
+        if (!mixed.empty() && g == mixed[0]) left.push_back(std::move(m));
+    }
+    h->segs = std::move(left);
+    for (uint32_t s = 0; s < S; ++s) h->svc_count[s] -= gone[s];
+    h->entries -= removed;
+    h->xtimed = timing;
+    if (removed_out) *removed_out = removed;
+    return ZK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -546,9 +708,11 @@ zk_status zk_ax_destroy(zk_ax* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     free_segments(h);
-    for (void* p : {h->obs, h->stage, h->mplan, h->sel, h->list[0], h->list[1]})
+    for (void* p : {h->obs, h->stage, h->mplan, h->xplan, h->sel, h->list[0], h->list[1]})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : h->oev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->xev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->qev)
         if (e) (void)hipEventDestroy(e);
@@ -681,6 +845,32 @@ zk_status zk_ax_compact(zk_ax* h) {
     if (h->segs.size() < 2) return ZK_OK;
     AX_HIP(h, hipSetDevice(h->device));
     return merge_all(h);
+    ZK_GUARD_END
+}
+
+zk_status zk_ax_expire(zk_ax* h, int64_t min_ts, uint64_t* removed) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (removed) *removed = 0;
+    h->xtimed = false;
+    if (h->segs.empty()) return ZK_OK;
+    AX_HIP(h, hipSetDevice(h->device));
+    return expire(h, (unsigned long long)min_ts ^ kTdSign, removed);
+    ZK_GUARD_END
+}
+
+zk_status zk_ax_expire_ms(zk_ax* h, double out[3]) {
+    ZK_GUARD_BEGIN
+    if (!h || !out) return ZK_ERR_INVALID_ARG;
+    if (!h->xtimed) return xfail(h, ZK_ERR_INVALID_ARG, "no timed expiry has run a pass (zk_ax_config.timing)");
+    AX_HIP(h, hipSetDevice(h->device));
+    AX_HIP(h, hipEventSynchronize(h->xev[3]));
+    for (int k = 0; k < 3; ++k) {
+        float ms = 0.f;
+        AX_HIP(h, hipEventElapsedTime(&ms, h->xev[k], h->xev[k + 1]));
+        out[k] = ms;
+    }
+    return ZK_OK;
     ZK_GUARD_END
 }
 

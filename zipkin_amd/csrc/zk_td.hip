@@ -23,6 +23,8 @@
 //   k_td_observe  one table update per (run, row of 64 records): a probe, at most one CAS on the key, at
 //                 most one atomicMin on start and one atomicMax on end
 //   k_td_rehash   the old table's entries into a grown one; k_td_clear empties a table
+//   k_td_expire_count, k_td_expire_move   zk_td_expire: the traces that stay, then (when some go) the
+//                 stayers into a fresh table sized for them (see there)
 //   k_td_query    zk_td_lookup
 //   k_td_scan, k_td_hist, k_td_collect   zk_td_top's passes (see there)
 #include <hip/hip_runtime.h>
@@ -49,7 +51,7 @@ constexpr int kTdWG = 256;
 constexpr uint32_t kTdMaxGrid = 4096;
 constexpr uint32_t kTdHistGrid = 1024;  // k_td_hist: every workgroup flushes up to 4096 bins
 constexpr uint32_t kTdCap = ZK_TD_MAX_TOP;  // the most entries the select brings to the host
-enum { kTsTraces = 0, kTsRuns = 1, kTsFull = 2, kTsWords = 4 };
+enum { kTsTraces = 0, kTsRuns = 1, kTsFull = 2, kTsAlive = 3, kTsWords = 4 };
 // the select's counters: matched, certain entries appended, then what a round zeroes: the OR of the
 // keys and of their complements (hi, lo) over the entries that stay candidates, and their number
 enum { kSelMatched = 0, kSelCertain = 1, kSelOrHi = 2, kSelNorHi = 3, kSelOrLo = 4, kSelNorLo = 5, kSelCand = 6, kSelWords = 8 };
@@ -108,6 +110,55 @@ __global__ __launch_bounds__(kTdWG) void k_td_rehash(const unsigned long long* _
     for (unsigned long long i = (unsigned long long)blockIdx.x * kTdWG + threadIdx.x; i <= old_slots; i += stride) {
         const unsigned long long key = old[3 * i], sk = old[3 * i + 1], ek = old[3 * i + 2];
         if (key == 0ull) continue;
+        if (i == old_slots) {  // traceId 0
+            tab[3 * slots] = 1ull;
+            tab[3 * slots + 1] = sk;
+            tab[3 * slots + 2] = ek;
+            continue;
+        }
+        unsigned long long s = td_home(key, slots), tries = 0;
+        for (; tries < slots; ++tries) {
+            if (atomicCAS(&tab[3 * s], 0ull, key) == 0ull) {
+                tab[3 * s + 1] = sk;
+                tab[3 * s + 2] = ek;
+                break;
+            }
+            s = (s + 1ull) & (slots - 1ull);
+        }
+        if (tries == slots) atomicAdd(&tstat[kTsFull], 1ull);
+    }
+}
+
+// ---- expiry --------------------------------------------------------------------------------------------
+// Linear probing has no delete in place: emptying a slot cuts the probe chain of every key that was
+// displaced past it. zk_td_expire so counts the traces that stay (k_td_expire_count) and, when some go,
+// moves the stayers into a fresh table sized for them (k_td_expire_move: k_td_rehash with the predicate).
+// A trace stays when its end key is >= cut; the slot of traceId 0 follows the same rule.
+__global__ __launch_bounds__(kTdWG) void k_td_expire_count(const unsigned long long* __restrict__ tab, unsigned long long slots,
+                                                           unsigned long long cut, unsigned long long* __restrict__ tstat) {
+    __shared__ unsigned long long s_sum;
+    if (threadIdx.x == 0) s_sum = 0ull;
+    __syncthreads();
+    const unsigned long long stride = (unsigned long long)gridDim.x * kTdWG;
+    unsigned long long c = 0;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * kTdWG + threadIdx.x; i <= slots; i += stride)
+        c += tab[3 * i] != 0ull && tab[3 * i + 2] >= cut;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
+    if (lane_id() == 0 && c) atomicAdd(&s_sum, c);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_sum) atomicAdd(&tstat[kTsAlive], s_sum);
+}
+
+// the old table's entries with end key >= cut into the fresh one (cleared, at load <= 1/2 for them): keys
+// are unique, so the thread that claims a key is the only writer of its two times
+__global__ __launch_bounds__(kTdWG) void k_td_expire_move(const unsigned long long* __restrict__ old, unsigned long long old_slots,
+                                                          unsigned long long cut, unsigned long long* __restrict__ tab,
+                                                          unsigned long long slots, unsigned long long* __restrict__ tstat) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * kTdWG;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * kTdWG + threadIdx.x; i <= old_slots; i += stride) {
+        const unsigned long long key = old[3 * i], sk = old[3 * i + 1], ek = old[3 * i + 2];
+        if (key == 0ull || ek < cut) continue;
         if (i == old_slots) {  // traceId 0
             tab[3 * slots] = 1ull;
             tab[3 * slots + 1] = sk;
@@ -447,7 +498,7 @@ struct zk_td {
     hipStream_t stream = nullptr, own = nullptr;
     bool timing = false;
     void* table = nullptr;   // three u64 words [slots + 1]
-    void* tstat = nullptr;   // u64 [kTsWords]: traces, the last batch's runs, probe loops that ran out
+    void* tstat = nullptr;   // u64 [kTsWords]: traces, the last batch's runs, probe loops that ran out, the last expiry's stayers
     void* stage = nullptr;   // the four columns of a host batch
     void* query = nullptr;   // zk_td_lookup: ids, starts, durations, found
     void* sel = nullptr;     // zk_td_top: counters, histogram, the certain list (kSelBytes)
@@ -456,7 +507,8 @@ struct zk_td {
     size_t stage_bytes = 0, query_bytes = 0, sel_bytes = 0, list_bytes[2] = {0, 0};
     hipEvent_t oev[4] = {};  // around the passes of the last observe (zk_td_observe_ms)
     hipEvent_t tev[2] = {};  // around the last top (zk_td_top_ms)
-    bool otimed = false, ttimed = false;
+    hipEvent_t xev[4] = {};  // around the passes of the last expiry (zk_td_expire_ms)
+    bool otimed = false, ttimed = false, xtimed = false;
     std::string err;
 };
 
@@ -580,6 +632,8 @@ zk_status zk_td_destroy(zk_td* h) {
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->tev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->xev)
+        if (e) (void)hipEventDestroy(e);
     if (h->own) (void)hipStreamDestroy(h->own);
     delete h;
     return ZK_OK;
@@ -680,6 +734,84 @@ zk_status zk_td_reserve(zk_td* h, uint64_t traces) {
     if (traces > kTdMaxSlots / 2) return tfail(h, ZK_ERR_CAPACITY, "a duration table of more than 2^40 slots");
     TD_HIP(h, hipSetDevice(h->device));
     return ensure_slots(h, 2 * traces);
+    ZK_GUARD_END
+}
+
+zk_status zk_td_expire(zk_td* h, int64_t min_end, uint64_t* removed) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (removed) *removed = 0;
+    h->xtimed = false;
+    if (!h->table) return ZK_OK;
+    TD_HIP(h, hipSetDevice(h->device));
+    const unsigned long long cut = (unsigned long long)min_end ^ kTdSign;
+    unsigned long long* tstat = (unsigned long long*)h->tstat;
+    const bool timing = h->timing;
+    for (hipEvent_t& e : h->xev)
+        if (timing && !e) TD_HIP(h, hipEventCreate(&e));
+    TD_HIP(h, hipMemsetAsync(tstat + kTsAlive, 0, 8, h->stream));
+    if (timing) TD_HIP(h, hipEventRecord(h->xev[0], h->stream));
+    TD_HIP(h, launch_checked("k_td_expire_count", k_td_expire_count, dim3(td_grid(h->slots + 1)), dim3(kTdWG), 0, h->stream,
+                             (const unsigned long long*)h->table, (unsigned long long)h->slots, cut, tstat));
+    if (timing) TD_HIP(h, hipEventRecord(h->xev[1], h->stream));
+    unsigned long long host[kTsWords];
+    TD_HIP(h, hipMemcpyAsync(host, tstat, sizeof host, hipMemcpyDeviceToHost, h->stream));
+    TD_HIP(h, hipStreamSynchronize(h->stream));  // the sizing synchronisation
+    if (host[kTsFull]) return tfail(h, ZK_ERR_HIP, "the duration table ran full (the sizing rule was broken)");
+    const uint64_t alive = host[kTsAlive];
+    if (alive > host[kTsTraces]) return tfail(h, ZK_ERR_HIP, "the expiry counted more traces than the table holds");
+    if (alive == host[kTsTraces]) {  // nothing goes: the table stays where and as it is
+        if (timing) TD_HIP(h, hipEventRecord(h->xev[2], h->stream));
+        if (timing) TD_HIP(h, hipEventRecord(h->xev[3], h->stream));
+        h->xtimed = timing;
+        return ZK_OK;
+    }
+    // the SIZING rule for the stayers alone: this is the one place where the table may shrink
+    uint64_t slots = kTdMinSlots;
+    while (slots < 2 * alive) slots <<= 1;
+    void* q = nullptr;
+    size_t have = 0;
+    const zk_status st = grow(h, &q, &have, (size_t)(slots + 1) * sizeof(TdEntry), "the duration table (24 B per slot)");
+    if (st != ZK_OK) return st;
+    const unsigned long long stay = alive;  // (a queued copy reads it; every path below synchronises)
+    hipError_t e = timing ? hipEventRecord(h->xev[2], h->stream) : hipSuccess;
+    if (e == hipSuccess)
+        e = launch_checked("k_td_clear", k_td_clear, dim3(td_grid(slots + 1)), dim3(kTdWG), 0, h->stream, (unsigned long long*)q,
+                           (unsigned long long)(slots + 1));
+    if (e == hipSuccess)
+        e = launch_checked("k_td_expire_move", k_td_expire_move, dim3(td_grid(h->slots + 1)), dim3(kTdWG), 0, h->stream,
+                           (const unsigned long long*)h->table, (unsigned long long)h->slots, cut, (unsigned long long*)q,
+                           (unsigned long long)slots, tstat);
+    if (e == hipSuccess && timing) e = hipEventRecord(h->xev[3], h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(tstat + kTsTraces, &stay, 8, hipMemcpyHostToDevice, h->stream);  // the stayers' count
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream);
+        (void)hipFree(q);
+        return tfail(h, is_refusal(e) ? ZK_ERR_CAPACITY : ZK_ERR_HIP, std::string("rebuilding the duration table: ") + launch_error_str(e));
+    }
+    // the new table is complete: the old one leaves
+    (void)hipFree(h->table);
+    h->table = q;
+    h->slots = slots;
+    h->xtimed = timing;
+    if (removed) *removed = host[kTsTraces] - alive;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_td_expire_ms(zk_td* h, double out[3]) {
+    ZK_GUARD_BEGIN
+    if (!h || !out) return ZK_ERR_INVALID_ARG;
+    if (!h->xtimed) return tfail(h, ZK_ERR_INVALID_ARG, "no timed expiry has run a pass (zk_td_config.timing)");
+    TD_HIP(h, hipSetDevice(h->device));
+    TD_HIP(h, hipEventSynchronize(h->xev[3]));
+    for (int k = 0; k < 3; ++k) {
+        float ms = 0.f;
+        TD_HIP(h, hipEventElapsedTime(&ms, h->xev[k], h->xev[k + 1]));
+        out[k] = ms;
+    }
+    return ZK_OK;
     ZK_GUARD_END
 }
 

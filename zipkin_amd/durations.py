@@ -98,12 +98,13 @@ class TraceDurationIndex:
             pass
 
     OBSERVE_PHASES = ("runs", "grow", "insert")
+    EXPIRE_PHASES = ("count", "size", "rebuild")
 
     def observe(self, cols, *, sync: bool = True) -> None:
         """Fold a batch (host SpanColumns or DeviceColumns, any order) into the index (zk_td_observe).
         Observing a batch again changes nothing. sync=False leaves the inserts queued on the handle's
         stream: device columns must then stay as they are until the next call that synchronises
-        (info, lookup, getTracesDuration, top, observe)."""
+        (info, lookup, getTracesDuration, top, expire, observe)."""
         flags = 0
         ab = cols.abi()
         if isinstance(cols, DeviceColumns):
@@ -122,6 +123,15 @@ class TraceDurationIndex:
     def reserve(self, traces: int) -> None:
         """Grow the table to at least 2 * traces slots now (zk_td_reserve); never shrinks."""
         self._check(self._L.zk_td_reserve(self._h, traces))
+
+    def expire(self, min_end: int) -> int:
+        """Remove every trace whose end < min_end, by the trace's own end time (zk_td_expire); a trace
+        that ends at min_end stays. Returns the number removed. When something goes the survivors are
+        rebuilt into a table sized for them (the one operation that may shrink it; a reserve() hint
+        does not survive it). Synchronises."""
+        n = C.c_uint64()
+        self._check(self._L.zk_td_expire(self._h, int(min_end), C.byref(n)))
+        return int(n.value)
 
     def info(self) -> dict:
         """{"slots", "traces", "bytes"} of the table (zk_td_info); synchronises."""
@@ -195,6 +205,12 @@ class TraceDurationIndex:
         out = (C.c_double * len(self.OBSERVE_PHASES))()
         self._check(self._L.zk_td_observe_ms(self._h, out))
         return dict(zip(self.OBSERVE_PHASES, out))
+
+    def expire_ms(self) -> dict:
+        """Device time (ms) of the passes of the last expire (zk_td_expire_ms; timing=True)."""
+        out = (C.c_double * len(self.EXPIRE_PHASES))()
+        self._check(self._L.zk_td_expire_ms(self._h, out))
+        return dict(zip(self.EXPIRE_PHASES, out))
 
     def top_ms(self) -> float:
         """Time (ms) on the handle's stream of the last top (zk_td_top_ms; timing=True)."""

@@ -58,6 +58,7 @@ class TraceNameIndex:
     i + 1); with them `service` and `span_name` may be strings, matched case-insensitively."""
 
     OBSERVE_PHASES = ("count", "size", "scatter")
+    EXPIRE_PHASES = ("count", "size", "rewrite")
 
     def __init__(self, num_services: int, device: int = 0, client_service: Optional[int] = None, timing: bool = False,
                  stream: Optional[int] = None, services: Optional[Sequence[str]] = None,
@@ -106,7 +107,7 @@ class TraceNameIndex:
         """Add a batch's entries (host SpanColumns or DeviceColumns, any order) as one segment
         (zk_ix_observe). Observing a batch again adds its entries again. sync=False leaves the scatter
         queued on the handle's stream: device columns must then stay as they are until the next call
-        that synchronises (info, getTraceIdsByName, getSpanNames, compact, observe)."""
+        that synchronises (info, getTraceIdsByName, getSpanNames, compact, expire, observe)."""
         flags = 0
         ab = cols.abi()
         if isinstance(cols, DeviceColumns):
@@ -125,6 +126,15 @@ class TraceNameIndex:
     def compact(self) -> None:
         """Merge all segments into one (zk_ix_compact)."""
         self._check(self._L.zk_ix_compact(self._h))
+
+    def expire(self, min_ts: int) -> int:
+        """Remove every entry with ts < min_ts, by the entry's own timestamp (zk_ix_expire); an entry at
+        min_ts stays. Returns the number removed. Afterwards the index answers as a fresh one that
+        observed only the survivors; segments that lose nothing are kept as they are, the survivors of
+        the others go into one new segment. Synchronises."""
+        n = C.c_uint64()
+        self._check(self._L.zk_ix_expire(self._h, int(min_ts), C.byref(n)))
+        return int(n.value)
 
     def info(self) -> dict:
         """{"entries", "segments", "bytes"} (zk_ix_info); synchronises."""
@@ -234,6 +244,12 @@ class TraceNameIndex:
         out = (C.c_double * len(self.OBSERVE_PHASES))()
         self._check(self._L.zk_ix_observe_ms(self._h, out))
         return dict(zip(self.OBSERVE_PHASES, out))
+
+    def expire_ms(self) -> dict:
+        """Device time (ms) of the passes of the last expire (zk_ix_expire_ms; timing=True)."""
+        out = (C.c_double * len(self.EXPIRE_PHASES))()
+        self._check(self._L.zk_ix_expire_ms(self._h, out))
+        return dict(zip(self.EXPIRE_PHASES, out))
 
     def query_ms(self) -> float:
         """Time (ms) on the handle's stream of the last getTraceIdsByName pass (zk_ix_query_ms)."""
