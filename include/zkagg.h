@@ -136,7 +136,11 @@ typedef struct zk_span_cols {
  * accumulate -- a trace cut at a batch edge, as a streaming reader of row-per-trace storage cuts
  * them. Its fragments are held back in HBM (up to max_trace_records) and joined with the next
  * batch's leading fragments of the same traceId; a held trace may continue over any number of
- * batches. The held trace is aggregated when a batch moves on to another traceId, when a batch
+ * batches. A trace longer than max_trace_records is reported as trace_too_large like any other,
+ * once and with none of its fragments aggregated, however many batches it spans: a last run of
+ * more than max_trace_records + 1 records is not held but reported with its batch, and its
+ * fragments in the batches that follow are skipped.
+ * The held trace is aggregated when a batch moves on to another traceId, when a batch
  * arrives without the flag, at finalize and at zk_deps_partial; zk_ctx_stats does not count it
  * before then. Decided on the device (no host round trip): one small kernel finds the batch's
  * edge runs (scanning from both ends until a trace boundary) and applies these rules. */
@@ -148,8 +152,14 @@ typedef struct zk_config {
     void*    stream;             /* hipStream_t to run on, or NULL for a private stream */
     uint32_t strict;             /* 1: finalize returns ZK_ERR_NO_SERVICE like the reference's
                                     None.get; 0: such pairs are skipped and counted */
-    uint32_t max_trace_records;  /* largest trace handled (default 131072 > MaxTraceCols=100000,
-                                    CassieSpanStore.scala:50) */
+    uint32_t max_trace_records;  /* largest trace handled (0: the default, 131072 > MaxTraceCols=100000,
+                                    CassieSpanStore.scala:50). A trace of more records is not
+                                    aggregated and counted once in trace_too_large, on every path and
+                                    wherever batches cut it. At least 512, the records of one window of
+                                    the streaming join, and at most 2^20: the bound sizes the spill
+                                    scratch and the held trace, the join of a trace that fits one
+                                    window does not look at it. zk_ctx_create refuses other values
+                                    (ZK_ERR_INVALID_ARG). */
     uint32_t timing;             /* 1: record per-kernel HIP events (zk_ctx_timing) */
     void*    table;              /* optional caller-owned device buffer for the exact accumulator
                                     (table_bytes >= ZK_TABLE_BYTES(S)), e.g. to place it in a pool the
@@ -169,7 +179,9 @@ typedef struct zk_ctx zk_ctx;
 
 /* Per-ctx counters since the last zk_deps_reset (all device-counted, exact). */
 typedef struct zk_stats {
-    uint64_t records;          /* span fragments accumulated */
+    uint64_t records;          /* span fragments aggregated: every accepted fragment but those of
+                                  traces counted in trace_too_large (on every path, and wherever
+                                  ZK_BATCH_CONTINUES batches cut such a trace) */
     uint64_t merged_spans;     /* distinct (traceId, spanId) after mergeSpan */
     uint64_t valid_spans;      /* merged spans passing isValid */
     uint64_t invalid_spans;    /* dropped by isValid (a core annotation > once) */

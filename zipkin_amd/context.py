@@ -77,6 +77,11 @@ class LinkTable:
 
 
 class DepsContext:
+    """max_trace_records: the largest trace aggregated; a longer one is counted once in
+    `trace_too_large` and finalize raises ZK_ERR_TRACE_TOO_LARGE. 0 is the default (131072), any other
+    value must be 512..2^20: 512 records are one window of the streaming join, which joins every trace
+    that fits a window without looking at the bound, so a smaller one is refused (ZK_ERR_INVALID_ARG)."""
+
     def __init__(
         self,
         num_services: int,

@@ -388,6 +388,10 @@ zk_status zk_ctx_create(const zk_config* cfg, zk_ctx** out) {
     *out = nullptr;
     if (cfg->num_services == 0 || cfg->num_services > kMaxServices) return ZK_ERR_INVALID_ARG;
     if (cfg->max_trace_records > (1u << 20)) return ZK_ERR_INVALID_ARG;
+    // K1 joins every trace that fits one of its windows without looking at the bound (the bound sizes
+    // the spill scratch and the carry), while the held-trace plan applies it: below one window the
+    // result would depend on where a reader cut the stream
+    if (cfg->max_trace_records && cfg->max_trace_records < join_tile_records()) return ZK_ERR_INVALID_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return ZK_ERR_NO_DEVICE;
     if (cfg->device < 0 || cfg->device >= ndev) return ZK_ERR_NO_DEVICE;

@@ -60,12 +60,14 @@ hipError_t launch_stats_fold(const unsigned long long* shards, unsigned long lon
 // k_carry_plan finds the batch's edge runs, mirrors the rules of zkagg.h (the leading run continues
 // the held trace when it has its traceId; the held trace is complete once a batch moves on; a held
 // trace longer than max_trace_records is dropped and counted once; with CONTINUES the batch's last
-// run is held back) and writes the batch's plan, which the trace check, K1 (skip_dev, n_dev = &hi),
+// run is held back, or, when it has more than max_trace + 1 records, left to K1, which reports it, and
+// remembered as dropped) and writes the batch's plan, which the trace check, K1 (skip_dev, n_dev = &hi),
 // the carry's join (K1 on one workgroup, or the spill kernel) and the tail copy read.
 struct CarryState {
     unsigned long long n;         // records held in the carry
     unsigned long long tid;       // their traceId
-    unsigned int dropped;         // the held trace outgrew max_trace_records: its rest is skipped
+    unsigned int dropped;         // the trace `tid` is longer than max_trace_records and already counted
+                                  // (n = 0): its rest is skipped
     unsigned int verify;          // a batch that carried it asked for ZK_BATCH_VERIFY_TRACES
     // the current batch's plan
     unsigned long long append_at; // the batch's records [0, append_n) go to carry[append_at, ...)

@@ -837,9 +837,16 @@ __global__ __launch_bounds__(256) void k_carry_plan(CarryState* __restrict__ cs,
             }
             if (!done) {
                 uint64_t hi = n;
-                if (continues && last_start != kUnknown) {
-                    // (a last run longer than L + 1 is not held: K1 reports it too large; the leading
-                    // run ends at or before the last run's start unless the batch is one run)
+                if (continues && last_start == kUnknown) {
+                    // a last run longer than L + 1 is not held: K1 reports it too large with this
+                    // batch. Its rest in the batches that follow is skipped like the rest of a held
+                    // trace that outgrew L, so the trace is counted once and no piece of it is joined
+                    cs->tid = tn;
+                    cs->n = 0;
+                    cs->verify = 0;
+                    cs->dropped = 1;
+                } else if (continues) {
+                    // (the leading run ends at or before the last run's start unless the batch is one run)
                     const uint64_t ls = (lead != kUnknown && lead > last_start) ? lead : last_start;
                     if (ls < n) {
                         cs->tail_lo = ls;
