@@ -198,12 +198,50 @@ zk_status   zk_ingest_dev_spans_multi(zk_ingest_dev* ing, uint32_t nb, const uin
                                       const uint64_t* const* offsets, const uint64_t* ns, uint32_t codec,
                                       uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
                                       uint64_t* n_rejected, zk_ingest_items* items);
+/* zk_ingest_dev_spans(_items) / zk_ingest_dev_spans_multi that also write the annotation index's entries
+ * (zkannindex.h) to the five DEVICE columns of `ix`: zk_ingest_spans_indexed on the device, so stored
+ * bytes reach zk_ax_observe (ZK_BATCH_DEVICE_PTRS) without leaving HBM. Records, rejection, dictionaries,
+ * `items` (may be NULL: none) and ZK_INGEST_SPAN_NAMES behave exactly as in those calls for the same
+ * arguments. ix, or any of its five columns, NULL: ZK_ERR_INVALID_ARG before any device is touched.
+ *   - Which spans give which entries is zk_ingest_spans_indexed's rule, word for word (accepted, at least
+ *     one annotation, shouldIndex evaluated exactly unless ZK_INGEST_NO_CLIENT_RULE; time entries from
+ *     the non-core annotations grouped by value, the group's minimum under the 32-bit truncated compare,
+ *     the first of equals, only if it has a host; binary entries from every binary annotation with a
+ *     host, an absent key or value hashing as ""; an absent or empty host name is "Unknown service
+ *     name"), on the wire forms documented above.
+ *   - Order: the host decoder's. Record order; within a record the time entries first, by first
+ *     occurrence of their value, then the binary entries in order. (Stronger than the items' "no
+ *     particular order": the output is reproducible, and ZK_ERR_CAPACITY leaves a defined prefix.)
+ *   - ix->cap too small: ZK_ERR_CAPACITY; the records and the first cap entries are written, ix->n = cap.
+ *   - `service` is this decoder's id of the entry's own host. An entry's host enters the service
+ *     dictionary like an item's host does (ids in slot order: compare through names). More names than
+ *     max_services: ZK_ERR_SERVICE_RANGE; two names with one hash: ZK_ERR_INVALID_SPAN; both with
+ *     ix->n = 0. A strict-mode failure or a span-name overflow returns before any entry is written
+ *     (ix->n = 0).
+ *   - The entries capture no strings (a query hashes its own): zk_ingest_dev_string is untouched by them.
+ * The entries come from an index pass of its own after the batch's decode (count -> scan -> write over
+ * slices of fragments whose decompressed Spans fit the Snappy scratch, which grows only for a fragment
+ * larger than all of it); the decode kernels are those of the calls above. */
+zk_status   zk_ingest_dev_spans_indexed(zk_ingest_dev* ing, const uint8_t* buf, const uint64_t* offsets, uint64_t n,
+                                        uint32_t codec, uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
+                                        uint64_t* n_rejected, zk_ingest_items* items /* may be NULL */,
+                                        zk_ingest_index_items* ix);
+zk_status   zk_ingest_dev_spans_multi_indexed(zk_ingest_dev* ing, uint32_t nb, const uint8_t* const* bufs,
+                                              const uint64_t* const* offsets, const uint64_t* ns, uint32_t codec,
+                                              uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
+                                              uint64_t* n_rejected, zk_ingest_items* items, zk_ingest_index_items* ix);
+/* the last index pass of this decoder: the device time between its first and last launch (ms), and the
+   slices it ran in (0 / 0 before the first indexed call) */
+zk_status   zk_ingest_dev_index_stats(const zk_ingest_dev* ing, double* pass_ms, uint64_t* slices);
 /* the string behind a key / value hash an items batch of this decoder has seen (two-phase) */
 zk_status   zk_ingest_dev_string(const zk_ingest_dev* ing, uint64_t hash, char* buf, uint64_t cap, uint64_t* len);
 zk_status   zk_ingest_dev_num_services(const zk_ingest_dev* ing, uint32_t* n);
 /* Snappy scratch (deferred fragments' Spans, names not yet in the dictionary): bump-allocated per
  * batch and grown when a batch runs out (the fragments that missed out are decoded again). `bytes`
- * sets its size from the next batch on; 0 = automatic (max(64 MiB, 24 B per fragment)). */
+ * sets its size from the next batch on; 0 = automatic (max(64 MiB, 24 B per fragment)). The index pass of
+ * the indexed calls lays the decompressed Spans of a slice of fragments out in the same scratch: with
+ * `bytes` set, a slice stays within max(bytes, the batch's largest fragment) even where the decode has
+ * grown the scratch past that. */
 zk_status   zk_ingest_dev_set_scratch(zk_ingest_dev* ing, uint64_t bytes);
 zk_status   zk_ingest_dev_service_name(const zk_ingest_dev* ing, uint32_t id, char* buf, uint64_t cap,
                                        uint64_t* len);

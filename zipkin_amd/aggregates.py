@@ -1108,12 +1108,16 @@ class StoredSpanJob:
                     st[k].close()
             self._dev = None
 
-    def run_device(self, batches, *, indexer: bool = True) -> Optional[Dependencies]:
+    def run_device(self, batches, *, indexer: bool = True, annotations=None) -> Optional[Dependencies]:
         """batches: (buf uint8, offsets int64[n + 1], n) torch tensors already in HBM, in row order.
         Decoded on the device into a reused column buffer and accumulated on the same stream, several
         small batches at a time (device_accumulate_records); with `indexer` the decoder's items feed
         the two count-min + top-K sketches batch by batch as in run(). The device objects are kept
-        for the next run (close() frees them)."""
+        for the next run (close() frees them).
+        annotations: an annindex.TraceAnnotationIndex that every decode of the run also feeds (the
+        indexed decode calls: the entries never leave HBM), so it answers getTraceIdsByAnnotation
+        for the run's spans; its service ids are the job decoder's (services = the decoder's names).
+        It must have been created with num_services >= max_services (ValueError before any decode)."""
         import torch
 
         from .columns import DeviceColumns
@@ -1122,6 +1126,21 @@ class StoredSpanJob:
         t0 = time.perf_counter()
         st = self._device_state(indexer)
         stream, dec, ctx, kvs, anns = st["stream"], st["dec"], st["ctx"], st["kvs"], st["anns"]
+        if annotations is not None and annotations.num_services < dec.max_services:
+            raise ValueError("annotations: an index of %d services cannot take the ids of a decoder of %d"
+                             % (annotations.num_services, dec.max_services))
+        ixkw = {"indexed": True} if annotations is not None else {}
+
+        def decode(fn, *args, **kw):
+            """one decode call -> (cols, rejected); its items into the sketches, its entries into the index
+            (fresh tensors per decode, and the decode waits for its results: observing them is ordered)"""
+            res = fn(*args, snappy=self.snappy, strict=self.strict, items=indexer, **ixkw, **kw)
+            if indexer:
+                items_in(*res[2], *res[3])
+            if annotations is not None and len(res[-1]):
+                annotations.observe(res[-1], sync=False)
+                annotations._held = res[-1]  # (until the index's next synchronising call)
+            return res[0], res[1]
         t1 = time.perf_counter()
         cap = self.device_accumulate_records
         filled = 0
@@ -1157,12 +1176,7 @@ class StoredSpanJob:
             # a kernel that writes them; a lazy iterator makes each batch just before it is read):
             # the job's stream waits for everything queued there
             stream.wait_stream(torch.cuda.current_stream(self.device))
-            if indexer:
-                out, rej, (ks, kh), (as_, ah) = dec.decode_device_many(
-                    group, snappy=self.snappy, strict=self.strict, out=out, items=True)
-                items_in(ks, kh, as_, ah)
-            else:
-                out, rej = dec.decode_device_many(group, snappy=self.snappy, strict=self.strict, out=out)
+            out, rej = decode(dec.decode_device_many, group, out=out)
             self.rejected += rej
             filled += out.n
             group, gn = [], 0
@@ -1183,16 +1197,14 @@ class StoredSpanJob:
                 stream.wait_stream(torch.cuda.current_stream(self.device))
                 if cols is None or cols.capacity < n:
                     cols = None
-                if indexer:
-                    cols, rej, (ks, kh), (as_, ah) = dec.decode_device(
-                        buf, off, n, snappy=self.snappy, strict=self.strict, out=cols, items=True)
-                    items_in(ks, kh, as_, ah)
-                else:
-                    cols, rej = dec.decode_device(buf, off, n, snappy=self.snappy, strict=self.strict, out=cols)
+                cols, rej = decode(dec.decode_device, buf, off, n, out=cols)
                 self.rejected += rej
                 ctx.accumulate(cols, clustered=True, continues=True, verify=self.verify)
             decode_group()
             flush()
+            if annotations is not None:
+                annotations.info()  # (synchronises: the last entry tensors are consumed)
+                annotations._held = None
             t2 = time.perf_counter()
             names = dec.service_names()
             deps = self._finish(ctx, names, st["lh"])

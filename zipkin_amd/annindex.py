@@ -4,7 +4,9 @@ HBM, and the query service's getTraceIds over it and a TraceNameIndex.
 TraceAnnotationIndex keeps one entry (service, key hash, value hash, timestamp, traceId) per indexed
 time annotation and binary annotation, grouped by service, and answers SpanStore.getTraceIdsByAnnotation:
 the newest `limit` trace ids of a service that carry the annotation (and value) at or before end_ts.
-The entries come from SpanDecoder.decode_indexed (zk_ingest_spans_indexed).
+The entries come from SpanDecoder.decode_indexed (zk_ingest_spans_indexed) or, for stored bytes already
+in HBM, from DeviceSpanDecoder.decode_device(indexed=True) (zk_ingest_dev_spans_indexed):
+TraceAnnotationIndex.observe_stored decodes and observes in one step.
 """
 from __future__ import annotations
 
@@ -125,6 +127,7 @@ class TraceAnnotationIndex:
         self.num_services = int(num_services)
         self.services = None if services is None else list(services)
         self.matched = 0  # matching entries of the last getTraceIdsByAnnotation
+        self._held = None  # device entry columns a queued observe may still read (observe_stored)
 
     def _check(self, st: int) -> None:
         if st != _abi.ZK_OK:
@@ -164,6 +167,28 @@ class TraceAnnotationIndex:
         if sync:
             self.info()
 
+    def observe_stored(self, decoder, buf, offsets, n: int, *, snappy: bool = True, strict: bool = True,
+                       client_rule: bool = True):
+        """Decode one batch of STORED fragments already in HBM (buf uint8, offsets int64[n + 1]: torch
+        tensors on the device) with `decoder` (an ingest.DeviceSpanDecoder whose service ids this index
+        takes: num_services >= its max_services) and observe its entries in one step: the twin of
+        GpuRealtimeAggregates.accumulate_stored. No entry column is copied to the host. Returns
+        (cols, rejected, entries_observed). The entry tensors are kept until this handle's next
+        synchronising call (info, trace_ids, compact, expire, observe, observe_stored), as
+        zk_ax_observe's device-pointer rule requires."""
+        import torch
+
+        if self.num_services < decoder.max_services:
+            raise ValueError("an index of %d services cannot take the ids of a decoder of %d"
+                             % (self.num_services, decoder.max_services))
+        torch.cuda.current_stream(self.device).synchronize()  # (the caller's tensors may still be in flight)
+        cols, rejected, entries = decoder.decode_device(buf, offsets, n, snappy=snappy, strict=strict, indexed=True,
+                                                        client_rule=client_rule)
+        if len(entries):
+            self.observe(entries, sync=False)
+        self._held = entries
+        return cols, rejected, len(entries)
+
     def reset(self) -> None:
         """Empty the index (zk_ax_reset)."""
         self._check(self._L.zk_ax_reset(self._h))
@@ -185,6 +210,7 @@ class TraceAnnotationIndex:
         """{"entries", "segments", "bytes"} (zk_ax_info); synchronises."""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self._L.zk_ax_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        self._held = None  # (synchronised: the columns of a queued observe are consumed)
         return {"entries": int(a.value), "segments": int(b.value), "bytes": int(c.value)}
 
     def service_counts(self) -> np.ndarray:

@@ -26,6 +26,10 @@
 // into the flags before D5. Without the flag the kNames = false kernels run: the code before the
 // span names existed.
 //
+// The annotation index's entries (zk_ingest_dev_spans_indexed) come from a pass of its own after D5,
+// k_ing_index_raw / _slices / _count / _write at the end of the kernels: count -> scan -> write over
+// slices of fragments whose Spans fit the scratch. The kernels above it are the same with and without it.
+//
 // Every byte read is bounds-checked: corrupt input marks the fragment undecodable, never faults.
 #include <string.h>
 
@@ -2471,6 +2475,269 @@ __global__ void k_ing_set_rehash(const uint64_t* __restrict__ old, uint64_t n_ol
         slot = (slot + 1) & mask;
 }
 
+// ---- the annotation index's entries (zk_ingest_dev_spans_indexed) --------------------------------
+// A pass of its own after the batch's ordinary decode has succeeded (the decoders above compile to
+// what they were): status, pos, the record columns at their final index and the dictionary exist.
+// The entries are zk_ingest_spans_indexed's (zk_ingest.cpp "indexer items"; CassieSpanStore.scala:
+// 214-244 behind SpanStore.shouldIndex), in its order: count -> scan -> write, one lane per fragment.
+//   k_ing_index_raw    per accepted fragment with an annotation, its decompressed length (0 for the
+//                      thrift codec: read in place); a scan gives scratch offsets, so the Spans of a
+//                      slice of fragments sit side by side in the scratch (no bump counter, no retry)
+//   k_ing_index_slices the slices: the longest runs of fragments whose Spans fit the scratch
+//   k_ing_index_count  per slice: decompress, evaluate shouldIndex, count the fragment's entries;
+//                      an entry host the dictionary does not hold goes to the extra-name list (D3 /
+//                      D4 of the items path run over it before the slice's scratch is reused)
+//   k_ing_index_write  per slice, over the same scratch bytes: entry j of fragment i at
+//                      base + eoff[i] + j (base: the entries of the slices before), the service by
+//                      dictionary lookup, traceId and last timestamp from the record columns
+struct IxArgs {
+    uint64_t lo, hi;             // the slice's fragments
+    uint64_t* raw;               // [n + 1] decompressed bytes the pass needs for fragment i
+    uint64_t* raw_off;           // [n + 1] their exclusive scan
+    uint64_t* cnt;               // [n] entries of fragment i
+    uint64_t* eoff;              // [n] exclusive scan of cnt within the slice
+    unsigned long long* ctl;     // [0] the largest raw [1] / [2] entries before the slice (ping-pong by
+                                 // `parity`) [3] fragments or hosts the pass could not read again
+    uint32_t dropped;            // the records were compacted: fragment i's record is at pos[i], else at i
+    uint32_t client_rule;
+    uint32_t parity;
+    const uint64_t* r_tid;       // the record columns at their final index
+    const int64_t* r_last;
+    const uint32_t* r_flags;
+    uint32_t* o_svc;             // the caller's entry columns
+    uint64_t* o_key;
+    uint64_t* o_val;
+    int64_t* o_ts;
+    uint64_t* o_tid;
+    uint64_t cap;
+};
+
+// the fragment gives entries at all: accepted, and its record has an annotation; *p: its record
+__device__ __forceinline__ bool ix_live(const IngArgs& a, const IxArgs& x, uint64_t i, uint64_t* p) {
+    if (a.status[i] != kStOk) return false;
+    *p = x.dropped ? (uint64_t)a.pos[i] : i;
+    return (x.r_flags[*p] & ZK_F_HAS_ANNOTATIONS) != 0;
+}
+
+__global__ __launch_bounds__(kIngWG) void k_ing_index_raw(IngArgs a, IxArgs x) {
+    const uint64_t i = (uint64_t)blockIdx.x * kIngWG + threadIdx.x;
+    uint32_t raw = 0;
+    uint64_t p;
+    if (i < a.n && a.snappy && ix_live(a, x, i, &p)) {
+        const uint64_t b = a.offsets[i], e = a.ends[i];
+        uint32_t h[5];
+        uint64_t v;
+        head_bytes(a, true, b, e, h);
+        if (head_status(true, b, e, h, &v) == kStOk) raw = (uint32_t)v;  // (<= kMaxRaw; D1 validated it)
+    }
+    if (i < a.n) x.raw[i] = raw;
+    uint32_t m = raw;  // the largest of the wave, one atomic per wave
+    for (int d = 32; d > 0; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d));
+    if (__lane_id() == 0 && m) atomicMax(&x.ctl[0], (unsigned long long)m);
+}
+
+// bounds[k] .. bounds[k + 1]: slice k, the longest run of fragments from bounds[k] whose raw bytes fit
+// `cap` (every fragment fits on its own: the host grows the scratch to the largest first). One thread:
+// a binary search per slice over the scanned lengths.
+__global__ void k_ing_index_slices(const uint64_t* __restrict__ raw_off, uint64_t n, uint64_t cap,
+                                   uint64_t* __restrict__ bounds, uint32_t max_slices, uint32_t* __restrict__ n_slices) {
+    if (blockIdx.x || threadIdx.x) return;
+    uint64_t lo = 0;
+    uint32_t k = 0;
+    bounds[0] = 0;
+    while (lo < n && k < max_slices) {
+        uint64_t l = lo + 1, h = n;
+        while (l < h) {
+            const uint64_t mid = l + (h - l + 1) / 2;
+            if (raw_off[mid] - raw_off[lo] <= cap)
+                l = mid;
+            else
+                h = mid - 1;
+        }
+        bounds[++k] = l;
+        lo = l;
+    }
+    *n_slices = lo == n ? k : 0u;  // (0: more slices than the host allowed for; it sized for the worst case)
+}
+
+template <class P>
+struct IxBann {  // a binary annotation as the index reads it: GBann and the value
+    P k;
+    uint32_t kl;
+    P v;
+    uint32_t vl;
+    bool host;
+    P hn;
+    uint32_t hl;
+};
+template <class P>
+__device__ bool ix_next_bann(GItemIter<P>& it, IxBann<P>& B) {
+    if (!it.next_elem()) return false;
+    B.k = nullptr;
+    B.kl = 0;
+    B.v = nullptr;
+    B.vl = 0;
+    B.host = false;
+    B.hn = nullptr;
+    B.hl = 0;
+    for (;;) {
+        uint8_t bt;
+        int16_t bid;
+        if (!it.r.field(&bt, &bid)) break;
+        if (bid == 1 && bt == T_STRING)
+            it.r.str(&B.k, &B.kl);
+        else if (bid == 2 && bt == T_STRING)
+            it.r.str(&B.v, &B.vl);
+        else if (bid == 4 && bt == T_STRUCT) {
+            B.host = true;
+            read_endpoint(it.r, &B.hn, &B.hl);
+        } else
+            skip_flat(it.r, bt);
+    }
+    return it.r.ok;
+}
+
+// the host service name is "client", ASCII-lowercased (zk_ingest.cpp is_client_name)
+__device__ __forceinline__ bool ix_is_client(const uint8_t* s, uint32_t l) {
+    if (!s || l != 6) return false;
+    const char c[7] = "client";
+    bool eq = true;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) eq &= (uint8_t)(s[k] | 0x20) == (uint8_t)c[k];
+    return eq;
+}
+
+// one entry of a host (hn / hl; absent or "" -> kUnknown). Count: a host the dictionary does not hold
+// is listed for D3 / D4 (its bytes are global memory that lives until they have run: the slice's
+// scratch, the input buffer or the arena). Write: the entry at `at` when that is below the capacity.
+template <bool kWrite>
+__device__ __forceinline__ void ix_entry(const IngArgs& a, const IxArgs& x, const uint8_t* hn, uint32_t hl, uint64_t key,
+                                         uint64_t val, int64_t ts, uint64_t tid, uint64_t at) {
+    if (!hn || hl == 0) {
+        hn = a.unknown;
+        hl = kUnknownLen;
+    }
+    uint64_t h;
+    uint32_t id = kNoId;
+    const bool found = resolve16_id(a, hn, hl, &h, &id);
+    if constexpr (kWrite) {
+        if (!found) atomicAdd(&x.ctl[3], 1ull);
+        if (at < x.cap) {
+            x.o_svc[at] = id;
+            x.o_key[at] = key;
+            x.o_val[at] = val;
+            x.o_ts[at] = ts;
+            x.o_tid[at] = tid;
+        }
+    } else if (!found) {
+        const unsigned long long q = atomicAdd(&a.icnt[3], 1ull);
+        if (q < a.x_cap) {  // (past it the host sees the count, grows the list and counts the slice again)
+            a.x_hash[q] = h;
+            a.x_ptr[q] = (uint64_t)(uintptr_t)hn;
+            a.x_len[q] = hl;
+            a.x_keep[q] = 1u;
+            a.x_status[q] = kStOk;
+            a.x_list[q] = (uint32_t)q;
+        }
+    }
+}
+
+// The entries of one Span at [src, src + len) (bytes the decoder accepted), in the host decoder's
+// order; returns their number. The generic walk of the items path (GItemIter), with the host
+// decoder's semantics: time entries from the non-core annotations grouped by value (the group's
+// minimum under the truncated compare, the first of equals, only if it has a host), then one entry
+// per binary annotation with a host.
+template <bool kWrite>
+__device__ uint32_t ix_walk(const IngArgs& a, const IxArgs& x, const uint8_t* src, uint64_t len, uint64_t at,
+                            int64_t last, uint64_t tid) {
+    typedef const uint8_t* P;
+    const GItemIter<P> head{DRdT<P>{src, src + len, true}, 0, 6};
+    GAnn<P> A, B;
+    int c;
+    {  // indexed at all: an annotation (CassieSpanStore.scala:214-218), and shouldIndex
+        GItemIter<P> z = head;
+        uint32_t nann = 0;
+        bool client_side = false, client_host = false;
+        while (z.next(A)) {
+            ++nann;
+            if (is_core(A.v, A.vl, &c) && c < 2) client_side = true;
+            if (A.host && ix_is_client((const uint8_t*)A.hn, A.hl)) client_host = true;
+        }
+        if (nann == 0 || (x.client_rule && client_side && client_host)) return 0;
+    }
+    uint32_t m = 0;
+    GItemIter<P> o = head;
+    for (uint32_t k = 0; o.next(A); ++k) {
+        if (is_core(A.v, A.vl, &c)) continue;
+        bool rep = true;  // the first of its value?
+        GItemIter<P> e = head;
+        for (uint32_t j = 0; j < k && e.next(B); ++j)
+            if (!is_core(B.v, B.vl, &c) && g_same_value(A, B)) {
+                rep = false;
+                break;
+            }
+        if (!rep) continue;
+        GAnn<P> M = A;  // the group's minimum
+        GItemIter<P> l = o;
+        while (l.next(B))
+            if (!is_core(B.v, B.vl, &c) && g_same_value(A, B) && (int32_t)(uint32_t)((uint64_t)M.ts - (uint64_t)B.ts) > 0)
+                M = B;
+        if (!M.host) continue;
+        ix_entry<kWrite>(a, x, (const uint8_t*)M.hn, M.hl, kWrite ? d_hash((const uint8_t*)A.v, A.v ? A.vl : 0u) : 0ull, 0ull,
+                         M.ts, tid, at + m);
+        ++m;
+    }
+    GItemIter<P> b{DRdT<P>{src, src + len, true}, 0, 8};
+    IxBann<P> K;
+    while (ix_next_bann(b, K)) {
+        if (!K.host) continue;
+        ix_entry<kWrite>(a, x, (const uint8_t*)K.hn, K.hl, kWrite ? d_hash((const uint8_t*)K.k, K.k ? K.kl : 0u) : 0ull,
+                         kWrite ? (d_hash((const uint8_t*)K.v, K.v ? K.vl : 0u) | 1ull) : 0ull, last, tid, at + m);
+        ++m;
+    }
+    return m;
+}
+
+// fragment i's Span for the pass: in place (thrift), or its slot of the slice's scratch
+__device__ __forceinline__ const uint8_t* ix_span(const IngArgs& a, const IxArgs& x, uint64_t i, uint64_t* len) {
+    if (!a.snappy) {
+        *len = a.ends[i] - a.offsets[i];
+        return a.buf + a.offsets[i];
+    }
+    *len = x.raw[i];
+    return a.scratch + (x.raw_off[i] - x.raw_off[x.lo]);
+}
+
+__global__ __launch_bounds__(kIngWG) void k_ing_index_count(IngArgs a, IxArgs x) {
+    const uint64_t i = x.lo + (uint64_t)blockIdx.x * kIngWG + threadIdx.x;
+    if (i >= x.hi) return;
+    uint64_t p, len, n = 0;
+    if (ix_live(a, x, i, &p)) {
+        const uint8_t* src = ix_span(a, x, i, &len);
+        bool ok = true;
+        if (a.snappy) {
+            const uint64_t so = x.raw_off[i] - x.raw_off[x.lo];
+            ok = len > 0 && so + len <= a.scratch_cap &&
+                 snappy_block(a.buf + a.offsets[i], a.ends[i] - a.offsets[i], a.scratch + so, len);
+            if (!ok) atomicAdd(&x.ctl[3], 1ull);  // (the decoder read these bytes: never taken)
+        }
+        if (ok) n = ix_walk<false>(a, x, src, len, 0, 0, 0);
+    }
+    x.cnt[i] = n;
+}
+
+__global__ __launch_bounds__(kIngWG) void k_ing_index_write(IngArgs a, IxArgs x) {
+    const uint64_t i = x.lo + (uint64_t)blockIdx.x * kIngWG + threadIdx.x;
+    if (i >= x.hi) return;
+    const uint64_t base = x.ctl[1 + x.parity], n = x.cnt[i], at = base + x.eoff[i];
+    if (i == x.hi - 1) x.ctl[1 + (x.parity ^ 1u)] = at + n;  // the entries before the next slice
+    if (n == 0) return;
+    uint64_t p, len;
+    if (!ix_live(a, x, i, &p)) return;
+    const uint8_t* src = ix_span(a, x, i, &len);
+    ix_walk<true>(a, x, src, len, at, x.r_last[p], x.r_tid[p]);
+}
+
 }  // namespace
 }  // namespace zk
 
@@ -2524,6 +2791,12 @@ struct zk_ingest_dev : zk_ing_dict {  // (the base: the service dictionary)
     uint64_t istage_cap = 0;
     uint8_t* multi = nullptr;   // zk_ingest_dev_spans_multi: the batch table, then starts / ends [n]
     uint64_t multi_cap = 0;
+    // the index pass (zk_ingest_dev_spans_indexed)
+    unsigned long long* ix_ctl = nullptr;  // IxArgs::ctl [8], then the slice bounds
+    uint64_t ix_ctl_cap = 0;               // slice bounds the buffer holds
+    hipEvent_t ix_ev[2] = {nullptr, nullptr};  // around the last pass
+    bool ix_timed = false;
+    uint64_t ix_slices = 0;                // slices of the last pass
     std::string err;
 };
 
@@ -2649,6 +2922,9 @@ zk_status zk_ingest_dev_destroy(zk_ingest_dev* g) {
     hipFree(g->xs);
     hipFree(g->istage);
     hipFree(g->multi);
+    hipFree(g->ix_ctl);
+    for (hipEvent_t e : g->ix_ev)
+        if (e) hipEventDestroy(e);
     if (g->own_stream && g->stream) hipStreamDestroy(g->stream);
     delete g;
     return ZK_OK;
@@ -2865,9 +3141,19 @@ zk_status dict_assign_ids(zk_ingest_dev* g, zk_ing_dict* d, hipStream_t s, std::
     return ZK_OK;
 }
 
+// What a finished decode leaves for the index pass (zk_ingest_dev_spans_indexed): the batch's
+// arguments (status, pos, extents, dictionary), whether the records were compacted, and four 8-byte
+// per-fragment arrays of the batch buffer that D5 is done with.
+struct IngBatchState {
+    bool done = false;  // the records are written (the decode returned ZK_OK, or only its items ran short)
+    bool dropped = false;
+    IngArgs a;
+    uint64_t* w[4];
+};
+
 zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
                        uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
-                       zk_ingest_items* items, const uint64_t* ends = nullptr) {
+                       zk_ingest_items* items, const uint64_t* ends = nullptr, IngBatchState* bs = nullptr) {
     if (!g || !n_out || !n_rejected) return ZK_ERR_INVALID_ARG;
     *n_out = *n_rejected = 0;
     if (items) items->kv_n = items->ann_n = 0;
@@ -3254,6 +3540,15 @@ zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* off
     }
     *n_out = kept;
     *n_rejected = bad;
+    if (bs) {
+        bs->done = true;
+        bs->dropped = dropped != 0;
+        bs->a = a;
+        bs->w[0] = (uint64_t*)tmp.trace_id;
+        bs->w[1] = (uint64_t*)tmp.span_id;
+        bs->w[2] = (uint64_t*)tmp.parent_id;
+        bs->w[3] = (uint64_t*)tmp.first_ts;
+    }
     if (items) {
         items->kv_n = nkv;
         items->ann_n = nan;
@@ -3268,7 +3563,7 @@ zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* off
 // one decode over all of them
 zk_status ingest_multi(zk_ingest_dev* g, uint32_t nb, const uint8_t* const* bufs, const uint64_t* const* offsets,
                        const uint64_t* ns, uint32_t codec, uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
-                       uint64_t* n_rejected, zk_ingest_items* items) {
+                       uint64_t* n_rejected, zk_ingest_items* items, IngBatchState* bs = nullptr) {
     if (!g || !n_out || !n_rejected) return ZK_ERR_INVALID_ARG;
     *n_out = *n_rejected = 0;
     if (items) items->kv_n = items->ann_n = 0;
@@ -3289,7 +3584,7 @@ zk_status ingest_multi(zk_ingest_dev* g, uint32_t nb, const uint8_t* const* bufs
     }
     if (n == 0) return ZK_OK;
     if (only < nb)  // one batch: its own extents
-        return ingest_batch(g, bufs[only], offsets[only], ns[only], codec, flags, out, n_out, n_rejected, items);
+        return ingest_batch(g, bufs[only], offsets[only], ns[only], codec, flags, out, n_out, n_rejected, items, nullptr, bs);
     ING_HIP(g, hipSetDevice(g->device));
     const uint64_t tab_bytes = align256((uint64_t)nb * sizeof(IngMultiBatch));
     const uint64_t need = tab_bytes + 2 * align256(8 * n);
@@ -3316,8 +3611,186 @@ zk_status ingest_multi(zk_ingest_dev* g, uint32_t nb, const uint8_t* const* bufs
     ING_HIP(g, hipMemcpyAsync(dtab, tab.data(), (uint64_t)nb * sizeof(IngMultiBatch), hipMemcpyHostToDevice, g->stream));
     ING_HIP(g, launch_checked("k_ing_multi_bounds", k_ing_multi_bounds, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                               g->stream, (const IngMultiBatch*)dtab, nb, n, starts, ends));
-    const zk_status st = ingest_batch(g, (const uint8_t*)base, starts, n, codec, flags, out, n_out, n_rejected, items, ends);
+    const zk_status st = ingest_batch(g, (const uint8_t*)base, starts, n, codec, flags, out, n_out, n_rejected, items, ends, bs);
     if (st != ZK_OK) hipStreamSynchronize(g->stream);  // (an early error return: the table copy is done)
+    return st;
+}
+
+// IxArgs::ctl and, behind it, room for `slices` + 1 slice bounds and their count
+hipError_t size_ix_ctl(zk_ingest_dev* g, uint64_t slices) {
+    if (g->ix_ctl && slices <= g->ix_ctl_cap) return hipSuccess;
+    hipFree(g->ix_ctl);
+    g->ix_ctl = nullptr;
+    g->ix_ctl_cap = 0;
+    const hipError_t e = hipMalloc(&g->ix_ctl, (8 + slices + 2) * 8);
+    if (e == hipSuccess) g->ix_ctl_cap = slices;
+    return e;
+}
+
+// The index pass over a decoded batch (the kernels' comment above IxArgs): the entries of the
+// accepted fragments into the device columns of ix, in the host decoder's order. The stream is idle
+// when this starts (the decode waits for its results) and when it returns.
+zk_status index_pass(zk_ingest_dev* g, const IngBatchState& bs, uint32_t flags, const zk_span_cols* out,
+                     zk_ingest_index_items* ix) {
+    IngArgs a = bs.a;
+    const uint64_t n = a.n, n1 = n + 1;
+    hipStream_t s = g->stream;
+    ING_HIP(g, hipSetDevice(g->device));
+    for (hipEvent_t& e : g->ix_ev)
+        if (!e) ING_HIP(g, hipEventCreate(&e));
+    g->ix_timed = false;
+    g->ix_slices = 0;
+    ING_HIP(g, size_ix_ctl(g, 1));
+    if (!g->xs) ING_HIP(g, size_extra(g, 4096, 0));  // (the items path sizes it only when it runs)
+    IxArgs x{};
+    x.raw = bs.w[0];
+    x.raw_off = bs.w[1];
+    x.cnt = bs.w[2];
+    x.eoff = bs.w[3];
+    x.ctl = g->ix_ctl;
+    x.dropped = bs.dropped ? 1u : 0u;
+    x.client_rule = (flags & ZK_INGEST_NO_CLIENT_RULE) ? 0u : 1u;
+    x.r_tid = (const uint64_t*)out->trace_id;
+    x.r_last = (const int64_t*)out->last_ts;
+    x.r_flags = (const uint32_t*)out->flags;
+    x.o_svc = ix->service;
+    x.o_key = ix->key;
+    x.o_val = ix->val;
+    x.o_ts = ix->ts;
+    x.o_tid = ix->trace_id;
+    x.cap = ix->cap;
+    a.scratch = g->scratch;
+    a.scratch_cap = g->scratch_cap;
+    a.unknown = g->arena;
+    const dim3 blk(kIngWG);
+    ING_HIP(g, hipEventRecord(g->ix_ev[0], s));
+    ING_HIP(g, hipMemsetAsync(x.ctl, 0, 8 * 8, s));
+    ING_HIP(g, hipMemsetAsync(a.icnt + 3, 0, 4 * 8, s));
+    ING_HIP(g, hipMemsetAsync(x.raw + n, 0, 8, s));
+    ING_HIP(g, launch_checked("k_ing_index_raw", k_ing_index_raw, dim3((unsigned)((n + kIngWG - 1) / kIngWG)), blk, 0, s, a, x));
+    size_t need = 0;
+    ING_HIP(g, hipcub::DeviceScan::ExclusiveSum(nullptr, need, x.raw, x.raw_off, (int)n1, s));
+    if (need > g->cub_cap) {
+        hipFree(g->cub);
+        g->cub = nullptr;
+        g->cub_cap = 0;
+        ING_HIP(g, hipMalloc(&g->cub, need));
+        g->cub_cap = need;
+    }
+    ING_HIP(g, hipcub::DeviceScan::ExclusiveSum(g->cub, need, x.raw, x.raw_off, (int)n1, s));
+    unsigned long long* const hc = g->h_counts;
+    ING_HIP(g, hipMemcpyAsync(hc, x.raw_off + n, 8, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipMemcpyAsync(hc + 1, x.ctl, 8, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipStreamSynchronize(s));
+    const uint64_t total_raw = hc[0], max_raw = hc[1];
+    // the slices: everything at once when the batch's Spans fit the scratch (always, for the thrift
+    // codec); the scratch grows only for a fragment larger than all of it
+    std::vector<uint64_t> bounds{0, n};
+    if (a.snappy && total_raw) {
+        if (max_raw > g->scratch_cap) {
+            hipFree(g->scratch);
+            g->scratch = nullptr;
+            g->scratch_cap = 0;
+            ING_HIP(g, hipMalloc(&g->scratch, max_raw));
+            g->scratch_cap = max_raw;
+        }
+        // the bytes alive at once: the scratch as it is, or the size zk_ingest_dev_set_scratch asked for
+        // when the decode has grown it past that (at least the largest fragment either way)
+        uint64_t budget = g->scratch_cap;
+        if (g->scratch_min) budget = std::min(budget, std::max(g->scratch_min, max_raw));
+        a.scratch = g->scratch;
+        a.scratch_cap = budget;
+        if (total_raw > budget) {
+            // two greedy slices in a row hold more than one budget: at most 2 total / budget + 1 of them
+            const uint64_t ms = 2 * (total_raw / budget) + 2;
+            ING_HIP(g, size_ix_ctl(g, ms));
+            x.ctl = g->ix_ctl;
+            ING_HIP(g, hipMemsetAsync(x.ctl, 0, 8 * 8, s));
+            uint64_t* const db = (uint64_t*)(g->ix_ctl + 8);
+            uint32_t* const dn = (uint32_t*)(db + ms + 1);
+            ING_HIP(g, launch_checked("k_ing_index_slices", k_ing_index_slices, dim3(1), dim3(64), 0, s,
+                                      (const uint64_t*)x.raw_off, n, budget, db, (uint32_t)std::min<uint64_t>(ms, 0xFFFFFFFFull), dn));
+            ING_HIP(g, hipMemcpyAsync(hc, dn, 4, hipMemcpyDeviceToHost, s));
+            ING_HIP(g, hipStreamSynchronize(s));
+            const uint32_t k = *(const uint32_t*)hc;
+            if (!k) return dfail(g, ZK_ERR_HIP, "index pass: the slices of the batch could not be laid out");
+            bounds.resize((size_t)k + 1);
+            ING_HIP(g, hipMemcpyAsync(bounds.data(), db, ((size_t)k + 1) * 8, hipMemcpyDeviceToHost, s));
+            ING_HIP(g, hipStreamSynchronize(s));
+        }
+    }
+    std::vector<uint8_t*> retired;  // old arenas stay valid until the pass is done
+    auto leave = [&](zk_status st, const std::string& m) {
+        for (uint8_t* r : retired) hipFree(r);
+        return dfail(g, st, m);
+    };
+    const dim3 xgrid(64);
+    IngArgs ax{};
+    uint32_t parity = 0;
+    for (size_t k = 0; k + 1 < bounds.size();) {
+        x.lo = bounds[k];
+        x.hi = bounds[k + 1];
+        x.parity = parity;
+        const uint64_t m = x.hi - x.lo;
+        const dim3 grid((unsigned)((m + kIngWG - 1) / kIngWG));
+        bind_items(g, a, ax);
+        ING_HIP(g, hipMemsetAsync(a.icnt + 3, 0, 8, s));
+        ING_HIP(g, launch_checked("k_ing_index_count", k_ing_index_count, grid, blk, 0, s, a, x));
+        ING_HIP(g, hipMemcpyAsync(hc, a.icnt + 3, 8, hipMemcpyDeviceToHost, s));
+        ING_HIP(g, hipStreamSynchronize(s));
+        const uint64_t extra = hc[0];
+        if (extra > g->x_cap) {  // the extra-name list is too short for this slice: a longer one, and again
+            ING_HIP(g, size_extra(g, std::max<uint64_t>(2 * g->x_cap, 2 * extra), 0));
+            continue;
+        }
+        if (extra) {
+            // the entry hosts that are new names: D3, ids in slot order, D4 (exact bytes, range), before
+            // the next slice takes the scratch their bytes may lie in
+            ING_HIP(g, launch_checked("k_ing_dict_insert_x", k_ing_dict_insert_x, xgrid, blk, 0, s, ax));
+            const zk_status st = dict_assign_ids(g, g, s, retired, 0, nullptr);
+            if (st != ZK_OK) return leave(st, g->err);
+            a.unknown = g->arena;
+            ING_HIP(g, launch_checked("k_ing_lookup_x", k_ing_lookup_x, xgrid, blk, 0, s, ax));
+            ING_HIP(g, hipMemsetAsync(a.icnt + 5, 0, 2 * 8, s));
+            ING_HIP(g, launch_checked("k_ing_count_extra", k_ing_count_extra, xgrid, blk, 0, s, ax));
+            ING_HIP(g, hipMemcpyAsync(hc, a.icnt + 5, 2 * 8, hipMemcpyDeviceToHost, s));
+            ING_HIP(g, hipStreamSynchronize(s));
+            if (hc[0]) return leave(ZK_ERR_INVALID_SPAN, "two service names (an entry's host) share a 64-bit hash");
+            if (hc[1]) return leave(ZK_ERR_SERVICE_RANGE, "more distinct service names than max_services");
+        }
+        ING_HIP(g, hipcub::DeviceScan::ExclusiveSum(g->cub, need, x.cnt + x.lo, x.eoff + x.lo, (int)m, s));
+        ING_HIP(g, launch_checked("k_ing_index_write", k_ing_index_write, grid, blk, 0, s, a, x));
+        parity ^= 1u;
+        ++k;
+    }
+    ING_HIP(g, hipEventRecord(g->ix_ev[1], s));
+    ING_HIP(g, hipMemcpyAsync(hc, x.ctl + 1 + parity, 8, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipMemcpyAsync(hc + 1, x.ctl + 3, 8, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipStreamSynchronize(s));
+    g->ix_timed = true;
+    g->ix_slices = bounds.size() - 1;
+    const uint64_t total = hc[0];
+    if (hc[1]) return leave(ZK_ERR_HIP, "index pass: " + std::to_string(hc[1]) + " fragments or hosts could not be read again");
+    for (uint8_t* r : retired) hipFree(r);
+    ix->n = std::min<uint64_t>(total, ix->cap);
+    if (total > ix->cap)
+        return dfail(g, ZK_ERR_CAPACITY, "index entry buffers too small: " + std::to_string(total) + " entries");
+    return ZK_OK;
+}
+
+bool ix_valid(const zk_ingest_index_items* ix) {
+    return ix && ix->service && ix->key && ix->val && ix->ts && ix->trace_id;
+}
+
+// after the decode of an indexed call: the index pass when the records are written (the decode
+// returned ZK_OK, or ZK_ERR_CAPACITY because only its items ran short, which is then still returned)
+zk_status finish_indexed(zk_ingest_dev* g, zk_status st, const IngBatchState& bs, uint32_t flags, const zk_span_cols* out,
+                         zk_ingest_index_items* ix) {
+    if (!bs.done || (st != ZK_OK && st != ZK_ERR_CAPACITY)) return st;
+    const std::string item_err = g->err;
+    const zk_status si = index_pass(g, bs, flags, out, ix);
+    if (si != ZK_OK) return si;
+    if (st != ZK_OK) g->err = item_err;
     return st;
 }
 
@@ -3348,6 +3821,45 @@ zk_status zk_ingest_dev_spans_items(zk_ingest_dev* g, const uint8_t* buf, const 
     ZK_GUARD_BEGIN
     if (!items) return ZK_ERR_INVALID_ARG;
     return ingest_batch(g, buf, offsets, n, codec, flags, out, n_out, n_rejected, items);
+    ZK_GUARD_END
+}
+
+zk_status zk_ingest_dev_spans_indexed(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* offsets, uint64_t n,
+                                      uint32_t codec, uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
+                                      uint64_t* n_rejected, zk_ingest_items* items, zk_ingest_index_items* ix) {
+    ZK_GUARD_BEGIN
+    if (!g || !ix_valid(ix)) return ZK_ERR_INVALID_ARG;  // (before any device is touched)
+    ix->n = 0;
+    IngBatchState bs;
+    const zk_status st = ingest_batch(g, buf, offsets, n, codec, flags, out, n_out, n_rejected, items, nullptr, &bs);
+    return finish_indexed(g, st, bs, flags, out, ix);
+    ZK_GUARD_END
+}
+
+zk_status zk_ingest_dev_spans_multi_indexed(zk_ingest_dev* g, uint32_t nb, const uint8_t* const* bufs,
+                                            const uint64_t* const* offsets, const uint64_t* ns, uint32_t codec,
+                                            uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
+                                            uint64_t* n_rejected, zk_ingest_items* items, zk_ingest_index_items* ix) {
+    ZK_GUARD_BEGIN
+    if (!g || !ix_valid(ix)) return ZK_ERR_INVALID_ARG;
+    ix->n = 0;
+    IngBatchState bs;
+    const zk_status st = ingest_multi(g, nb, bufs, offsets, ns, codec, flags, out, n_out, n_rejected, items, &bs);
+    return finish_indexed(g, st, bs, flags, out, ix);
+    ZK_GUARD_END
+}
+
+zk_status zk_ingest_dev_index_stats(const zk_ingest_dev* g, double* pass_ms, uint64_t* slices) {
+    ZK_GUARD_BEGIN
+    if (!g || !pass_ms || !slices) return ZK_ERR_INVALID_ARG;
+    *pass_ms = 0.0;
+    *slices = g->ix_slices;
+    if (g->ix_timed) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, g->ix_ev[0], g->ix_ev[1]) != hipSuccess) return ZK_ERR_HIP;
+        *pass_ms = ms;
+    }
+    return ZK_OK;
     ZK_GUARD_END
 }
 

@@ -244,29 +244,41 @@ class DeviceSpanDecoder:
             raise _abi.ZkError(st, self._L.zk_ingest_dev_last_error(self._h).decode() or _abi.status_str(st))
 
     def decode_device(self, buf, offsets, n: int, *, snappy: bool = True, strict: bool = True, out=None,
-                      items: bool = False, item_cap: int | None = None, span_names: bool = False):
+                      items: bool = False, item_cap: int | None = None, span_names: bool = False,
+                      indexed: bool = False, client_rule: bool = True, index_cap: int | None = None):
         """-> (DeviceColumns with .n = records written, rejected), or with items=True
         (cols, rejected, (kv_service, kv_key), (ann_service, ann_value)): the span indexer's items as
         device tensors (int32 service ids of this decoder, int64 hashes = uint64 bit patterns), in no
         particular order within the batch (zk_ingest_dev_spans_items). item_cap: the items per kind
         to allow for (default 2n + 16; a batch with more is decoded again with 4x the room).
-        span_names: ZK_INGEST_SPAN_NAMES (a decoder made with max_span_names > 0)."""
+        span_names: ZK_INGEST_SPAN_NAMES (a decoder made with max_span_names > 0).
+        indexed=True (zk_ingest_dev_spans_indexed) appends the annotation index's entries, an
+        annindex.DeviceAnnotationItems in the host decoder's order, to the result: (cols, rejected,
+        entries), or after the two item pairs with items=True. client_rule=False emits the entries of
+        a client-side span of the service "client" too (ZK_INGEST_NO_CLIENT_RULE). index_cap: the
+        entries to allow for (default 8 per fragment, at least 16; a batch with more is decoded again
+        with 4x the room)."""
         L, h = self._L, self._h
         bp, op = buf.data_ptr(), offsets.data_ptr()
 
-        def call(codec, flags, ab, nout, nrej, it):
+        def call(codec, flags, ab, nout, nrej, it, ix=None):
+            if ix is not None:
+                return L.zk_ingest_dev_spans_indexed(h, bp, op, n, codec, flags, C.byref(ab), C.byref(nout), C.byref(nrej),
+                                                     None if it is None else C.byref(it), C.byref(ix))
             if it is None:
                 return L.zk_ingest_dev_spans(h, bp, op, n, codec, flags, C.byref(ab), C.byref(nout), C.byref(nrej))
             return L.zk_ingest_dev_spans_items(h, bp, op, n, codec, flags, C.byref(ab), C.byref(nout), C.byref(nrej),
                                                C.byref(it))
 
-        return self._run(call, n, snappy, strict, out, items, item_cap, span_names)
+        return self._run(call, n, snappy, strict, out, items, item_cap, span_names, indexed, client_rule, index_cap)
 
     def decode_device_many(self, batches, *, snappy: bool = True, strict: bool = True, out=None,
-                           items: bool = False, item_cap: int | None = None, span_names: bool = False):
+                           items: bool = False, item_cap: int | None = None, span_names: bool = False,
+                           indexed: bool = False, client_rule: bool = True, index_cap: int | None = None):
         """Several HBM-resident batches [(buf, offsets, n), ...] in ONE decode
-        (zk_ingest_dev_spans_multi): the results of decode_device over the batches joined in order,
-        for one set of launches and one host round trip."""
+        (zk_ingest_dev_spans_multi, or zk_ingest_dev_spans_multi_indexed with indexed=True): the
+        results of decode_device over the batches joined in order, for one set of launches and one
+        host round trip."""
         L, h = self._L, self._h
         nb = len(batches)
         n = sum(int(b[2]) for b in batches)
@@ -274,13 +286,17 @@ class DeviceSpanDecoder:
         offs = (C.c_void_p * max(1, nb))(*[b[1].data_ptr() if int(b[2]) else None for b in batches])
         ns = (C.c_uint64 * max(1, nb))(*[int(b[2]) for b in batches])
 
-        def call(codec, flags, ab, nout, nrej, it):
+        def call(codec, flags, ab, nout, nrej, it, ix=None):
+            if ix is not None:
+                return L.zk_ingest_dev_spans_multi_indexed(h, nb, bufs, offs, ns, codec, flags, C.byref(ab), C.byref(nout),
+                                                           C.byref(nrej), None if it is None else C.byref(it), C.byref(ix))
             return L.zk_ingest_dev_spans_multi(h, nb, bufs, offs, ns, codec, flags, C.byref(ab), C.byref(nout),
                                                C.byref(nrej), None if it is None else C.byref(it))
 
-        return self._run(call, n, snappy, strict, out, items, item_cap, span_names)
+        return self._run(call, n, snappy, strict, out, items, item_cap, span_names, indexed, client_rule, index_cap)
 
-    def _run(self, call, n, snappy, strict, out, items, item_cap, span_names=False):
+    def _run(self, call, n, snappy, strict, out, items, item_cap, span_names=False, indexed=False, client_rule=True,
+             index_cap=None):
         import torch
 
         from .columns import DeviceColumns
@@ -291,25 +307,53 @@ class DeviceSpanDecoder:
         ab = cols.abi(n)
         codec = _abi.ZK_CODEC_SNAPPY_THRIFT if snappy else _abi.ZK_CODEC_THRIFT
         flags = (_abi.ZK_INGEST_STRICT if strict else 0) | (_abi.ZK_INGEST_SPAN_NAMES if span_names else 0)
-        if not items:
+        if indexed and not client_rule:
+            flags |= _abi.ZK_INGEST_NO_CLIENT_RULE
+        if not items and not indexed:
             self._check(call(codec, flags, ab, nout, nrej, None))
             cols.n = int(nout.value)
             return cols, int(nrej.value)
         cap = item_cap if item_cap is not None else 2 * n + 16
+        icap = int(index_cap) if index_cap is not None else max(16, 8 * n)
+        it = ix = None
         while True:
-            ks = torch.empty(cap, dtype=torch.int32, device=dev)
-            kh = torch.empty(cap, dtype=torch.int64, device=dev)
-            as_ = torch.empty(cap, dtype=torch.int32, device=dev)
-            ah = torch.empty(cap, dtype=torch.int64, device=dev)
-            it = _abi.zk_ingest_items(ks.data_ptr(), kh.data_ptr(), cap, 0, as_.data_ptr(), ah.data_ptr(), cap, 0)
-            st = call(codec, flags, ab, nout, nrej, it)
-            if st == _abi.ZK_ERR_CAPACITY and (it.kv_n == cap or it.ann_n == cap):
-                cap *= 4  # more items than guessed: the batch again
-                continue
+            if items:
+                ks = torch.empty(cap, dtype=torch.int32, device=dev)
+                kh = torch.empty(cap, dtype=torch.int64, device=dev)
+                as_ = torch.empty(cap, dtype=torch.int32, device=dev)
+                ah = torch.empty(cap, dtype=torch.int64, device=dev)
+                it = _abi.zk_ingest_items(ks.data_ptr(), kh.data_ptr(), cap, 0, as_.data_ptr(), ah.data_ptr(), cap, 0)
+            if indexed:
+                # (fresh tensors per decode: an index that observed the last ones may still read them)
+                ent = [torch.empty(max(1, icap), dtype=torch.int32 if k == 0 else torch.int64, device=dev) for k in range(5)]
+                ix = _abi.zk_ingest_index_items(*[t.data_ptr() for t in ent], icap, 0)
+                st = call(codec, flags, ab, nout, nrej, it, ix)
+            else:
+                st = call(codec, flags, ab, nout, nrej, it)
+            if st == _abi.ZK_ERR_CAPACITY:
+                grow_items = items and (it.kv_n == cap or it.ann_n == cap)
+                grow_index = indexed and ix.n == icap
+                if grow_items or grow_index:  # more items / entries than guessed: the batch again
+                    cap = cap * 4 if grow_items else cap
+                    icap = max(16, icap * 4) if grow_index else icap
+                    continue
             self._check(st)
             break
         cols.n = int(nout.value)
-        return cols, int(nrej.value), (ks[: it.kv_n], kh[: it.kv_n]), (as_[: it.ann_n], ah[: it.ann_n])
+        res = (cols, int(nrej.value))
+        if items:
+            res += ((ks[: it.kv_n], kh[: it.kv_n]), (as_[: it.ann_n], ah[: it.ann_n]))
+        if indexed:
+            from .annindex import DeviceAnnotationItems
+
+            res += (DeviceAnnotationItems(*[t[: ix.n] for t in ent]),)
+        return res
+
+    def index_stats(self) -> dict:
+        """{"pass_ms", "slices"} of the last indexed decode's index pass (zk_ingest_dev_index_stats)."""
+        ms, sl = C.c_double(), C.c_uint64()
+        self._check(self._L.zk_ingest_dev_index_stats(self._h, C.byref(ms), C.byref(sl)))
+        return {"pass_ms": float(ms.value), "slices": int(sl.value)}
 
     def string(self, h: int) -> str:
         """The key / value string behind a hash an items batch has seen (zk_ingest_dev_string);
@@ -327,7 +371,8 @@ class DeviceSpanDecoder:
         return v
 
     def decode(self, blobs: Sequence[bytes], *, snappy: bool = True, strict: bool = True, items: bool = False,
-               span_names: bool = False):
+               span_names: bool = False, indexed: bool = False, client_rule: bool = True,
+               index_cap: int | None = None):
         import torch
 
         dev = f"cuda:{self.device}"
@@ -338,7 +383,7 @@ class DeviceSpanDecoder:
         buf = torch.from_numpy(raw.copy()).to(dev)
         off = torch.from_numpy(offsets).to(dev)
         return self.decode_device(buf, off, len(blobs), snappy=snappy, strict=strict, items=items,
-                                  span_names=span_names)
+                                  span_names=span_names, indexed=indexed, client_rule=client_rule, index_cap=index_cap)
 
     @property
     def num_services(self) -> int:
