@@ -1,0 +1,154 @@
+/*
+ * zkspans.h -- the span store by trace id: tracesExist and getSpansByTraceIds on the device.
+ *
+ * Everything the reference's query service returns about a trace starts from
+ * storage.getSpansByTraceIds(traceIds) (QueryService.scala:286-355: tracesExist, getTracesByIds,
+ * getTraceSummariesByIds; SpanStore.scala:76-84), and a Trace is built from those spans (Trace.scala,
+ * TraceSummary.scala). The trace-id indices (zkindex.h, zkannindex.h) and the duration index
+ * (zkduration.h) hand out trace ids; this handle keeps the 48-B records themselves in HBM, findable by
+ * trace id, and hands the fragments of the asked traces back.
+ *
+ * Semantics
+ *  - EVERY observed fragment is kept, whole: trace_id, span_id, parent_id, first_ts, last_ts,
+ *    service_id, flags. No fragment is filtered (the reference's shouldIndex governs its indices, not
+ *    its span data) and no service-range rule applies: the config has no num_services and service_id may
+ *    be any 32-bit value.
+ *  - The store is a MULTISET of fragments, like InMemorySpanStore's `spans ++= newSpans`: observing a
+ *    batch again adds it again. Batches and records may come in any order; a trace may be spread over
+ *    any number of batches.
+ *  - Legal: traceIds 0 and 2^64 - 1, timestamps at INT64_MIN / INT64_MAX.
+ *  - MEMBERSHIP: a traceId exists exactly when some observed fragment carries it, TIMED OR NOT
+ *    (tracesExist's rule: a row of the trace is there). This is WIDER than zkduration.h's rule, which
+ *    admits a trace only through a timed fragment: a trace of untimed fragments alone exists here, is
+ *    absent there, and has no TraceSummary (TraceSummary.apply yields None).
+ *  - CANONICAL ORDER: the fragments of one trace are returned ascending lexicographically by
+ *    (span_id unsigned, parent_id unsigned, first_ts signed, last_ts signed, service_id, flags); equal
+ *    fragments appear as often as they were entered. Every answer is so a function of the multiset alone.
+ *
+ * Departures from the reference
+ *  - A record carries no endpoint (ip, port): a TraceSummary built from this store has no endpoints.
+ *  - A record carries one service (Span.serviceName's choice), not Span.serviceNames.
+ *  - Nothing expires: the reference keeps span data under a TTL of its own; this store grows until
+ *    zk_sp_reset.
+ *
+ * Layout
+ *  - One zk_sp_observe makes one SEGMENT: the batch's records grouped by BUCKET,
+ *        bucket = zk_mix64(trace_id ^ ZK_SP_SALT) >> 52          (ZK_SP_BUCKETS = 4096 buckets)
+ *    (zk_mix64: the splitmix64 finalizer, z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) *
+ *    0x94D049BB133111EB, z ^ z >> 31), in seven columns, 48 B per entry, each column 256-B aligned. The
+ *    host keeps each segment's offsets[4097]; a copy of them (4 B each) lies behind the segment's columns
+ *    for the lookups. The order inside a bucket's slice is not reproducible.
+ *  - At most ZK_SP_MAX_SEGMENTS segments exist: an observe that would make one more first merges all
+ *    segments into one (each bucket's slices concatenated in segment order into a freshly sized segment,
+ *    then the old ones freed). zk_sp_compact does the same on request.
+ *  - At most 2^32 - 1 entries per handle: a batch that would exceed it is ZK_ERR_CAPACITY and changes
+ *    nothing.
+ *  - A refused allocation is ZK_ERR_CAPACITY and leaves the handle exactly as it was: nothing is freed
+ *    before its replacement is complete.
+ *
+ * Conventions are those of zkduration.h: every entry point returns zk_status; a handle is not
+ * thread-safe; all device work of a handle is ordered on one HIP stream; nothing is allocated before the
+ * first observe. Every call refuses a NULL handle or argument with ZK_ERR_INVALID_ARG before any device
+ * is touched; errors go to zk_sp_last_error.
+ */
+#ifndef ZKSPANS_H
+#define ZKSPANS_H
+
+#include "zkagg.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* the salt of the bucket function (not the ones of zkwindow.h and zkduration.h: the three hash apart) */
+#define ZK_SP_SALT 0x8CB92BA72F3D8DD7ull
+/* buckets of a segment: the 12 highest bits of the salted hash */
+#define ZK_SP_BUCKETS 4096u
+/* the most segments a handle holds */
+#define ZK_SP_MAX_SEGMENTS 64u
+/* the most ids one zk_sp_exist or zk_sp_gather asks */
+#define ZK_SP_MAX_IDS 4096u
+
+typedef struct zk_sp_config {
+    int32_t  device;   /* HIP device ordinal */
+    uint32_t timing;   /* 1: record HIP events (zk_sp_observe_ms, zk_sp_query_ms) */
+    void*    stream;   /* hipStream_t to run on, or NULL for a private stream */
+    uint32_t reserved[8];
+} zk_sp_config;
+
+/* zk_sp_gather's output: seven HOST columns of `cap` entries each */
+typedef struct zk_sp_rows {
+    uint64_t* trace_id;
+    uint64_t* span_id;
+    uint64_t* parent_id;
+    int64_t*  first_ts;
+    int64_t*  last_ts;
+    uint32_t* service_id;
+    uint32_t* flags;
+} zk_sp_rows;
+
+typedef struct zk_sp zk_sp;
+
+zk_status   zk_sp_create(const zk_sp_config* cfg, zk_sp** out);
+zk_status   zk_sp_destroy(zk_sp* sp);
+const char* zk_sp_last_error(const zk_sp* sp);
+
+/* Add a batch's records as one segment. All seven columns of `in` are read. flags:
+   ZK_BATCH_DEVICE_PTRS: `in` holds device pointers; without it `in` is host memory, staged (48 B per
+   record), and the call waits for its staging copy. ZK_BATCH_TRACE_CLUSTERED is accepted and changes
+   nothing. A count kernel over trace_id (8 B per record) builds the 4096-bin histogram; the call
+   synchronises once, to read the counts it sizes the segment by (a merge, see Layout, synchronises once
+   more). The scatter of the seven columns (48 B read and 48 B written per record, trace_id read once
+   more) is queued on the handle's stream behind that: DEVICE columns must stay as they are until the
+   handle's next synchronising call (zk_sp_info, zk_sp_exist, zk_sp_gather, zk_sp_compact,
+   zk_sp_observe). A record whose place falls outside its bucket's slice (it cannot while the columns
+   stay as they were) is dropped, never written elsewhere. n == 0 is ZK_OK; n >= 2^32 is
+   ZK_ERR_UNSUPPORTED. */
+zk_status   zk_sp_observe(zk_sp* sp, const zk_span_cols* in, uint32_t flags);
+/* Empty the store: every segment is freed. */
+zk_status   zk_sp_reset(zk_sp* sp);
+/* Merge all segments into one (see Layout): 48 B read and 48 B written per entry. Fewer than two
+   segments: nothing to do. Synchronises. */
+zk_status   zk_sp_compact(zk_sp* sp);
+/* entries in the store, segments, bytes of HBM the segments hold. Any of the three pointers may be
+   NULL. Synchronises. */
+zk_status   zk_sp_info(zk_sp* sp, uint64_t* entries, uint64_t* segments, uint64_t* bytes);
+/* found[i] = 1 when ids[i] is a member, else 0: answers in the order asked, a duplicated id answered as
+   often as asked.
+     ids     n trace ids: device memory under ZK_BATCH_DEVICE_PTRS (no other flag is accepted), else host.
+     n       1..ZK_SP_MAX_IDS; more is ZK_ERR_INVALID_ARG; 0 is ZK_OK and writes nothing.
+     found   a HOST array of n bytes.
+   One work item per (asked id, segment) reads the trace_id slice of the id's bucket in that segment and
+   nothing else (a slice longer than 4096 entries is split over several workgroups). An empty store
+   answers without a device pass. Synchronises. */
+zk_status   zk_sp_exist(zk_sp* sp, const uint64_t* ids, uint32_t n, uint32_t flags, uint8_t* found);
+/* The fragments of the asked traces.
+     ids, n, flags   as for zk_sp_exist; n == 0 is ZK_OK with *n_out = 0.
+     counts  a HOST array of n entries: counts[i] = the fragments of ids[i] (0: not a member).
+     out     seven HOST columns of `cap` entries each. The rows of ids[0] come first, then those of
+             ids[1], and so on; a duplicated id gets its rows again; inside one trace the rows are in
+             CANONICAL ORDER (the host sorts them). out, or any of its columns, may be NULL only when
+             cap == 0.
+     n_out   the total number of rows, the sum of counts.
+   When cap is below the total the call returns ZK_ERR_CAPACITY with *n_out set to the needed total and
+   counts written; no row is written. cap == 0 with NULL columns is the sizing call.
+   Two device passes: the count pass of zk_sp_exist, one synchronisation and the host's prefix sum, then
+   the write pass, which reads the same slices again and appends every matching row (all seven columns,
+   48 B) behind its asked id's offset, a wave's matches with one atomic. A trace may be of any length:
+   no pass keeps a trace's rows in LDS. Staging for the rows (48 B each) is allocated on first use and
+   grown; a refused allocation is ZK_ERR_CAPACITY. Synchronises. */
+zk_status   zk_sp_gather(zk_sp* sp, const uint64_t* ids, uint32_t n, uint32_t flags, uint32_t* counts,
+                         zk_sp_rows* out, uint64_t cap, uint64_t* n_out);
+/* Device time in ms of the last zk_sp_observe that added a segment: the count, the sizing step (the
+   counts' copy and, when the segment bound was met, the merge), the scatter. Needs zk_sp_config.timing;
+   waits for the scatter. */
+zk_status   zk_sp_observe_ms(zk_sp* sp, double out[3]);
+/* Time in ms on the handle's stream of the last zk_sp_exist or zk_sp_gather that ran a pass, from its
+   first pass to its last copy (the host's prefix sum included, the host's sort not). Needs
+   zk_sp_config.timing. */
+zk_status   zk_sp_query_ms(zk_sp* sp, double* ms);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* ZKSPANS_H */

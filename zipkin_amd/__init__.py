@@ -11,6 +11,7 @@ from .durations import TraceDurationIndex, TraceIdDuration, merge_top  # noqa: F
 from .nameindex import IndexedTraceId, TraceNameIndex, merge_trace_ids  # noqa: F401
 from .annindex import AnnotationItems, DeviceAnnotationItems, TraceAnnotationIndex, get_trace_ids, trace_ids_intersect  # noqa: F401
 from .retention import IndexRetention  # noqa: F401
+from .spanstore import Span, SpanTimestamp, Timespan, Trace, TraceSpanStore, TraceSummary  # noqa: F401
 from .windows import WindowedAggregateJob, WindowPartition  # noqa: F401
 from . import table  # noqa: F401
 
@@ -39,5 +40,11 @@ __all__ = [
     "get_trace_ids",
     "trace_ids_intersect",
     "IndexRetention",
+    "TraceSpanStore",
+    "Trace",
+    "TraceSummary",
+    "Span",
+    "SpanTimestamp",
+    "Timespan",
     "BYTES_PER_RECORD",
 ]

@@ -304,6 +304,33 @@ class zk_ax_config(C.Structure):
     ]
 
 
+ZK_SP_SALT = 0x8CB92BA72F3D8DD7
+ZK_SP_BUCKETS = 4096
+ZK_SP_MAX_SEGMENTS = 64
+ZK_SP_MAX_IDS = 4096
+
+
+class zk_sp_config(C.Structure):
+    _fields_ = [
+        ("device", C.c_int32),
+        ("timing", C.c_uint32),
+        ("stream", C.c_void_p),
+        ("reserved", C.c_uint32 * 8),
+    ]
+
+
+class zk_sp_rows(C.Structure):
+    _fields_ = [
+        ("trace_id", C.c_void_p),
+        ("span_id", C.c_void_p),
+        ("parent_id", C.c_void_p),
+        ("first_ts", C.c_void_p),
+        ("last_ts", C.c_void_p),
+        ("service_id", C.c_void_p),
+        ("flags", C.c_void_p),
+    ]
+
+
 ZK_RT_WITH_DEPS = 0
 ZK_RT_ONLY = 1
 ZK_RL_ANY_RPC = 0xFFFFFFFF
@@ -595,6 +622,18 @@ _SIGNATURES = [
     ("zk_ax_expire_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_ax_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_ax_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    # include/zkspans.h: the span store by trace id
+    ("zk_sp_create", C.c_int, [C.POINTER(zk_sp_config), C.POINTER(_P)]),
+    ("zk_sp_destroy", C.c_int, [_P]),
+    ("zk_sp_last_error", C.c_char_p, [_P]),
+    ("zk_sp_observe", C.c_int, [_P, C.POINTER(zk_span_cols), C.c_uint32]),
+    ("zk_sp_reset", C.c_int, [_P]),
+    ("zk_sp_compact", C.c_int, [_P]),
+    ("zk_sp_info", C.c_int, [_P, _U64P, _U64P, _U64P]),
+    ("zk_sp_exist", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8)]),
+    ("zk_sp_gather", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _U32P, C.POINTER(zk_sp_rows), C.c_uint64, _U64P]),
+    ("zk_sp_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zk_sp_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
 ]
 
 SYMBOLS = [s[0] for s in _SIGNATURES]

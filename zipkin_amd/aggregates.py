@@ -796,16 +796,21 @@ class ZipkinAggregateJob:
     before it is accumulated, so that after run() it answers getTraceIdsByName, getSpanNames and
     getAllServiceNames for the job's spans. The job neither resets nor closes it; None changes nothing.
 
+    spans (a spanstore.TraceSpanStore): likewise every batch is observed into it, synchronously and
+    before it is accumulated, so that after run() it answers tracesExist, getSpansByTraceIds and
+    getTraceSummariesByIds for the job's traces. The job neither resets nor closes it; None changes nothing.
+
     The device context is kept between runs (a scheduled job reuses its buffers); close() frees it.
     """
 
     def __init__(self, services: Dictionary, *, device: int = 0, strict: bool = True,
                  aggregates: Optional[Aggregates] = None, clock=now_us, order: str = "any", verify: bool = True,
-                 link_quantiles: Optional[Sequence[float]] = None, durations=None, names=None):
+                 link_quantiles: Optional[Sequence[float]] = None, durations=None, names=None, spans=None):
         if order not in ("rows", "any"):
             raise ValueError("order is 'rows' or 'any'")
         self.durations = durations  # a durations.TraceDurationIndex, or None
         self.names = names  # a nameindex.TraceNameIndex, or None
+        self.spans = spans  # a spanstore.TraceSpanStore, or None
         self.link_quantiles = None if link_quantiles is None else tuple(float(q) for q in link_quantiles)
         self._lh = None
         self._link_durations: List[LinkDuration] = []
@@ -858,6 +863,8 @@ class ZipkinAggregateJob:
                 self.durations.observe(b, sync=True)
             if self.names is not None:
                 self.names.observe(b, sync=True)
+            if self.spans is not None:
+                self.spans.observe(b, sync=True)
             ctx.accumulate(b, clustered=rows, continues=rows, verify=self.verify)
         return ctx
 

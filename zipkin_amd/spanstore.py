@@ -1,0 +1,398 @@
+"""The span store by trace id (include/zkspans.h): tracesExist, getSpansByTraceIds and trace summaries
+from whole records in HBM.
+
+TraceSpanStore keeps every observed 48-B fragment, grouped by a hash of its trace id, and hands the
+fragments of asked traces back (SpanStore.tracesExist / getSpansByTraceIds). Trace and TraceSummary restate
+the reference's Trace.scala and TraceSummary.scala at record granularity on the host, so that the ids a
+TraceNameIndex, TraceAnnotationIndex or TraceDurationIndex returns become the query service's
+getTraceSummariesByIds without another store.
+
+A trace's fragments travel as a list of ROWS, tuples (trace_id, span_id, parent_id, first_ts, last_ts,
+service_id, flags) of Python ints, in the header's canonical order.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from . import _abi
+from .columns import COLUMNS, DeviceColumns
+
+INT64_MIN, INT64_MAX = -(2 ** 63), 2 ** 63 - 1
+_M64 = 2 ** 64 - 1
+
+Row = Tuple[int, int, int, int, int, int, int]
+
+
+def _wrap64(x: int) -> int:
+    """x as the JVM's Long holds it (two's complement, 64 bits)."""
+    x &= _M64
+    return x - 2 ** 64 if x >= 2 ** 63 else x
+
+
+def _to_int(x: int) -> int:
+    """Long.toInt: the low 32 bits as a signed value."""
+    x &= 0xFFFFFFFF
+    return x - 2 ** 32 if x >= 2 ** 31 else x
+
+
+def canonical_key(row: Row) -> tuple:
+    """The canonical order inside a trace: (span_id, parent_id, first_ts, last_ts, service_id, flags)."""
+    return row[1:]
+
+
+class Span(NamedTuple):
+    """One merged span of a Trace. parent, first, last: None when no fragment has one. name: the span-name
+    id (0: none), or with a span_names dictionary the name (None: none). services: ascending service ids,
+    or with a services dictionary the lower-cased names in the ids' order."""
+    trace_id: int
+    id: int
+    parent: Optional[int]
+    name: Union[int, str, None]
+    first: Optional[int]
+    last: Optional[int]
+    services: tuple
+
+
+class SpanTimestamp(NamedTuple):
+    """The reference's SpanTimestamp(name, startTimestamp, endTimestamp); name is the service."""
+    name: Union[int, str]
+    start_timestamp: int
+    end_timestamp: int
+
+    @property
+    def duration(self) -> int:
+        return _wrap64(self.end_timestamp - self.start_timestamp)
+
+
+class Timespan(NamedTuple):
+    start: int
+    end: int
+
+
+class Trace:
+    """Trace.scala over one trace's rows (in any order; they are put into canonical order first, so every
+    answer is a function of the multiset of rows).
+
+    spans: the fragments merged by span id. A span is timed when any of its fragments is
+    (ZK_F_HAS_ANNOTATIONS); first = the minimum first_ts and last = the maximum last_ts over its TIMED
+    fragments; parent = the parent_id of the first fragment (canonical order) with ZK_F_HAS_PARENT; the
+    name id = the first non-zero one in canonical order; services = the ascending set of service_id over
+    the fragments with ZK_F_SVC_CLIENT | ZK_F_SVC_SERVER. Spans are sorted by first, an untimed span as
+    INT64_MAX (Trace.scala:38-43); ties go by span id ascending as unsigned (the reference's tie order is
+    a HashMap's: a stated choice)."""
+
+    def __init__(self, rows: Sequence[Row], services: Optional[Sequence[str]] = None,
+                 span_names: Optional[Sequence[str]] = None):
+        self.rows: List[Row] = sorted((tuple(int(v) for v in r) for r in rows), key=canonical_key)
+        self._services = None if services is None else list(services)
+        self._span_names = None if span_names is None else list(span_names)
+        self.spans: List[Span] = self._merge()
+
+    def _service(self, i: int):
+        if self._services is None:
+            return i
+        if i >= len(self._services):
+            raise ValueError("a service id beyond the services dictionary")
+        return self._services[i].lower()
+
+    def _name(self, i: int):
+        if self._span_names is None:
+            return i
+        if i == 0:
+            return None
+        if i > len(self._span_names):
+            raise ValueError("a name id beyond the span_names dictionary")
+        return self._span_names[i - 1]
+
+    def _merge(self) -> List[Span]:
+        acc: Dict[int, list] = {}
+        for tid, sid, pid, first, last, svc, fl in self.rows:
+            a = acc.setdefault(sid, [tid, None, 0, None, None, set()])
+            if fl & _abi.ZK_F_HAS_PARENT and a[1] is None:
+                a[1] = pid
+            if a[2] == 0:
+                a[2] = (fl >> _abi.ZK_F_NAME_SHIFT) & _abi.ZK_F_NAME_MASK
+            if fl & _abi.ZK_F_HAS_ANNOTATIONS:
+                a[3] = first if a[3] is None else min(a[3], first)
+                a[4] = last if a[4] is None else max(a[4], last)
+            if fl & (_abi.ZK_F_SVC_CLIENT | _abi.ZK_F_SVC_SERVER):
+                a[5].add(svc)
+        spans = [Span(a[0], sid, a[1], self._name(a[2]), a[3], a[4], tuple(self._service(s) for s in sorted(a[5])))
+                 for sid, a in acc.items()]
+        spans.sort(key=lambda s: (INT64_MAX if s.first is None else s.first, s.id))
+        return spans
+
+    @property
+    def id(self) -> Optional[int]:
+        return self.spans[0].trace_id if self.spans else None
+
+    def getRootSpan(self) -> Optional[Span]:
+        """The first span without a parent."""
+        return next((s for s in self.spans if s.parent is None), None)
+
+    def getSpanById(self, span_id: int) -> Optional[Span]:
+        return next((s for s in self.spans if s.id == span_id), None)
+
+    def getIdToSpanMap(self) -> Dict[int, Span]:
+        return {s.id: s for s in self.spans}
+
+    def getRootMostSpan(self) -> Optional[Span]:
+        """The root span, else (Trace.scala:70-85) from the first span upwards through the parents the
+        trace holds, to the last one found. A parent chain that closes on itself ends where it would
+        repeat (the reference does not terminate on one)."""
+        root = self.getRootSpan()
+        if root is not None or not self.spans:
+            return root
+        by_id = self.getIdToSpanMap()
+        s, seen = self.spans[0], set()
+        while s.parent is not None and s.parent in by_id and s.id not in seen:
+            seen.add(s.id)
+            s = by_id[s.parent]
+        return s
+
+    def getIdToChildrenMap(self) -> Dict[int, List[Span]]:
+        """parent id -> its child spans, in span order."""
+        out: Dict[int, List[Span]] = {}
+        for s in self.spans:
+            if s.parent is not None:
+                out.setdefault(s.parent, []).append(s)
+        return out
+
+    def toSpanDepths(self) -> Optional[Dict[int, int]]:
+        """span id -> depth in the tree under the root-most span, which is at depth 1; None for a trace
+        without spans. A span reached twice keeps its first depth."""
+        root = self.getRootMostSpan()
+        if root is None:
+            return None
+        children = self.getIdToChildrenMap()
+        depths, level, d = {}, [root], 1
+        while level:
+            nxt = []
+            for s in level:
+                if s.id in depths:
+                    continue
+                depths[s.id] = d
+                nxt += children.get(s.id, [])
+            level, d = nxt, d + 1
+        return depths
+
+    def getStartAndEndTimestamp(self) -> Optional[Timespan]:
+        """(min first, max last) over the timed fragments; None when no fragment is timed."""
+        timed = [s for s in self.spans if s.first is not None]
+        if not timed:
+            return None
+        return Timespan(min(s.first for s in timed), max(s.last for s in timed))
+
+    @property
+    def duration(self) -> int:
+        """end - start as the reference's wrapping Long subtraction; 0 for a trace without times."""
+        t = self.getStartAndEndTimestamp()
+        return 0 if t is None else _wrap64(t.end - t.start)
+
+    @property
+    def services(self) -> set:
+        return {v for s in self.spans for v in s.services}
+
+    def serviceCounts(self) -> Dict[Union[int, str], int]:
+        """service -> the number of merged spans that name it."""
+        out: Dict[Union[int, str], int] = {}
+        for s in self.spans:
+            for v in set(s.services):
+                out[v] = out.get(v, 0) + 1
+        return out
+
+    def spanTimestamps(self) -> List[SpanTimestamp]:
+        """(service, first, last) for each timed span, in span order, and for each of the span's
+        services, ascending by id."""
+        return [SpanTimestamp(v, s.first, s.last) for s in self.spans if s.first is not None for v in s.services]
+
+
+class TraceSummary(NamedTuple):
+    """The reference's TraceSummary. duration_micro = (end - start) wrapped to 64 bits and truncated to a
+    signed 32-bit value (its .toInt). endpoints is always []: a record carries no ip or port."""
+    trace_id: int
+    start: int
+    end: int
+    duration_micro: int
+    span_timestamps: List[SpanTimestamp]
+    endpoints: list
+
+    @staticmethod
+    def of(trace: Trace) -> Optional["TraceSummary"]:
+        """TraceSummary.apply: None for a trace without spans or without a timed fragment."""
+        t = trace.getStartAndEndTimestamp()
+        if trace.id is None or t is None:
+            return None
+        return TraceSummary(trace.id, t.start, t.end, _to_int(_wrap64(t.end - t.start)), trace.spanTimestamps(), [])
+
+
+class TraceSpanStore:
+    """A zk_sp handle. `with TraceSpanStore() as store:` frees it on exit.
+
+    services / span_names: the decoders' dictionaries (index i of services is service id i, index i of
+    span_names is name id i + 1); with them the Traces this store builds give services as lower-cased
+    names (Span.serviceNames) and span names as strings; without, as ids."""
+
+    OBSERVE_PHASES = ("count", "size", "scatter")
+
+    def __init__(self, device: int = 0, timing: bool = False, stream: Optional[int] = None,
+                 services: Optional[Sequence[str]] = None, span_names: Optional[Sequence[str]] = None):
+        self._L = _abi.lib()
+        cfg = _abi.zk_sp_config()
+        cfg.device = device
+        cfg.timing = 1 if timing else 0
+        cfg.stream = stream
+        h = C.c_void_p()
+        st = self._L.zk_sp_create(C.byref(cfg), C.byref(h))
+        if st != _abi.ZK_OK:
+            raise _abi.ZkError(st, _abi.status_str(st))
+        self._h = h
+        self.device = device
+        self.services = None if services is None else list(services)
+        self.span_names = None if span_names is None else list(span_names)
+
+    def _check(self, st: int) -> None:
+        if st != _abi.ZK_OK:
+            raise _abi.ZkError(st, self._L.zk_sp_last_error(self._h).decode() or _abi.status_str(st))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._L.zk_sp_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- writing ---------------------------------------------------------------------------------------
+    def observe(self, cols, *, sync: bool = True) -> None:
+        """Add a batch's records (host SpanColumns or DeviceColumns, any order) as one segment
+        (zk_sp_observe). Observing a batch again adds it again. sync=False leaves the scatter queued on
+        the handle's stream: device columns must then stay as they are until the next call that
+        synchronises (info, tracesExist, getSpansByTraceIds, compact, observe)."""
+        flags = 0
+        ab = cols.abi()
+        if isinstance(cols, DeviceColumns):
+            import torch
+
+            flags |= _abi.ZK_BATCH_DEVICE_PTRS
+            torch.cuda.current_stream(self.device).synchronize()  # (torch may still be writing the batch)
+        self._check(self._L.zk_sp_observe(self._h, C.byref(ab), flags))
+        if sync:
+            self.info()
+
+    def reset(self) -> None:
+        """Empty the store (zk_sp_reset)."""
+        self._check(self._L.zk_sp_reset(self._h))
+
+    def compact(self) -> None:
+        """Merge all segments into one (zk_sp_compact)."""
+        self._check(self._L.zk_sp_compact(self._h))
+
+    def info(self) -> dict:
+        """{"entries", "segments", "bytes"} (zk_sp_info); synchronises."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self._L.zk_sp_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"entries": int(a.value), "segments": int(b.value), "bytes": int(c.value)}
+
+    # ---- reading ---------------------------------------------------------------------------------------
+    def _ask(self, ids):
+        """(keep-alive, pointer, n, flags) of an ask: anything numpy turns into uint64, or a torch int64
+        tensor on the handle's device (the ids' bit patterns)."""
+        if hasattr(ids, "data_ptr"):
+            import torch
+
+            if ids.dtype != torch.int64 or not ids.is_contiguous() or ids.device.index != self.device:
+                raise ValueError("device ids: a contiguous int64 tensor on the handle's device")
+            torch.cuda.current_stream(self.device).synchronize()
+            return ids, ids.data_ptr(), int(ids.numel()), _abi.ZK_BATCH_DEVICE_PTRS
+        a = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64))
+        return a, a.ctypes.data, len(a), 0
+
+    def exist(self, ids) -> np.ndarray:
+        """found bool[n] for at most ZK_SP_MAX_IDS ids, in the order asked (zk_sp_exist)."""
+        keep, ptr, n, flags = self._ask(ids)
+        f = np.zeros(n, np.uint8)
+        self._check(self._L.zk_sp_exist(self._h, ptr, n, flags, f.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return f.astype(bool)
+
+    def gather(self, ids):
+        """(counts uint32[n], columns) for at most ZK_SP_MAX_IDS ids (zk_sp_gather): the sizing call, then
+        the call that fills seven numpy columns (a dict by column name) of exactly the total."""
+        keep, ptr, n, flags = self._ask(ids)
+        counts = np.zeros(n, np.uint32)
+        cp = counts.ctypes.data_as(_abi._U32P)
+        total = C.c_uint64()
+        st = self._L.zk_sp_gather(self._h, ptr, n, flags, cp, None, 0, C.byref(total))
+        if st not in (_abi.ZK_OK, _abi.ZK_ERR_CAPACITY):
+            self._check(st)
+        cols = {k: np.zeros(total.value, dt) for k, dt in COLUMNS}
+        if st == _abi.ZK_ERR_CAPACITY:
+            rows = _abi.zk_sp_rows(*[cols[k].ctypes.data for k, _ in COLUMNS])
+            self._check(self._L.zk_sp_gather(self._h, ptr, n, flags, cp, C.byref(rows), total.value, C.byref(total)))
+        return counts, cols
+
+    def _chunks(self, ids):
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64))
+        for a in range(0, len(ids), _abi.ZK_SP_MAX_IDS):
+            yield ids[a:a + _abi.ZK_SP_MAX_IDS]
+
+    def tracesExist(self, ids) -> set:
+        """SpanStore.tracesExist: the asked ids that some observed fragment carries."""
+        out = set()
+        for part in self._chunks(ids):
+            out.update(part[self.exist(part)].tolist())
+        return out
+
+    def getSpansByTraceIds(self, ids) -> List[List[Row]]:
+        """SpanStore.getSpansByTraceIds: one list of rows, in canonical order, per asked id that was
+        found, in the order asked; ids that are not found are left out (SpanStore.scala:76-84), a
+        duplicated id is answered as often as asked."""
+        out: List[List[Row]] = []
+        for part in self._chunks(ids):
+            counts, cols = self.gather(part)
+            rows = list(zip(*[cols[k].tolist() for k, _ in COLUMNS]))
+            at = 0
+            for c in counts.tolist():
+                if c:
+                    out.append(rows[at:at + c])
+                at += c
+        return out
+
+    def getSpansByTraceId(self, trace_id: int) -> List[Row]:
+        """The rows of one trace; [] when it is not found."""
+        found = self.getSpansByTraceIds([trace_id])
+        return found[0] if found else []
+
+    def getTracesByIds(self, ids) -> List[Trace]:
+        """One Trace per asked id that was found, in the order asked."""
+        return [Trace(rows, self.services, self.span_names) for rows in self.getSpansByTraceIds(ids)]
+
+    def getTraceSummariesByIds(self, ids) -> List[TraceSummary]:
+        """QueryService.getTraceSummariesByIds: the summaries in the order asked; ids that are not found
+        and traces without a timed fragment (TraceSummary.apply yields None) are left out."""
+        return [s for s in (TraceSummary.of(t) for t in self.getTracesByIds(ids)) if s is not None]
+
+    # ---- timing ----------------------------------------------------------------------------------------
+    def observe_ms(self) -> dict:
+        """Device time (ms) of the passes of the last observe (zk_sp_observe_ms; timing=True)."""
+        out = (C.c_double * len(self.OBSERVE_PHASES))()
+        self._check(self._L.zk_sp_observe_ms(self._h, out))
+        return dict(zip(self.OBSERVE_PHASES, out))
+
+    def query_ms(self) -> float:
+        """Time (ms) on the handle's stream of the last exist or gather (zk_sp_query_ms; timing=True)."""
+        ms = C.c_double()
+        self._check(self._L.zk_sp_query_ms(self._h, C.byref(ms)))
+        return float(ms.value)
