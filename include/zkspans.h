@@ -9,10 +9,10 @@
  * trace id, and hands the fragments of the asked traces back.
  *
  * Semantics
- *  - EVERY observed fragment is kept, whole: trace_id, span_id, parent_id, first_ts, last_ts,
- *    service_id, flags. No fragment is filtered (the reference's shouldIndex governs its indices, not
- *    its span data) and no service-range rule applies: the config has no num_services and service_id may
- *    be any 32-bit value.
+ *  - EVERY observed fragment is kept, whole, until its trace expires (see Expiry): trace_id, span_id,
+ *    parent_id, first_ts, last_ts, service_id, flags. No fragment is filtered (the reference's
+ *    shouldIndex governs its indices, not its span data) and no service-range rule applies: the config
+ *    has no num_services and service_id may be any 32-bit value.
  *  - The store is a MULTISET of fragments, like InMemorySpanStore's `spans ++= newSpans`: observing a
  *    batch again adds it again. Batches and records may come in any order; a trace may be spread over
  *    any number of batches.
@@ -28,8 +28,35 @@
  * Departures from the reference
  *  - A record carries no endpoint (ip, port): a TraceSummary built from this store has no endpoints.
  *  - A record carries one service (Span.serviceName's choice), not Span.serviceNames.
- *  - Nothing expires: the reference keeps span data under a TTL of its own; this store grows until
- *    zk_sp_reset.
+ *  - Expiry is by the data's own time, not by the wall-clock time of the write (see Expiry): the
+ *    reference's column TTL counts from the write. Every answer so stays a function of the observed
+ *    multiset and the cutoffs applied. This is zkindex.h's stated departure.
+ *  - A pin (the reference's setTimeToLive) covers the whole trace, fragments observed later included;
+ *    Cassandra gives later columns spanTtl again and getTimeToLive answers the minimum.
+ *
+ * Expiry (zk_sp_expire; the reference writes every span column with spanTtl, 7 days, and lets one trace's
+ * ttl be set and read: CassieSpanStore.scala:47,295,317-339)
+ *  - A trace goes or stays WHOLE. end(trace) = the maximum last_ts over the trace's TIMED fragments in
+ *    the whole store, over all segments (timed: flags & ZK_F_HAS_ANNOTATIONS, zkduration.h's rule). A
+ *    trace survives exactly when end(trace) >= cutoff(trace); end == cutoff stays. The untimed fragments
+ *    of a surviving trace stay with it.
+ *  - The first_ts / last_ts of an untimed fragment are never read as times: an untimed fragment with
+ *    last_ts = INT64_MAX keeps no trace alive.
+ *  - A trace with no timed fragment has end = INT64_MIN: it goes at any cutoff above INT64_MIN. The
+ *    duration index does not hold such a trace and it has no TraceSummary.
+ *  - cutoff(trace) = min_end, unless the call carries a pin for the trace id: then the pin's own min_end,
+ *    which may be lower or higher than the default.
+ *  - min_end == INT64_MIN with no pins removes nothing and rewrites nothing (segments, bytes and
+ *    allocations stay); INT64_MAX keeps only the traces whose end is INT64_MAX.
+ *  - After a call the store is indistinguishable, through zk_sp_exist, zk_sp_gather and zk_sp_info's
+ *    entries, from a fresh store that observed only the surviving fragments. The cut is made once: a
+ *    later observe of older data enters the store again.
+ *  - INVARIANT: a zk_td (zkduration.h) and this store fed the same batches and cut at the same value
+ *    hold the same trace ids: the store's surviving traces with a timed fragment are exactly the ids the
+ *    duration index still finds. With the span cutoff at or below the indices' cutoff (7 days against 3)
+ *    every id an index returns has its whole trace here.
+ *  - Legal as before: trace ids 0 and 2^64 - 1, times at the int64 bounds, a trace of any length spread
+ *    over any number of segments.
  *
  * Layout
  *  - One zk_sp_observe makes one SEGMENT: the batch's records grouped by BUCKET,
@@ -68,12 +95,18 @@ extern "C" {
 #define ZK_SP_MAX_SEGMENTS 64u
 /* the most ids one zk_sp_exist or zk_sp_gather asks */
 #define ZK_SP_MAX_IDS 4096u
+/* the most pins one zk_sp_expire carries */
+#define ZK_SP_MAX_PINS 4096u
+/* the salt of the expiry's scratch table, home slot = zk_mix64(trace_id ^ ZK_SP_END_SALT) & (slots - 1)
+   (apart from ZK_SP_SALT: a range of buckets shares the bucket hash's high bits) */
+#define ZK_SP_END_SALT 0x3C79AC492BA7B653ull
 
 typedef struct zk_sp_config {
     int32_t  device;   /* HIP device ordinal */
-    uint32_t timing;   /* 1: record HIP events (zk_sp_observe_ms, zk_sp_query_ms) */
+    uint32_t timing;   /* 1: record HIP events (zk_sp_observe_ms, zk_sp_query_ms, zk_sp_expire_ms) */
     void*    stream;   /* hipStream_t to run on, or NULL for a private stream */
-    uint32_t reserved[8];
+    uint32_t expire_chunk; /* zk_sp_expire: entries per range of buckets at most; 0: the default, 2^24 */
+    uint32_t reserved[7];
 } zk_sp_config;
 
 /* zk_sp_gather's output: seven HOST columns of `cap` entries each */
@@ -101,7 +134,7 @@ const char* zk_sp_last_error(const zk_sp* sp);
    more). The scatter of the seven columns (48 B read and 48 B written per record, trace_id read once
    more) is queued on the handle's stream behind that: DEVICE columns must stay as they are until the
    handle's next synchronising call (zk_sp_info, zk_sp_exist, zk_sp_gather, zk_sp_compact,
-   zk_sp_observe). A record whose place falls outside its bucket's slice (it cannot while the columns
+   zk_sp_expire, zk_sp_observe). A record whose place falls outside its bucket's slice (it cannot while the columns
    stay as they were) is dropped, never written elsewhere. n == 0 is ZK_OK; n >= 2^32 is
    ZK_ERR_UNSUPPORTED. */
 zk_status   zk_sp_observe(zk_sp* sp, const zk_span_cols* in, uint32_t flags);
@@ -147,6 +180,40 @@ zk_status   zk_sp_observe_ms(zk_sp* sp, double out[3]);
    first pass to its last copy (the host's prefix sum included, the host's sort not). Needs
    zk_sp_config.timing. */
 zk_status   zk_sp_query_ms(zk_sp* sp, double* ms);
+
+/* Expire whole traces by their end (see Expiry).
+     min_end       the default cutoff.
+     pin_ids, pin_min_end   n_pins HOST entries: trace pin_ids[i] is judged by pin_min_end[i]. n_pins == 0
+                   allows NULL arrays; more than ZK_SP_MAX_PINS, or an id given twice, is
+                   ZK_ERR_INVALID_ARG and changes nothing. A pin for an id that is not in the store is
+                   ignored.
+     removed       the entries (fragments) removed.
+   An empty store, and min_end == INT64_MIN without pins, are ZK_OK with *removed = 0 and no device pass.
+   A trace's fragments share one bucket but may lie in every segment, so its end is folded over the store
+   before a fragment is judged. The 4096 buckets are cut into consecutive RANGES of at most
+   zk_sp_config.expire_chunk entries over all segments (one bucket above that is a range of its own); a
+   range is one contiguous slice of every segment. Per range a scratch table {key, end} (16 B per slot;
+   slots a power of two >= 2 x the range's entries; trace id 0 apart) is cleared, then
+     k_sp_end_fold   reads trace_id, last_ts, flags of the range's slices (20 B per entry): claims the key,
+                     folds the end with a 64-bit atomic max; an untimed fragment only claims the key; a
+                     wave folds the runs of equal ids among its 64 entries first, one table update each;
+     k_sp_end_pins   keeps, beside the table, the verdict of every pinned id it finds there, and replaces
+                     the id's end by all ones, which sends the mark pass to the verdicts;
+     k_sp_end_mark   reads trace_id again (8 B per entry), probes, writes one bit per entry (a wave's ballot
+                     as one 64-bit word) and adds the survivors per (segment, bucket).
+   The scratch is bounded by the range, not by the store; the marks take entries / 8 bytes. One copy of
+   the survivor counts and ONE synchronisation follow. Segments where nothing goes are untouched and not
+   read again; segments where everything goes are freed; the survivors of all other segments are written
+   (k_sp_expire_rewrite: the mark bits, and the seven columns of survivors only), grouped by bucket, into
+   ONE new segment that takes the first of their places: the segment count never grows. When nothing goes
+   nothing is rewritten, reallocated or freed. A refused allocation is ZK_ERR_CAPACITY and leaves the
+   handle exactly as it was: nothing is freed or swapped in before every replacement is complete.
+   Synchronises. */
+zk_status   zk_sp_expire(zk_sp* sp, int64_t min_end, const uint64_t* pin_ids, const int64_t* pin_min_end,
+                         uint32_t n_pins, uint64_t* removed);
+/* Device time in ms of the last zk_sp_expire that ran a pass: the end-table passes of all ranges, the
+   sizing step (the counts' copy and the synchronisation), the rewrite. Needs zk_sp_config.timing. */
+zk_status   zk_sp_expire_ms(zk_sp* sp, double out[3]);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ from .realtime import LinkHistogram, LinkHistogramSnapshot  # noqa: F401
 from .durations import TraceDurationIndex, TraceIdDuration, merge_top  # noqa: F401
 from .nameindex import IndexedTraceId, TraceNameIndex, merge_trace_ids  # noqa: F401
 from .annindex import AnnotationItems, DeviceAnnotationItems, TraceAnnotationIndex, get_trace_ids, trace_ids_intersect  # noqa: F401
-from .retention import IndexRetention  # noqa: F401
+from .retention import IndexRetention, SpanRetention  # noqa: F401
 from .spanstore import Span, SpanTimestamp, Timespan, Trace, TraceSpanStore, TraceSummary  # noqa: F401
 from .windows import WindowedAggregateJob, WindowPartition  # noqa: F401
 from . import table  # noqa: F401
@@ -40,6 +40,7 @@ __all__ = [
     "get_trace_ids",
     "trace_ids_intersect",
     "IndexRetention",
+    "SpanRetention",
     "TraceSpanStore",
     "Trace",
     "TraceSummary",

@@ -308,6 +308,8 @@ ZK_SP_SALT = 0x8CB92BA72F3D8DD7
 ZK_SP_BUCKETS = 4096
 ZK_SP_MAX_SEGMENTS = 64
 ZK_SP_MAX_IDS = 4096
+ZK_SP_MAX_PINS = 4096
+ZK_SP_END_SALT = 0x3C79AC492BA7B653
 
 
 class zk_sp_config(C.Structure):
@@ -315,7 +317,8 @@ class zk_sp_config(C.Structure):
         ("device", C.c_int32),
         ("timing", C.c_uint32),
         ("stream", C.c_void_p),
-        ("reserved", C.c_uint32 * 8),
+        ("expire_chunk", C.c_uint32),
+        ("reserved", C.c_uint32 * 7),
     ]
 
 
@@ -634,6 +637,8 @@ _SIGNATURES = [
     ("zk_sp_gather", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _U32P, C.POINTER(zk_sp_rows), C.c_uint64, _U64P]),
     ("zk_sp_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_sp_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zk_sp_expire", C.c_int, [_P, C.c_int64, _P, _P, C.c_uint32, _U64P]),
+    ("zk_sp_expire_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
 ]
 
 SYMBOLS = [s[0] for s in _SIGNATURES]

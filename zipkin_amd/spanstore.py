@@ -237,14 +237,17 @@ class TraceSpanStore:
     names (Span.serviceNames) and span names as strings; without, as ids."""
 
     OBSERVE_PHASES = ("count", "size", "scatter")
+    EXPIRE_PHASES = ("ends", "size", "rewrite")
 
     def __init__(self, device: int = 0, timing: bool = False, stream: Optional[int] = None,
-                 services: Optional[Sequence[str]] = None, span_names: Optional[Sequence[str]] = None):
+                 services: Optional[Sequence[str]] = None, span_names: Optional[Sequence[str]] = None,
+                 expire_chunk: int = 0):
         self._L = _abi.lib()
         cfg = _abi.zk_sp_config()
         cfg.device = device
         cfg.timing = 1 if timing else 0
         cfg.stream = stream
+        cfg.expire_chunk = expire_chunk  # expire's entries per range of buckets at most (0: 2^24)
         h = C.c_void_p()
         st = self._L.zk_sp_create(C.byref(cfg), C.byref(h))
         if st != _abi.ZK_OK:
@@ -299,6 +302,21 @@ class TraceSpanStore:
     def compact(self) -> None:
         """Merge all segments into one (zk_sp_compact)."""
         self._check(self._L.zk_sp_compact(self._h))
+
+    def expire(self, min_end: int, pins: Optional[Dict[int, int]] = None) -> int:
+        """Remove every trace whose end (the maximum last_ts of its timed fragments, INT64_MIN without
+        one) is below its cutoff, whole (zk_sp_expire): the cutoff is min_end, or pins[trace_id] for a
+        pinned trace. The entries removed. More than ZK_SP_MAX_PINS pins are refused: a second call would
+        judge the first call's pinned traces by the default."""
+        pins = {} if pins is None else dict(pins)
+        if len(pins) > _abi.ZK_SP_MAX_PINS:
+            raise ValueError("more than ZK_SP_MAX_PINS pins in one expiry")
+        ids = np.array([int(k) & _M64 for k in pins], np.uint64)
+        cuts = np.array([int(v) for v in pins.values()], np.int64)
+        removed = C.c_uint64()
+        self._check(self._L.zk_sp_expire(self._h, int(min_end), ids.ctypes.data if len(ids) else None,
+                                         cuts.ctypes.data if len(ids) else None, len(ids), C.byref(removed)))
+        return int(removed.value)
 
     def info(self) -> dict:
         """{"entries", "segments", "bytes"} (zk_sp_info); synchronises."""
@@ -390,6 +408,12 @@ class TraceSpanStore:
         out = (C.c_double * len(self.OBSERVE_PHASES))()
         self._check(self._L.zk_sp_observe_ms(self._h, out))
         return dict(zip(self.OBSERVE_PHASES, out))
+
+    def expire_ms(self) -> dict:
+        """Device time (ms) of the passes of the last expire that ran one (zk_sp_expire_ms; timing=True)."""
+        out = (C.c_double * len(self.EXPIRE_PHASES))()
+        self._check(self._L.zk_sp_expire_ms(self._h, out))
+        return dict(zip(self.EXPIRE_PHASES, out))
 
     def query_ms(self) -> float:
         """Time (ms) on the handle's stream of the last exist or gather (zk_sp_query_ms; timing=True)."""
