@@ -6,7 +6,8 @@
  * getTraceSummariesByIds; SpanStore.scala:76-84), and a Trace is built from those spans (Trace.scala,
  * TraceSummary.scala). The trace-id indices (zkindex.h, zkannindex.h) and the duration index
  * (zkduration.h) hand out trace ids; this handle keeps the 48-B records themselves in HBM, findable by
- * trace id, and hands the fragments of the asked traces back.
+ * trace id, and hands the fragments of the asked traces back, or their TraceSummary alone, merged on the
+ * device (zk_sp_summaries).
  *
  * Semantics
  *  - EVERY observed fragment is kept, whole, until its trace expires (see Expiry): trace_id, span_id,
@@ -101,6 +102,16 @@ extern "C" {
    (apart from ZK_SP_SALT: a range of buckets shares the bucket hash's high bits) */
 #define ZK_SP_END_SALT 0x3C79AC492BA7B653ull
 
+/* the longest trace (in rows) whose spans zk_sp_summaries merges on the device; a power of two */
+#define ZK_SP_SUM_MAX_ROWS 2048u
+/* zk_sp_summaries' plan: a trace of up to this many rows is summarized by one wave, a longer one by a workgroup */
+#define ZK_SP_SUM_WAVE_ROWS 64u
+/* zk_sp_summary.state */
+#define ZK_SP_SUM_FOUND    1u  /* some fragment carries the id */
+#define ZK_SP_SUM_TIMED    2u  /* some fragment of the trace is timed; clear: start = end = 0, the trace for
+                                  which TraceSummary.apply yields None */
+#define ZK_SP_SUM_OVERFLOW 4u  /* more than ZK_SP_SUM_MAX_ROWS rows: spans = span_ts = 0 and no entries */
+
 typedef struct zk_sp_config {
     int32_t  device;   /* HIP device ordinal */
     uint32_t timing;   /* 1: record HIP events (zk_sp_observe_ms, zk_sp_query_ms, zk_sp_expire_ms) */
@@ -120,6 +131,24 @@ typedef struct zk_sp_rows {
     uint32_t* flags;
 } zk_sp_rows;
 
+/* zk_sp_summaries' head of one asked id, 40 bytes */
+typedef struct zk_sp_summary {
+    uint64_t trace_id;   /* the asked id; 0 when it is not found (the whole head is zeros then) */
+    int64_t  start;      /* the minimum first_ts over the trace's timed fragments */
+    int64_t  end;        /* the maximum last_ts over them */
+    uint32_t fragments;  /* the trace's rows */
+    uint32_t spans;      /* its merged spans, timed or not */
+    uint32_t span_ts;    /* its entries in zk_sp_span_ts */
+    uint32_t state;      /* ZK_SP_SUM_* */
+} zk_sp_summary;
+
+/* zk_sp_summaries' entries: three HOST columns of `cap` entries each */
+typedef struct zk_sp_span_ts {
+    uint32_t* service_id;
+    int64_t*  first;
+    int64_t*  last;
+} zk_sp_span_ts;
+
 typedef struct zk_sp zk_sp;
 
 zk_status   zk_sp_create(const zk_sp_config* cfg, zk_sp** out);
@@ -133,7 +162,7 @@ const char* zk_sp_last_error(const zk_sp* sp);
    synchronises once, to read the counts it sizes the segment by (a merge, see Layout, synchronises once
    more). The scatter of the seven columns (48 B read and 48 B written per record, trace_id read once
    more) is queued on the handle's stream behind that: DEVICE columns must stay as they are until the
-   handle's next synchronising call (zk_sp_info, zk_sp_exist, zk_sp_gather, zk_sp_compact,
+   handle's next synchronising call (zk_sp_info, zk_sp_exist, zk_sp_gather, zk_sp_summaries, zk_sp_compact,
    zk_sp_expire, zk_sp_observe). A record whose place falls outside its bucket's slice (it cannot while the columns
    stay as they were) is dropped, never written elsewhere. n == 0 is ZK_OK; n >= 2^32 is
    ZK_ERR_UNSUPPORTED. */
@@ -172,12 +201,48 @@ zk_status   zk_sp_exist(zk_sp* sp, const uint64_t* ids, uint32_t n, uint32_t fla
    grown; a refused allocation is ZK_ERR_CAPACITY. Synchronises. */
 zk_status   zk_sp_gather(zk_sp* sp, const uint64_t* ids, uint32_t n, uint32_t flags, uint32_t* counts,
                          zk_sp_rows* out, uint64_t cap, uint64_t* n_out);
+/* The reference's TraceSummary (TraceSummary.scala, Trace.scala) of the asked traces, at record granularity:
+   only summaries cross to the host. For one asked id, over all its fragments in all segments:
+     merged spans  the fragments grouped by span_id. A span is timed when any of its fragments has
+                   ZK_F_HAS_ANNOTATIONS; first = the minimum first_ts and last = the maximum last_ts over its
+                   TIMED fragments (an untimed fragment's times are never read).
+     services      of a span: the set of service_id over its fragments with ZK_F_SVC_CLIENT |
+                   ZK_F_SVC_SERVER; a fragment with neither bit gives no service and is still a fragment
+                   of the span.
+     span order    by first ascending (signed), ties by span_id ascending as unsigned; an untimed span counts
+                   in `spans` and has no entry.
+     entries       in span order, per timed span one (service_id, first, last) for each of its services,
+                   ascending by id; a timed span without a service has none.
+     start, end    the minimum first_ts and the maximum last_ts over the trace's timed fragments.
+   The answer is a function of the store's multiset of fragments and the asked ids alone.
+     ids, n, flags   as for zk_sp_gather; n == 0 is ZK_OK with *n_out = 0.
+     heads   n HOST structs, in the order asked; a duplicated id is answered as often as asked; an id that is
+             not found gets a head of zeros.
+     out     three HOST columns of `cap` entries each: the entries of ids[0] first, then those of ids[1], and
+             so on. out, or any of its columns, may be NULL only when cap == 0.
+     n_out   the total number of entries, the sum of span_ts.
+   When cap is below the total the call returns ZK_ERR_CAPACITY with *n_out set to the needed total and the
+   heads written; no entry is written. cap == 0 with NULL columns is the sizing call. An empty store
+   answers without a device pass.
+   fragments, start, end, FOUND and TIMED are plain reductions, exact for a trace of any length. The merge
+   by span id sorts the trace's rows in LDS, for traces of up to ZK_SP_SUM_MAX_ROWS rows; a longer trace gets
+   ZK_SP_SUM_OVERFLOW, spans = span_ts = 0 and no entries (the caller merges it from zk_sp_gather's rows).
+   The passes: zk_sp_gather's count pass, synchronisation and prefix sum, its write pass into the handle's
+   staging (the rows stay in HBM), then k_sp_summarize over the staged rows, a trace of up to 64 rows per
+   wave and a longer one per workgroup of 256 (31 B of LDS per row: sort by (span_id, service), fold, mark
+   one entry per (span, service), sort by (first, span_id, service)). Entries are staged at their rows' own
+   bases (a trace has at most as many entries as rows). The heads (40 B per id) are copied and the call
+   synchronises; if the entries fit, the staged entry columns (20 B per row) follow in one copy and are
+   packed per trace on the host. Staging is grown on use; a refused allocation is ZK_ERR_CAPACITY and leaves
+   the handle as it was. */
+zk_status   zk_sp_summaries(zk_sp* sp, const uint64_t* ids, uint32_t n, uint32_t flags, zk_sp_summary* heads,
+                            zk_sp_span_ts* out, uint64_t cap, uint64_t* n_out);
 /* Device time in ms of the last zk_sp_observe that added a segment: the count, the sizing step (the
    counts' copy and, when the segment bound was met, the merge), the scatter. Needs zk_sp_config.timing;
    waits for the scatter. */
 zk_status   zk_sp_observe_ms(zk_sp* sp, double out[3]);
-/* Time in ms on the handle's stream of the last zk_sp_exist or zk_sp_gather that ran a pass, from its
-   first pass to its last copy (the host's prefix sum included, the host's sort not). Needs
+/* Time in ms on the handle's stream of the last zk_sp_exist, zk_sp_gather or zk_sp_summaries that ran a
+   pass, from its first pass to its last copy (the host's prefix sum included, the host's sort not). Needs
    zk_sp_config.timing. */
 zk_status   zk_sp_query_ms(zk_sp* sp, double* ms);
 

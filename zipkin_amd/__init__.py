@@ -11,7 +11,7 @@ from .durations import TraceDurationIndex, TraceIdDuration, merge_top  # noqa: F
 from .nameindex import IndexedTraceId, TraceNameIndex, merge_trace_ids  # noqa: F401
 from .annindex import AnnotationItems, DeviceAnnotationItems, TraceAnnotationIndex, get_trace_ids, trace_ids_intersect  # noqa: F401
 from .retention import IndexRetention, SpanRetention  # noqa: F401
-from .spanstore import Span, SpanTimestamp, Timespan, Trace, TraceSpanStore, TraceSummary  # noqa: F401
+from .spanstore import SUMMARY_HEAD, Span, SpanTimestamp, Timespan, Trace, TraceSpanStore, TraceSummary  # noqa: F401
 from .windows import WindowedAggregateJob, WindowPartition  # noqa: F401
 from . import table  # noqa: F401
 
@@ -47,5 +47,6 @@ __all__ = [
     "Span",
     "SpanTimestamp",
     "Timespan",
+    "SUMMARY_HEAD",
     "BYTES_PER_RECORD",
 ]

@@ -334,6 +334,33 @@ class zk_sp_rows(C.Structure):
     ]
 
 
+ZK_SP_SUM_MAX_ROWS = 2048
+ZK_SP_SUM_WAVE_ROWS = 64
+ZK_SP_SUM_FOUND = 1
+ZK_SP_SUM_TIMED = 2
+ZK_SP_SUM_OVERFLOW = 4
+
+
+class zk_sp_summary(C.Structure):
+    _fields_ = [
+        ("trace_id", C.c_uint64),
+        ("start", C.c_int64),
+        ("end", C.c_int64),
+        ("fragments", C.c_uint32),
+        ("spans", C.c_uint32),
+        ("span_ts", C.c_uint32),
+        ("state", C.c_uint32),
+    ]
+
+
+class zk_sp_span_ts(C.Structure):
+    _fields_ = [
+        ("service_id", C.c_void_p),
+        ("first", C.c_void_p),
+        ("last", C.c_void_p),
+    ]
+
+
 ZK_RT_WITH_DEPS = 0
 ZK_RT_ONLY = 1
 ZK_RL_ANY_RPC = 0xFFFFFFFF
@@ -635,6 +662,7 @@ _SIGNATURES = [
     ("zk_sp_info", C.c_int, [_P, _U64P, _U64P, _U64P]),
     ("zk_sp_exist", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8)]),
     ("zk_sp_gather", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _U32P, C.POINTER(zk_sp_rows), C.c_uint64, _U64P]),
+    ("zk_sp_summaries", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.POINTER(zk_sp_span_ts), C.c_uint64, _U64P]),
     ("zk_sp_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_sp_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_sp_expire", C.c_int, [_P, C.c_int64, _P, _P, C.c_uint32, _U64P]),

@@ -20,6 +20,13 @@
 //                 id, segment, part of the slice) walks the trace_id slice of the id's bucket; the write
 //                 pass appends a wave's matching rows behind the asked id's offset with one returning
 //                 atomic per wave. Nothing of a trace is held in LDS: a trace may be of any length.
+//   k_sp_summarize   zk_sp_summaries' pass over the rows the write pass staged: one trace per wave (up to 64
+//                 rows) or per workgroup (up to ZK_SP_SUM_MAX_ROWS). The head's start, end and counts are
+//                 plain reductions; the trace's rows are sorted by (span id, service) in LDS (bitonic, over
+//                 16-bit row numbers), first / last / timed folded into each span's first row with LDS
+//                 atomics, the first row of every (span, service) pair of a timed span marked as an ENTRY,
+//                 and the rows sorted again by (entry, first, span id, service): the entries are then the
+//                 leading rows, written behind the trace's row base. 31 B of LDS per row.
 //   k_sp_end_fold, k_sp_end_pins, k_sp_end_mark, k_sp_expire_rewrite   zk_sp_expire's passes: per range of
 //                 buckets a scratch table trace id -> end in HBM (the fold over every segment's slice of
 //                 the range, 20 B per entry), the pins' verdicts, then one mark bit per entry and the
@@ -68,8 +75,23 @@ constexpr uint64_t kSpExpireChunk = 1ull << 24;      // zk_sp_config.expire_chun
 constexpr uint64_t kSpEndMinSlots = 1024;
 constexpr uint32_t kSpEndGrid = 4096;                // the end-table passes: workgroups per segment at most
 constexpr uint32_t kSpMaxItems = 4096;               // the rewrite's work items at most, plus one per segment
+constexpr uint32_t kSpSumMaxRows = ZK_SP_SUM_MAX_ROWS;  // the summaries: the longest trace merged on the device
+constexpr int kSpSumWave = ZK_SP_SUM_WAVE_ROWS;                     // a trace of up to this many rows gets a wave, a longer one a workgroup
+constexpr int kSpSumItems = kSpSumMaxRows / kSpWG;   // rows per thread of the workgroup at most
+constexpr uint32_t kSumTimed = 1u, kSumSvc = 2u, kSumSpanTimed = 4u, kSumEntry = 8u;  // a row's byte in LDS
+constexpr size_t kSumLdsHead = 32;                   // start, end [8 B], timed, spans, entries [4 B], 4 B unused
+constexpr size_t kSumLdsPerRow = 31;                 // span, first, last [8 B], service [4 B], order [2 B], bits [1 B]
 
 static_assert(kSpBins == 4096, "the bucket is the hash's 12 highest bits");
+static_assert(kSpSumMaxRows >= 2048 && kSpSumMaxRows <= 65536 && (kSpSumMaxRows & (kSpSumMaxRows - 1)) == 0 &&
+                  kSpSumItems * kSpWG == (int)kSpSumMaxRows,
+              "the summaries sort 16-bit row numbers over a power of two");
+static_assert(kSumLdsHead + kSumLdsPerRow * kSpSumMaxRows <= 65536, "a trace of ZK_SP_SUM_MAX_ROWS rows fits 64 KiB of LDS");
+static_assert(sizeof(zk_sp_summary) == 40, "zk_sp_summary's layout");
+static_assert(kSpSumWave == 64, "a wave holds one row per lane");
+
+// LDS of one k_sp_summarize workgroup whose launch admits traces of up to `rows` rows (a power of two >= 64)
+constexpr size_t sp_sum_lds(uint32_t rows) { return kSumLdsHead + kSumLdsPerRow * rows; }
 
 __host__ __device__ inline uint32_t sp_bucket(unsigned long long id) { return (uint32_t)(zk_mix64(id ^ kSpSalt) >> 52); }
 
@@ -88,13 +110,15 @@ struct SpCols {
 };
 static_assert(sizeof(SpCols) == 72, "the segment table's stride");
 
-// the lookups' block: the asked ids, their counts, the write pass's cursors, the rows' bases, the segments
+// the lookups' block: the asked ids, their counts, the write pass's cursors, the rows' bases, the segments,
+// the summaries' work lists
 constexpr size_t kQIdsAt = 0;
 constexpr size_t kQCountsAt = kQIdsAt + ZK_SP_MAX_IDS * 8;
 constexpr size_t kQCursorAt = kQCountsAt + ZK_SP_MAX_IDS * 4;
 constexpr size_t kQBaseAt = kQCursorAt + ZK_SP_MAX_IDS * 4;
 constexpr size_t kQSegsAt = kQBaseAt + ZK_SP_MAX_IDS * 8;
-constexpr size_t kQBytes = kQSegsAt + ZK_SP_MAX_SEGMENTS * sizeof(SpCols);
+constexpr size_t kQListAt = kQSegsAt + ZK_SP_MAX_SEGMENTS * sizeof(SpCols);  // the summaries' work lists (asked indices)
+constexpr size_t kQBytes = kQListAt + ZK_SP_MAX_IDS * 4;
 // the observe's block: the counts, then the cursors
 constexpr size_t kObsCursorAt = kSpBins * 4;
 constexpr size_t kObsBytes = 2 * kSpBins * 4;
@@ -278,6 +302,238 @@ __global__ __launch_bounds__(kSpWG) void k_sp_find_write(const SpCols* __restric
                 out.fl[at] = sg.fl[i];
             }
         }
+    }
+}
+
+// ---- the summaries -------------------------------------------------------------------------------------
+// One trace's rows in LDS, by ROW NUMBER (the row's place among the trace's staged rows): span, first and
+// last ([8 B]; a time is held ^ sign, an untimed row's first as all ones and its last as 0, the folds'
+// neutral values), svc [4 B], bits (one byte: kSumTimed, kSumSvc of the row, then kSumSpanTimed on a span's
+// first row and kSumEntry), and ord [2 B]: the row numbers in sorted order; a number at or past n is padding.
+struct SpSumRows {
+    unsigned long long* span;
+    unsigned long long* first;
+    unsigned long long* last;
+    uint32_t* svc;
+    uint16_t* ord;
+    uint8_t* bits;
+    uint32_t n;
+};
+
+// (span id, then the service-bearing rows by service, then the rows without a service); padding last
+__device__ inline bool sp_sum_by_span(const SpSumRows& t, uint32_t a, uint32_t b) {
+    if (b >= t.n) return a < t.n;
+    if (a >= t.n) return false;
+    if (t.span[a] != t.span[b]) return t.span[a] < t.span[b];
+    const bool sa = t.bits[a] & kSumSvc, sb = t.bits[b] & kSumSvc;
+    if (sa != sb) return sa;
+    return sa && t.svc[a] < t.svc[b];
+}
+
+// the entries first, by (first signed, span id unsigned, service); everything else behind them, in any order
+__device__ inline bool sp_sum_by_first(const SpSumRows& t, uint32_t a, uint32_t b) {
+    const bool ea = a < t.n && (t.bits[a] & kSumEntry), eb = b < t.n && (t.bits[b] & kSumEntry);
+    if (ea != eb) return ea;
+    if (!ea) return false;
+    if (t.first[a] != t.first[b]) return t.first[a] < t.first[b];
+    if (t.span[a] != t.span[b]) return t.span[a] < t.span[b];
+    return t.svc[a] < t.svc[b];
+}
+
+// A bitonic sort of ord[0, P) (P a power of two >= 2, the same for the whole workgroup): every thread takes
+// pairs (i, i | j). Ends behind a barrier.
+template <int T, bool (*Less)(const SpSumRows&, uint32_t, uint32_t)>
+__device__ inline void sp_sum_sort(const SpSumRows& t, uint32_t P) {
+    for (uint32_t k = 2; k <= P; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t w = threadIdx.x; w < P / 2; w += T) {
+                const uint32_t i = ((w & ~(j - 1u)) << 1) | (w & (j - 1u)), x = i | j;
+                const uint16_t a = t.ord[i], b = t.ord[x];
+                if ((i & k) == 0 ? Less(t, b, a) : Less(t, a, b)) {
+                    t.ord[i] = b;
+                    t.ord[x] = a;
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// The summary of asked id list[blockIdx.x] from its staged rows [base[q], base[q] + counts[q]): the head
+// into heads[q], the entries behind the rows' own base in the entry columns (a trace has at most as many
+// entries as rows). T threads hold up to T * I rows; the launch's LDS admits `cap` rows. A trace above
+// either, or above ZK_SP_SUM_MAX_ROWS, gets the reductions (fragments, start, end, FOUND, TIMED) and
+// OVERFLOW: nothing of it goes to LDS. Every bound that guards a barrier is the same for the whole
+// workgroup. The first_ts / last_ts of an untimed row are not loaded.
+template <int T, int I>
+__global__ __launch_bounds__(T) void k_sp_summarize(SpCols rows, const uint32_t* __restrict__ list,
+                                                    const unsigned long long* __restrict__ ids,
+                                                    const uint32_t* __restrict__ counts,
+                                                    const unsigned long long* __restrict__ base, uint32_t cap,
+                                                    zk_sp_summary* __restrict__ heads, uint32_t* __restrict__ e_svc,
+                                                    long long* __restrict__ e_first, long long* __restrict__ e_last) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_sum[];
+    unsigned long long* s_start = (unsigned long long*)s_sum;
+    unsigned long long* s_end = s_start + 1;
+    uint32_t* s_cnt = (uint32_t*)(s_sum + 16);  // timed, spans, entries
+    const uint32_t q = list[blockIdx.x];
+    const uint32_t n = counts[q];
+    const unsigned long long r0 = base[q];
+    if (n == 0 || r0 + n > rows.n) return;  // (not a staged trace: never on a work list)
+    const bool fits = n <= cap && n <= kSpSumMaxRows && n <= (uint32_t)(T * I);
+    SpSumRows t;
+    t.span = (unsigned long long*)(s_sum + kSumLdsHead);
+    t.first = t.span + cap;
+    t.last = t.first + cap;
+    t.svc = (uint32_t*)(t.last + cap);
+    t.ord = (uint16_t*)(t.svc + cap);
+    t.bits = (uint8_t*)(t.ord + cap);
+    t.n = n;
+    uint32_t P = 2;
+    while (P < n && P < cap) P <<= 1;
+    if (threadIdx.x == 0) {
+        *s_start = kSpNone;
+        *s_end = 0ull;
+        s_cnt[0] = s_cnt[1] = s_cnt[2] = 0u;
+    }
+    __syncthreads();
+    unsigned long long lo = kSpNone, hi = 0ull;
+    bool any = false;
+    for (uint32_t i = threadIdx.x; i < n; i += T) {
+        const unsigned long long at = r0 + i;
+        const uint32_t f = rows.fl[at];
+        const bool timed = f & ZK_F_HAS_ANNOTATIONS;
+        const unsigned long long a = timed ? (unsigned long long)rows.first[at] ^ kSpSign : kSpNone;
+        const unsigned long long z = timed ? (unsigned long long)rows.last[at] ^ kSpSign : 0ull;
+        lo = a < lo ? a : lo;
+        hi = z > hi ? z : hi;
+        any |= timed;
+        if (fits) {
+            t.span[i] = rows.span[at];
+            t.first[i] = a;
+            t.last[i] = z;
+            t.svc[i] = rows.svc[at];
+            t.bits[i] = (uint8_t)((timed ? kSumTimed : 0u) | (f & (ZK_F_SVC_CLIENT | ZK_F_SVC_SERVER) ? kSumSvc : 0u));
+        }
+    }
+    if (fits)
+        for (uint32_t i = threadIdx.x; i < P; i += T) t.ord[i] = (uint16_t)i;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long ol = __shfl_down(lo, off), oh = __shfl_down(hi, off);
+        lo = ol < lo ? ol : lo;
+        hi = oh > hi ? oh : hi;
+    }
+    const bool wave_any = __ballot(any) != 0ull;
+    if (lane_id() == 0 && wave_any) {
+        atomicMin(s_start, lo);
+        atomicMax(s_end, hi);
+        atomicOr(&s_cnt[0], 1u);
+    }
+    __syncthreads();
+    if (!fits) {
+        if (threadIdx.x == 0) {
+            const bool timed = s_cnt[0] != 0u;
+            zk_sp_summary hd;
+            hd.trace_id = ids[q];
+            hd.start = timed ? (long long)(*s_start ^ kSpSign) : 0;
+            hd.end = timed ? (long long)(*s_end ^ kSpSign) : 0;
+            hd.fragments = n;
+            hd.spans = 0u;
+            hd.span_ts = 0u;
+            hd.state = ZK_SP_SUM_FOUND | (timed ? ZK_SP_SUM_TIMED : 0u) | ZK_SP_SUM_OVERFLOW;
+            heads[q] = hd;
+        }
+        return;
+    }
+    sp_sum_sort<T, sp_sum_by_span>(t, P);
+    // The fold: a row finds its span's first row in the sorted order (a binary search over the span ids) and
+    // folds its times into that row's. Only first rows are updated, and only with atomics; what the others
+    // read here (their own times, every row's span id and low bits) does not change. The bits' atomic is on
+    // the byte's 32-bit word and sets kSumSpanTimed alone.
+    uint32_t* bits_w = (uint32_t*)t.bits;
+    uint32_t head_of[I];
+#pragma unroll
+    for (int k = 0; k < I; ++k) {
+        const uint32_t p = threadIdx.x + (uint32_t)k * T;
+        head_of[k] = 0u;
+        if (p < n) {
+            const uint32_t r = t.ord[p];
+            const unsigned long long s = t.span[r];
+            uint32_t a = 0, z = p;
+            while (a < z) {
+                const uint32_t mid = (a + z) >> 1;
+                if (t.span[t.ord[mid]] < s) a = mid + 1; else z = mid;
+            }
+            const uint32_t h = t.ord[a];
+            head_of[k] = h;
+            if (a == p) atomicAdd(&s_cnt[1], 1u);
+            if (t.bits[r] & kSumTimed) {
+                if (a != p) {
+                    atomicMin(&t.first[h], t.first[r]);
+                    atomicMax(&t.last[h], t.last[r]);
+                }
+                atomicOr(&bits_w[h >> 2], kSumSpanTimed << (8u * (h & 3u)));
+            }
+        }
+    }
+    __syncthreads();
+    // every row takes its span's times; the first row of a (span, service) pair of a timed span is an entry
+    unsigned long long sf[I], sl[I];
+    bool entry[I];
+#pragma unroll
+    for (int k = 0; k < I; ++k) {
+        const uint32_t p = threadIdx.x + (uint32_t)k * T;
+        sf[k] = sl[k] = 0ull;
+        entry[k] = false;
+        if (p < n) {
+            const uint32_t r = t.ord[p], h = head_of[k];
+            sf[k] = t.first[h];
+            sl[k] = t.last[h];
+            bool e = (t.bits[r] & kSumSvc) && (t.bits[h] & kSumSpanTimed);
+            if (e && p > 0) {
+                const uint32_t prev = t.ord[p - 1];
+                if (t.span[prev] == t.span[r] && (t.bits[prev] & kSumSvc) && t.svc[prev] == t.svc[r]) e = false;
+            }
+            entry[k] = e;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < I; ++k) {
+        const uint32_t p = threadIdx.x + (uint32_t)k * T;
+        if (p < n) {
+            const uint32_t r = t.ord[p];
+            t.first[r] = sf[k];
+            t.last[r] = sl[k];
+            if (entry[k]) {
+                t.bits[r] = (uint8_t)(t.bits[r] | kSumEntry);
+                atomicAdd(&s_cnt[2], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    sp_sum_sort<T, sp_sum_by_first>(t, P);
+    const uint32_t E = s_cnt[2] < n ? s_cnt[2] : n;
+    for (uint32_t p = threadIdx.x; p < E; p += T) {
+        const uint32_t r = t.ord[p];
+        const unsigned long long at = r0 + p;  // (p < n: inside the trace's own rows, r0 + n <= rows.n)
+        if (r < n) {
+            e_svc[at] = t.svc[r];
+            e_first[at] = (long long)(t.first[r] ^ kSpSign);
+            e_last[at] = (long long)(t.last[r] ^ kSpSign);
+        }
+    }
+    if (threadIdx.x == 0) {
+        const bool timed = s_cnt[0] != 0u;
+        zk_sp_summary hd;
+        hd.trace_id = ids[q];
+        hd.start = timed ? (long long)(*s_start ^ kSpSign) : 0;
+        hd.end = timed ? (long long)(*s_end ^ kSpSign) : 0;
+        hd.fragments = n;
+        hd.spans = s_cnt[1];
+        hd.span_ts = E;
+        hd.state = ZK_SP_SUM_FOUND | (timed ? ZK_SP_SUM_TIMED : 0u);
+        heads[q] = hd;
     }
 }
 
@@ -533,7 +789,11 @@ struct zk_sp {
     void* mplan = nullptr;   // a merge's bases, per old segment
     void* q = nullptr;       // the lookups' block (kQBytes)
     void* rows = nullptr;    // the write pass's rows, seven columns
-    size_t stage_bytes = 0, mplan_bytes = 0, rows_bytes = 0;
+    void* sum_heads = nullptr;  // the summaries' heads (ZK_SP_MAX_IDS of them)
+    void* ents = nullptr;       // the summaries' entries at their rows' bases: first, last [8 B], service [4 B]
+    size_t stage_bytes = 0, mplan_bytes = 0, rows_bytes = 0, ents_bytes = 0;
+    std::vector<uint32_t> sum_counts_host, sum_list_host;
+    std::vector<uint8_t> ents_host;
     std::vector<uint32_t> counts_host, cursor_host, off_host;  // (queued copies read the last two: they change only behind a synchronisation)
     std::vector<uint32_t> mplan_host, moff_host;
     std::vector<uint64_t> ids_host, base_host;
@@ -910,7 +1170,7 @@ zk_status zk_sp_destroy(zk_sp* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     free_segments(h);
-    for (void* p : {h->obs, h->stage, h->mplan, h->q, h->rows, h->xplan})
+    for (void* p : {h->obs, h->stage, h->mplan, h->q, h->rows, h->xplan, h->sum_heads, h->ents})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : h->oev)
         if (e) (void)hipEventDestroy(e);
@@ -1201,6 +1461,108 @@ zk_status zk_sp_gather(zk_sp* h, const uint64_t* ids, uint32_t n, uint32_t flags
             out->service_id[d] = r.svc[s];
             out->flags[d] = r.fl[s];
         }
+    }
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_sp_summaries(zk_sp* h, const uint64_t* ids, uint32_t n, uint32_t flags, zk_sp_summary* heads, zk_sp_span_ts* out,
+                          uint64_t cap, uint64_t* n_out) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (!n_out) return sfail(h, ZK_ERR_INVALID_ARG, "null argument");
+    zk_status st = check_ask(h, ids, n, flags);
+    if (st != ZK_OK) return st;
+    if (n && !heads) return sfail(h, ZK_ERR_INVALID_ARG, "null argument");
+    if (cap && (!out || !out->service_id || !out->first || !out->last)) return sfail(h, ZK_ERR_INVALID_ARG, "null output column");
+    *n_out = 0;
+    if (n == 0) return ZK_OK;
+    memset(heads, 0, (size_t)n * sizeof(zk_sp_summary));
+    if (h->segs.empty()) return ZK_OK;
+    SP_HIP(h, hipSetDevice(h->device));
+    // the two passes of zk_sp_gather: the rows of the asked traces into the handle's staging
+    uint32_t parts = 1;
+    h->sum_counts_host.resize(n);
+    uint32_t* counts = h->sum_counts_host.data();
+    if ((st = find_count(h, ids, n, flags, counts, &parts)) != ZK_OK) return st;
+    h->base_host.resize(n);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        h->base_host[i] = total;
+        total += counts[i];
+    }
+    if (total == 0) return ZK_OK;
+    // the work lists: the traces a wave takes, then the ones a workgroup takes; the workgroups' LDS is sized
+    // by the longest trace among them that is merged on the device
+    h->sum_list_host.clear();
+    for (uint32_t i = 0; i < n; ++i)
+        if (counts[i] && counts[i] <= (uint32_t)kSpSumWave) h->sum_list_host.push_back(i);
+    const uint32_t n_wave = (uint32_t)h->sum_list_host.size();
+    uint32_t big_rows = kSpSumWave;
+    for (uint32_t i = 0; i < n; ++i)
+        if (counts[i] > (uint32_t)kSpSumWave) {
+            h->sum_list_host.push_back(i);
+            if (counts[i] <= kSpSumMaxRows)
+                while (big_rows < counts[i]) big_rows <<= 1;
+        }
+    const uint32_t n_group = (uint32_t)h->sum_list_host.size() - n_wave;
+    const size_t e8 = Block::col8(total);
+    if (!h->sum_heads && (st = alloc(h, &h->sum_heads, ZK_SP_MAX_IDS * sizeof(zk_sp_summary), "the summaries' heads")) != ZK_OK) return st;
+    if ((st = grow(h, &h->rows, &h->rows_bytes, Block::cols_bytes(total), "the gathered rows (48 B each)")) != ZK_OK) return st;
+    if ((st = grow(h, &h->ents, &h->ents_bytes, 2 * e8 + Block::col4(total), "the summaries' entries (20 B per row)")) != ZK_OK) return st;
+    uint8_t* qb = (uint8_t*)h->q;
+    const SpCols dev = Block::view(h->rows, total, false);
+    const uint32_t G = (uint32_t)h->segs.size();
+    zk_sp_summary* d_heads = (zk_sp_summary*)h->sum_heads;
+    long long* d_first = (long long*)h->ents;
+    long long* d_last = (long long*)((uint8_t*)h->ents + e8);
+    uint32_t* d_svc = (uint32_t*)((uint8_t*)h->ents + 2 * e8);
+    const uint32_t* d_list = (const uint32_t*)(qb + kQListAt);
+    const unsigned long long* d_ids = (const unsigned long long*)(qb + kQIdsAt);
+    const uint32_t* d_counts = (const uint32_t*)(qb + kQCountsAt);
+    const unsigned long long* d_base = (const unsigned long long*)(qb + kQBaseAt);
+    SP_HIP(h, hipMemcpyAsync(qb + kQBaseAt, h->base_host.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    SP_HIP(h, hipMemcpyAsync(qb + kQListAt, h->sum_list_host.data(), h->sum_list_host.size() * 4, hipMemcpyHostToDevice, h->stream));
+    SP_HIP(h, hipMemsetAsync(qb + kQCursorAt, 0, (size_t)n * 4, h->stream));
+    SP_HIP(h, hipMemsetAsync(d_heads, 0, (size_t)n * sizeof(zk_sp_summary), h->stream));
+    SP_HIP(h, launch_checked("k_sp_find_write", k_sp_find_write, dim3(n, G, parts), dim3(kSpWG), 0, h->stream,
+                             (const SpCols*)(qb + kQSegsAt), d_ids, d_counts, (uint32_t*)(qb + kQCursorAt), d_base, dev));
+    SP_HIP(h, launch_checked("k_sp_summarize (a wave per trace)", k_sp_summarize<kSpSumWave, 1>, dim3(n_wave), dim3(kSpSumWave),
+                             sp_sum_lds(kSpSumWave), h->stream, dev, d_list, d_ids, d_counts, d_base, (uint32_t)kSpSumWave, d_heads,
+                             d_svc, d_first, d_last));
+    SP_HIP(h, launch_checked("k_sp_summarize (a workgroup per trace)", k_sp_summarize<kSpWG, kSpSumItems>, dim3(n_group), dim3(kSpWG),
+                             sp_sum_lds(big_rows), h->stream, dev, d_list + n_wave, d_ids, d_counts, d_base, big_rows, d_heads, d_svc,
+                             d_first, d_last));
+    // only the heads cross before the entries' total is known
+    SP_HIP(h, hipMemcpyAsync(heads, d_heads, (size_t)n * sizeof(zk_sp_summary), hipMemcpyDeviceToHost, h->stream));
+    if (h->timing) SP_HIP(h, hipEventRecord(h->qev[1], h->stream));
+    SP_HIP(h, hipStreamSynchronize(h->stream));
+    h->qtimed = h->timing;
+    uint64_t need = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (heads[i].span_ts > counts[i]) return sfail(h, ZK_ERR_HIP, "a summary has more entries than its trace has rows");
+        need += heads[i].span_ts;
+    }
+    *n_out = need;
+    if (need > cap) return sfail(h, ZK_ERR_CAPACITY, "the output columns hold fewer entries than the asked traces have");
+    if (need == 0) return ZK_OK;
+    // the staged entry columns in one copy, then each trace's entries packed behind the ones before it
+    const size_t bytes = 2 * e8 + (size_t)total * 4;
+    h->ents_host.resize(bytes);
+    SP_HIP(h, hipMemcpyAsync(h->ents_host.data(), h->ents, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (h->timing) SP_HIP(h, hipEventRecord(h->qev[1], h->stream));
+    SP_HIP(h, hipStreamSynchronize(h->stream));
+    const int64_t* s_first = (const int64_t*)h->ents_host.data();
+    const int64_t* s_last = (const int64_t*)(h->ents_host.data() + e8);
+    const uint32_t* s_svc = (const uint32_t*)(h->ents_host.data() + 2 * e8);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t c = heads[i].span_ts, from = h->base_host[i];
+        if (!c) continue;
+        memcpy(out->service_id + at, s_svc + from, c * 4);
+        memcpy(out->first + at, s_first + from, c * 8);
+        memcpy(out->last + at, s_last + from, c * 8);
+        at += c;
     }
     return ZK_OK;
     ZK_GUARD_END

@@ -25,6 +25,11 @@ _M64 = 2 ** 64 - 1
 
 Row = Tuple[int, int, int, int, int, int, int]
 
+# zk_sp_summary, the 40-byte head of one asked id
+SUMMARY_HEAD = np.dtype([("trace_id", np.uint64), ("start", np.int64), ("end", np.int64), ("fragments", np.uint32),
+                         ("spans", np.uint32), ("span_ts", np.uint32), ("state", np.uint32)])
+ENTRY_COLUMNS = (("service_id", np.uint32), ("first", np.int64), ("last", np.int64))
+
 
 def _wrap64(x: int) -> int:
     """x as the JVM's Long holds it (two's complement, 64 bits)."""
@@ -397,9 +402,52 @@ class TraceSpanStore:
         """One Trace per asked id that was found, in the order asked."""
         return [Trace(rows, self.services, self.span_names) for rows in self.getSpansByTraceIds(ids)]
 
-    def getTraceSummariesByIds(self, ids) -> List[TraceSummary]:
+    def summaries(self, ids):
+        """(heads, entries) for at most ZK_SP_MAX_IDS ids (zk_sp_summaries): heads, a SUMMARY_HEAD array in
+        the order asked, and the (service_id, first, last) entries of all asked traces one after another
+        (a dict of three numpy columns of exactly the total). The sizing call, then the call that fills."""
+        keep, ptr, n, flags = self._ask(ids)
+        heads = np.zeros(n, SUMMARY_HEAD)
+        total = C.c_uint64()
+        st = self._L.zk_sp_summaries(self._h, ptr, n, flags, heads.ctypes.data, None, 0, C.byref(total))
+        if st not in (_abi.ZK_OK, _abi.ZK_ERR_CAPACITY):
+            self._check(st)
+        cols = {k: np.zeros(total.value, dt) for k, dt in ENTRY_COLUMNS}
+        if st == _abi.ZK_ERR_CAPACITY:
+            out = _abi.zk_sp_span_ts(*[cols[k].ctypes.data for k, _ in ENTRY_COLUMNS])
+            self._check(self._L.zk_sp_summaries(self._h, ptr, n, flags, heads.ctypes.data, C.byref(out), total.value,
+                                                C.byref(total)))
+        return heads, cols
+
+    def _summaries_on_device(self, ids) -> List[TraceSummary]:
+        """getTraceSummariesByIds from summaries(): the services go through the dictionary as in
+        Trace._service (lower-cased names; an entry's service id beyond the dictionary is a ValueError)."""
+        out: List[TraceSummary] = []
+        low = None if self.services is None else [s.lower() for s in self.services]
+        for part in self._chunks(ids):
+            heads, cols = self.summaries(part)
+            svc, first, last = (cols[k].tolist() for k, _ in ENTRY_COLUMNS)
+            if low is not None:
+                if svc and max(svc) >= len(low):
+                    raise ValueError("a service id beyond the services dictionary")
+                svc = [low[i] for i in svc]
+            entries = list(map(SpanTimestamp, svc, first, last))
+            at = 0
+            for tid, start, end, _, _, c, state in heads.tolist():
+                if state & _abi.ZK_SP_SUM_OVERFLOW:  # a trace too long for the device merge: the host path
+                    out += self.getTraceSummariesByIds([tid])
+                elif state & _abi.ZK_SP_SUM_TIMED:
+                    out.append(TraceSummary(tid, start, end, _to_int(_wrap64(end - start)), entries[at:at + c], []))
+                at += c
+        return out
+
+    def getTraceSummariesByIds(self, ids, on_device: bool = False) -> List[TraceSummary]:
         """QueryService.getTraceSummariesByIds: the summaries in the order asked; ids that are not found
-        and traces without a timed fragment (TraceSummary.apply yields None) are left out."""
+        and traces without a timed fragment (TraceSummary.apply yields None) are left out. on_device:
+        the summaries are merged on the device (zk_sp_summaries) and only they cross to the host; the
+        answer is the same."""
+        if on_device:
+            return self._summaries_on_device(ids)
         return [s for s in (TraceSummary.of(t) for t in self.getTracesByIds(ids)) if s is not None]
 
     # ---- timing ----------------------------------------------------------------------------------------
@@ -416,7 +464,8 @@ class TraceSpanStore:
         return dict(zip(self.EXPIRE_PHASES, out))
 
     def query_ms(self) -> float:
-        """Time (ms) on the handle's stream of the last exist or gather (zk_sp_query_ms; timing=True)."""
+        """Time (ms) on the handle's stream of the last exist, gather or summaries (zk_sp_query_ms;
+        timing=True)."""
         ms = C.c_double()
         self._check(self._L.zk_sp_query_ms(self._h, C.byref(ms)))
         return float(ms.value)
