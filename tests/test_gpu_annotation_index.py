@@ -1,6 +1,8 @@
 """The trace-id index by annotation on the device (include/zkannindex.h, zipkin_amd/annindex.py) against
 tests/axref.py and the validator's vectors (tests/golden/trace_ids_by_annotation.json). Every comparison
 is exact equality; nothing depends on the order inside a service's slice."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -103,6 +105,34 @@ def test_empty_index_and_one_entry(make):
         with pytest.raises(ZkError) as err:
             idx.trace_ids(**kw)
         assert err.value.status == _abi.ZK_ERR_INVALID_ARG
+
+
+def test_refusals_leave_the_outputs_as_they_were(make):
+    """zk_ax_trace_ids' refusals at the C ABI, as tests/test_gpu_trace_index.py has them for zk_ix_trace_ids:
+    the two calls share the select's driver behind these checks."""
+    S = 2
+    it = items_of(np.arange(6) % S, 7, 9, T0 + np.arange(6), 100 + np.arange(6))
+    idx = make(S)
+    observe(idx, it)
+    L = _abi.lib()
+    ids = (C.c_uint64 * 8)(*[0x5A5A5A5A5A5A5A5A] * 8)
+    ts = (C.c_int64 * 8)(*[0x5A5A5A5A] * 8)
+    n, m = C.c_uint32(99), C.c_uint64(99)
+    #      service, limit
+    bad = [(S, 8), (0xFFFFFFFF, 8), (0, 0), (0, _abi.ZK_AX_MAX_LIMIT + 1)]
+    for service, limit in bad:
+        assert L.zk_ax_trace_ids(idx._h, service, 7, ANY, INT64_MAX, limit, ids, ts, C.byref(n), C.byref(m)) == _abi.ZK_ERR_INVALID_ARG
+        assert L.zk_ax_last_error(idx._h)
+    assert L.zk_ax_trace_ids(idx._h, 0, 7, ANY, 0, 8, None, ts, C.byref(n), None) == _abi.ZK_ERR_INVALID_ARG
+    assert L.zk_ax_trace_ids(idx._h, 0, 7, ANY, 0, 8, ids, None, C.byref(n), None) == _abi.ZK_ERR_INVALID_ARG
+    assert L.zk_ax_trace_ids(idx._h, 0, 7, ANY, 0, 8, ids, ts, None, None) == _abi.ZK_ERR_INVALID_ARG
+    assert L.zk_ax_observe(idx._h, None, 0) == _abi.ZK_ERR_INVALID_ARG
+    assert L.zk_ax_service_counts(idx._h, None) == _abi.ZK_ERR_INVALID_ARG
+    assert list(ids) == [0x5A5A5A5A5A5A5A5A] * 8 and list(ts) == [0x5A5A5A5A] * 8
+    assert (n.value, m.value) == (99, 99)
+    # matched may be NULL, and the handle still answers
+    assert L.zk_ax_trace_ids(idx._h, 1, 7, ANY, INT64_MAX, 8, ids, ts, C.byref(n), None) == _abi.ZK_OK
+    assert [(ids[i], ts[i]) for i in range(n.value)] == axref.trace_ids(it.rows(), 1, 7, ANY, INT64_MAX, 8)[0]
 
 
 # ---- 3. the service bins' bounds -----------------------------------------------------------------------

@@ -1,6 +1,7 @@
-// zk_expire.h — the device side that the expiry of the two segment indices shares (zk_ix.hip's
-// zk_ix_expire, zk_ax.hip's zk_ax_expire): a workgroup's stretch of a segment, the services it touches,
-// and the two passes' bodies.
+// zk_expire.h — the device side of the segment indices' expiry (zk_seg_index.h's seg_expire(), which
+// includes this file and checks its constants against the indices'; the kernels are the wrappers
+// k_ix_expire_* in zk_ix.hip and k_ax_expire_* in zk_ax.hip): a workgroup's stretch of a segment, the
+// services it touches, and the two passes' bodies.
 //
 // An entry's service is not stored: a segment's entries are grouped by service and the host keeps
 // off[S + 1]. The passes get a copy of every segment's offsets (u32: a handle holds fewer than 2^32
