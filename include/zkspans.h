@@ -112,6 +112,19 @@ extern "C" {
                                   which TraceSummary.apply yields None */
 #define ZK_SP_SUM_OVERFLOW 4u  /* more than ZK_SP_SUM_MAX_ROWS rows: spans = span_ts = 0 and no entries */
 
+/* the longest trace (in rows) that zk_sp_traces merges on the device: zk_sp_summaries' bound, so that both
+   device paths overflow at the same length */
+#define ZK_SP_TRACE_MAX_ROWS 2048u
+/* zk_sp_trace.state: the ZK_SP_SUM_* bits, value for value */
+#define ZK_SP_TR_FOUND    1u
+#define ZK_SP_TR_TIMED    2u
+#define ZK_SP_TR_OVERFLOW 4u  /* more than ZK_SP_TRACE_MAX_ROWS rows: spans = services = 0, nothing emitted */
+/* zk_sp_span.bits */
+#define ZK_SP_SPAN_HAS_PARENT   1u  /* some fragment of the span carries ZK_F_HAS_PARENT */
+#define ZK_SP_SPAN_TIMED        2u  /* some fragment of the span is timed */
+#define ZK_SP_SPAN_PARENT_FOUND 4u  /* the parent id is a span of this trace */
+#define ZK_SP_SPAN_ROOT_MOST    8u  /* the trace's root-most span */
+
 typedef struct zk_sp_config {
     int32_t  device;   /* HIP device ordinal */
     uint32_t timing;   /* 1: record HIP events (zk_sp_observe_ms, zk_sp_query_ms, zk_sp_expire_ms) */
@@ -149,6 +162,30 @@ typedef struct zk_sp_span_ts {
     int64_t*  last;
 } zk_sp_span_ts;
 
+/* zk_sp_traces' head of one asked id, 48 bytes */
+typedef struct zk_sp_trace {
+    uint64_t trace_id;   /* the asked id; 0 when it is not found (the whole head is zeros then) */
+    int64_t  start;      /* as in zk_sp_summary */
+    int64_t  end;
+    uint64_t root_most;  /* the span id of getRootMostSpan; 0 when spans == 0 */
+    uint32_t fragments;  /* the trace's rows */
+    uint32_t spans;      /* its merged spans: its entries in the span column */
+    uint32_t services;   /* its (span, service) pairs: its entries in the services column */
+    uint32_t state;      /* ZK_SP_TR_* */
+} zk_sp_trace;
+
+/* one merged span of zk_sp_traces, 48 bytes */
+typedef struct zk_sp_span {
+    uint64_t span_id;
+    uint64_t parent_id;  /* 0 without ZK_SP_SPAN_HAS_PARENT (0 and 2^64 - 1 are legal parents: the bit decides) */
+    int64_t  first;      /* 0 when untimed */
+    int64_t  last;
+    uint32_t name;       /* the 16-bit span-name id, 0 for none */
+    uint32_t depth;      /* 1 for the root-most span; 0: the span is not under it */
+    uint32_t services;   /* its entries in the services column */
+    uint32_t bits;       /* ZK_SP_SPAN_* */
+} zk_sp_span;
+
 typedef struct zk_sp zk_sp;
 
 zk_status   zk_sp_create(const zk_sp_config* cfg, zk_sp** out);
@@ -162,7 +199,7 @@ const char* zk_sp_last_error(const zk_sp* sp);
    synchronises once, to read the counts it sizes the segment by (a merge, see Layout, synchronises once
    more). The scatter of the seven columns (48 B read and 48 B written per record, trace_id read once
    more) is queued on the handle's stream behind that: DEVICE columns must stay as they are until the
-   handle's next synchronising call (zk_sp_info, zk_sp_exist, zk_sp_gather, zk_sp_summaries, zk_sp_compact,
+   handle's next synchronising call (zk_sp_info, zk_sp_exist, zk_sp_gather, zk_sp_summaries, zk_sp_traces, zk_sp_compact,
    zk_sp_expire, zk_sp_observe). A record whose place falls outside its bucket's slice (it cannot while the columns
    stay as they were) is dropped, never written elsewhere. n == 0 is ZK_OK; n >= 2^32 is
    ZK_ERR_UNSUPPORTED. */
@@ -237,12 +274,62 @@ zk_status   zk_sp_gather(zk_sp* sp, const uint64_t* ids, uint32_t n, uint32_t fl
    the handle as it was. */
 zk_status   zk_sp_summaries(zk_sp* sp, const uint64_t* ids, uint32_t n, uint32_t flags, zk_sp_summary* heads,
                             zk_sp_span_ts* out, uint64_t cap, uint64_t* n_out);
+/* The asked traces MERGED: per trace a head, its merged spans with parent, name, times and DEPTH, and the
+   spans' services: what QueryService.getTraceCombosByIds needs of a trace (Trace.scala's mergeBySpanId,
+   getRootMostSpan and toSpanDepths, TraceSummary.scala), at record granularity, without a fragment crossing
+   to the host. For one asked id, as a function of the store's multiset of fragments alone:
+     merged spans  the fragments grouped by span_id; timed, first, last and the services of a span as in
+                   zk_sp_summaries.
+     parent        of a span: the parent_id of its first fragment in CANONICAL ORDER that carries
+                   ZK_F_HAS_PARENT, which is the minimum unsigned parent_id over those fragments. A span
+                   without such a fragment has NO parent: that is a bit (ZK_SP_SPAN_HAS_PARENT), never a
+                   value; parent ids 0 and 2^64 - 1 are legal.
+     name          of a span: the name id (flags >> ZK_F_NAME_SHIFT) of its first fragment in canonical order
+                   (parent_id, first_ts, last_ts, service_id, flags) whose name id is non-zero, else 0. This
+                   order reads the RAW first_ts / last_ts of untimed fragments too (nowhere else are they read).
+     SPAN ORDER    by first ascending (signed), an untimed span as INT64_MAX; ties by span_id ascending as
+                   unsigned (a timed span with first == INT64_MAX and an untimed one tie and go by id).
+     root-most     the first span in span order without a parent. When every span has one: from the first
+                   span in span order upwards through the parents that are spans of this trace, to the span
+                   whose parent is not one; on a parent chain that closes on itself, the first span the walk
+                   meets twice (the reference does not terminate on such a chain: a stated choice).
+     depth         of span s: 1 + the fewest parent hops from s to the root-most span; 0 when the chain from
+                   s (every span has at most one parent, so there is one chain) never reaches it. The
+                   root-most span is at depth 1 whatever its own parent is.
+     ids, n, flags   as for zk_sp_gather; n == 0 is ZK_OK with n_out[0] = n_out[1] = 0.
+     heads     n HOST structs, in the order asked; a duplicated id is answered as often as asked; an id that is
+               not found gets a head of zeros. fragments, start, end, FOUND and TIMED are plain reductions,
+               exact for a trace of any length; a trace of more than ZK_SP_TRACE_MAX_ROWS rows gets
+               ZK_SP_TR_OVERFLOW, spans = services = 0 and root_most = 0, and emits nothing (the caller merges
+               it from zk_sp_gather's rows).
+     spans     cap_spans HOST structs: the spans of ids[0] in span order, then those of ids[1], and so on.
+     services  cap_services HOST entries: one service_id per (span, service) pair, the spans in the order of
+               `spans`, each span's ids ascending (zk_sp_span.services of them).
+               spans and services may be NULL only with their cap at 0.
+     n_out     n_out[0] = the total of merged spans, n_out[1] = the total of (span, service) pairs.
+   When either cap is below its total the call returns ZK_ERR_CAPACITY with both totals and the heads
+   written; no span and no service is written. Both caps 0 with NULL buffers is the sizing call. An empty
+   store answers without a device pass.
+   The passes are zk_sp_summaries' (count pass, synchronisation and prefix sum, write pass into the handle's
+   staging, the same two work lists: a trace of up to ZK_SP_SUM_WAVE_ROWS rows per wave, a longer one per
+   workgroup of 256), with k_sp_trace in k_sp_summarize's place: 66 B of LDS per row; a sort of the rows by
+   the full canonical key, the fold per span onto its first row (times, the first fragment with a parent,
+   the first named fragment), every span's parent by binary search, a second sort into span order that also
+   brings equal (span, service) pairs together, the root-most span, the depths by pointer doubling
+   (ceil(log2(spans)) rounds), a prefix sum over the sorted rows that places every span and every pair. Both
+   are staged at their trace's own row base (spans <= rows, pairs <= rows). The heads (48 B per id) are
+   copied and the call synchronises; if both outputs fit, the staged spans and services (52 B per row)
+   follow in one copy and are packed per trace on the host. Staging is grown on use; a refused allocation
+   is ZK_ERR_CAPACITY and leaves the handle as it was. */
+zk_status   zk_sp_traces(zk_sp* sp, const uint64_t* ids, uint32_t n, uint32_t flags, zk_sp_trace* heads,
+                         zk_sp_span* spans, uint64_t cap_spans, uint32_t* services, uint64_t cap_services,
+                         uint64_t n_out[2]);
 /* Device time in ms of the last zk_sp_observe that added a segment: the count, the sizing step (the
    counts' copy and, when the segment bound was met, the merge), the scatter. Needs zk_sp_config.timing;
    waits for the scatter. */
 zk_status   zk_sp_observe_ms(zk_sp* sp, double out[3]);
-/* Time in ms on the handle's stream of the last zk_sp_exist, zk_sp_gather or zk_sp_summaries that ran a
-   pass, from its first pass to its last copy (the host's prefix sum included, the host's sort not). Needs
+/* Time in ms on the handle's stream of the last zk_sp_exist, zk_sp_gather, zk_sp_summaries or zk_sp_traces
+   that ran a pass, from its first pass to its last copy (the host's prefix sum included, the host's sort not). Needs
    zk_sp_config.timing. */
 zk_status   zk_sp_query_ms(zk_sp* sp, double* ms);
 

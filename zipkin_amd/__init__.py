@@ -11,7 +11,8 @@ from .durations import TraceDurationIndex, TraceIdDuration, merge_top  # noqa: F
 from .nameindex import IndexedTraceId, TraceNameIndex, merge_trace_ids  # noqa: F401
 from .annindex import AnnotationItems, DeviceAnnotationItems, TraceAnnotationIndex, get_trace_ids, trace_ids_intersect  # noqa: F401
 from .retention import IndexRetention, SpanRetention  # noqa: F401
-from .spanstore import SUMMARY_HEAD, Span, SpanTimestamp, Timespan, Trace, TraceSpanStore, TraceSummary  # noqa: F401
+from .spanstore import (SUMMARY_HEAD, TRACE_HEAD, TRACE_SPAN, Span, SpanTimestamp, Timespan, Trace, TraceCombo,  # noqa: F401
+                        TraceSpanStore, TraceSummary)
 from .windows import WindowedAggregateJob, WindowPartition  # noqa: F401
 from . import table  # noqa: F401
 
@@ -48,5 +49,8 @@ __all__ = [
     "SpanTimestamp",
     "Timespan",
     "SUMMARY_HEAD",
+    "TRACE_HEAD",
+    "TRACE_SPAN",
+    "TraceCombo",
     "BYTES_PER_RECORD",
 ]

@@ -361,6 +361,42 @@ class zk_sp_span_ts(C.Structure):
     ]
 
 
+ZK_SP_TRACE_MAX_ROWS = 2048
+ZK_SP_TR_FOUND = 1
+ZK_SP_TR_TIMED = 2
+ZK_SP_TR_OVERFLOW = 4
+ZK_SP_SPAN_HAS_PARENT = 1
+ZK_SP_SPAN_TIMED = 2
+ZK_SP_SPAN_PARENT_FOUND = 4
+ZK_SP_SPAN_ROOT_MOST = 8
+
+
+class zk_sp_trace(C.Structure):
+    _fields_ = [
+        ("trace_id", C.c_uint64),
+        ("start", C.c_int64),
+        ("end", C.c_int64),
+        ("root_most", C.c_uint64),
+        ("fragments", C.c_uint32),
+        ("spans", C.c_uint32),
+        ("services", C.c_uint32),
+        ("state", C.c_uint32),
+    ]
+
+
+class zk_sp_span(C.Structure):
+    _fields_ = [
+        ("span_id", C.c_uint64),
+        ("parent_id", C.c_uint64),
+        ("first", C.c_int64),
+        ("last", C.c_int64),
+        ("name", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("services", C.c_uint32),
+        ("bits", C.c_uint32),
+    ]
+
+
 ZK_RT_WITH_DEPS = 0
 ZK_RT_ONLY = 1
 ZK_RL_ANY_RPC = 0xFFFFFFFF
@@ -663,6 +699,7 @@ _SIGNATURES = [
     ("zk_sp_exist", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8)]),
     ("zk_sp_gather", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _U32P, C.POINTER(zk_sp_rows), C.c_uint64, _U64P]),
     ("zk_sp_summaries", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.POINTER(zk_sp_span_ts), C.c_uint64, _U64P]),
+    ("zk_sp_traces", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
     ("zk_sp_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_sp_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_sp_expire", C.c_int, [_P, C.c_int64, _P, _P, C.c_uint32, _U64P]),

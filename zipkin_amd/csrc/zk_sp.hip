@@ -27,6 +27,12 @@
 //                 atomics, the first row of every (span, service) pair of a timed span marked as an ENTRY,
 //                 and the rows sorted again by (entry, first, span id, service): the entries are then the
 //                 leading rows, written behind the trace's row base. 31 B of LDS per row.
+//   k_sp_trace    zk_sp_traces' pass over the same staged rows, on the same two work lists: the merged spans
+//                 themselves. The rows are sorted by the full canonical key, every span folded onto its
+//                 first row (times, the first fragment with a parent, the first named one), its parent found
+//                 by binary search, the rows sorted again into span order, the root-most span chosen, the
+//                 depths computed by pointer doubling, and a prefix sum over the sorted rows places every span
+//                 (48 B) and every (span, service) pair behind the trace's row base. 66 B of LDS per row.
 //   k_sp_end_fold, k_sp_end_pins, k_sp_end_mark, k_sp_expire_rewrite   zk_sp_expire's passes: per range of
 //                 buckets a scratch table trace id -> end in HBM (the fold over every segment's slice of
 //                 the range, 20 B per entry), the pins' verdicts, then one mark bit per entry and the
@@ -89,6 +95,19 @@ static_assert(kSpSumMaxRows >= 2048 && kSpSumMaxRows <= 65536 && (kSpSumMaxRows 
 static_assert(kSumLdsHead + kSumLdsPerRow * kSpSumMaxRows <= 65536, "a trace of ZK_SP_SUM_MAX_ROWS rows fits 64 KiB of LDS");
 static_assert(sizeof(zk_sp_summary) == 40, "zk_sp_summary's layout");
 static_assert(kSpSumWave == 64, "a wave holds one row per lane");
+
+// the merged traces (k_sp_trace): the same bound, work lists and thread shapes as the summaries
+constexpr uint32_t kSpTrMaxRows = ZK_SP_TRACE_MAX_ROWS;
+constexpr uint32_t kTrNone = 0xFFFFFFFFu;             // no sorted position
+constexpr uint32_t kTrNoRow = 0xFFFFu;                // no row number (a 16-bit index)
+constexpr uint32_t kTrHead = 1u, kTrSpanTimed = 2u, kTrSeen = 4u;  // a head's bits in LDS
+constexpr size_t kTrLdsHead = 64;    // start, end [8 B], timed, spans, root position, root [4 B], the waves' totals [4 x 4 B]
+constexpr size_t kTrLdsPerRow = 66;  // span, parent, first, last [8 B], svc, fl, ppos, npos, nsvc, bits [4 B], ord, head, phead, jump, dist [2 B]
+static_assert(kSpTrMaxRows == kSpSumMaxRows, "both device merges overflow at the same length");
+static_assert(kTrLdsHead + kTrLdsPerRow * kSpTrMaxRows <= 160 * 1024, "a trace of ZK_SP_TRACE_MAX_ROWS rows fits the 160 KiB of a CU");
+static_assert(kSpTrMaxRows < kTrNoRow && kSpTrMaxRows < 0x10000u, "row numbers and both prefix sums fit 16 bits");
+static_assert(sizeof(zk_sp_trace) == 48 && sizeof(zk_sp_span) == 48, "zk_sp_trace's and zk_sp_span's layouts");
+constexpr size_t sp_tr_lds(uint32_t rows) { return kTrLdsHead + kTrLdsPerRow * rows; }
 
 // LDS of one k_sp_summarize workgroup whose launch admits traces of up to `rows` rows (a power of two >= 64)
 constexpr size_t sp_sum_lds(uint32_t rows) { return kSumLdsHead + kSumLdsPerRow * rows; }
@@ -537,6 +556,379 @@ __global__ __launch_bounds__(T) void k_sp_summarize(SpCols rows, const uint32_t*
     }
 }
 
+// ---- the merged traces ---------------------------------------------------------------------------------
+// One trace's rows in LDS for k_sp_trace, by ROW NUMBER. Of every row: span, parent, first, last ([8 B]; the
+// times RAW ^ sign until the first sort is done, then the row's contribution to its span's times, all ones /
+// 0 for an untimed row), svc, fl [4 B], head [2 B]: the row number of its span's HEAD, the span's first row in
+// canonical order. A head carries its span: first / last folded, parent = the span's parent id, ppos / npos
+// [4 B]: the first sorted position of a fragment with a parent / with a name (all ones: none; npos then
+// becomes the name id), nsvc [4 B]: the span's (span, service) pairs, bits [4 B], phead [2 B]: the head of
+// its parent (kTrNoRow: not a span of the trace), jump / dist [2 B]: the pointer doubling's state. ord
+// [2 B]: the row numbers in sorted order; a number at or past n is padding.
+struct SpTrRows {
+    unsigned long long* span;
+    unsigned long long* parent;
+    unsigned long long* first;
+    unsigned long long* last;
+    uint32_t* svc;
+    uint32_t* fl;
+    uint32_t* ppos;
+    uint32_t* npos;
+    uint32_t* nsvc;
+    uint32_t* bits;
+    uint16_t* ord;
+    uint16_t* head;
+    uint16_t* phead;
+    uint16_t* jump;
+    uint16_t* dist;
+    uint32_t n;
+};
+
+__device__ inline bool sp_tr_has_svc(uint32_t fl) { return (fl & (ZK_F_SVC_CLIENT | ZK_F_SVC_SERVER)) != 0u; }
+
+// the header's canonical order inside a trace (the times are held ^ sign); padding last
+__device__ inline bool sp_tr_canonical(const SpTrRows& t, uint32_t a, uint32_t b) {
+    if (b >= t.n) return a < t.n;
+    if (a >= t.n) return false;
+    if (t.span[a] != t.span[b]) return t.span[a] < t.span[b];
+    if (t.parent[a] != t.parent[b]) return t.parent[a] < t.parent[b];
+    if (t.first[a] != t.first[b]) return t.first[a] < t.first[b];
+    if (t.last[a] != t.last[b]) return t.last[a] < t.last[b];
+    if (t.svc[a] != t.svc[b]) return t.svc[a] < t.svc[b];
+    return t.fl[a] < t.fl[b];
+}
+
+// SPAN ORDER over all rows: (the span's first, an untimed span's being all ones = INT64_MAX ^ sign; span id),
+// inside a span the service-bearing rows by service, then the rest; padding last
+__device__ inline bool sp_tr_span_order(const SpTrRows& t, uint32_t a, uint32_t b) {
+    if (b >= t.n) return a < t.n;
+    if (a >= t.n) return false;
+    const uint32_t ha = t.head[a], hb = t.head[b];
+    if (ha != hb) {
+        if (t.first[ha] != t.first[hb]) return t.first[ha] < t.first[hb];
+        return t.span[a] < t.span[b];
+    }
+    const bool sa = sp_tr_has_svc(t.fl[a]), sb = sp_tr_has_svc(t.fl[b]);
+    if (sa != sb) return sa;
+    return sa && t.svc[a] < t.svc[b];
+}
+
+// sp_sum_sort over SpTrRows: a bitonic sort of ord[0, P) (P a power of two >= 2, the same for the whole
+// workgroup). Ends behind a barrier.
+template <int T, bool (*Less)(const SpTrRows&, uint32_t, uint32_t)>
+__device__ inline void sp_tr_sort(const SpTrRows& t, uint32_t P) {
+    for (uint32_t k = 2; k <= P; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t w = threadIdx.x; w < P / 2; w += T) {
+                const uint32_t i = ((w & ~(j - 1u)) << 1) | (w & (j - 1u)), x = i | j;
+                const uint16_t a = t.ord[i], b = t.ord[x];
+                if ((i & k) == 0 ? Less(t, b, a) : Less(t, a, b)) {
+                    t.ord[i] = b;
+                    t.ord[x] = a;
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// the first sorted position in [0, hi) whose row's span id is not below s (ord in canonical order)
+__device__ inline uint32_t sp_tr_lower(const SpTrRows& t, unsigned long long s, uint32_t hi) {
+    uint32_t a = 0, z = hi;
+    while (a < z) {
+        const uint32_t mid = (a + z) >> 1;
+        if (t.span[t.ord[mid]] < s) a = mid + 1; else z = mid;
+    }
+    return a;
+}
+
+// The merged trace of asked id list[blockIdx.x] from its staged rows [base[q], base[q] + counts[q]): the head
+// into heads[q]; its spans, in span order, and its (span, service) pairs behind the rows' OWN base in o_spans
+// and o_svc (a trace has at most as many spans, and as many pairs, as rows: no prefix sum over the traces is
+// needed, and the host packs per trace). T threads hold up to T * I rows; the launch's LDS admits `cap` rows.
+// A trace above either, or above ZK_SP_TRACE_MAX_ROWS, gets the reductions and OVERFLOW: nothing of it goes to
+// LDS. Every bound that guards a barrier (n, cap, P, the span count) is the same for the whole workgroup.
+template <int T, int I>
+__global__ __launch_bounds__(T) void k_sp_trace(SpCols rows, const uint32_t* __restrict__ list,
+                                                const unsigned long long* __restrict__ ids,
+                                                const uint32_t* __restrict__ counts,
+                                                const unsigned long long* __restrict__ base, uint32_t cap,
+                                                zk_sp_trace* __restrict__ heads, zk_sp_span* __restrict__ o_spans,
+                                                uint32_t* __restrict__ o_svc) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_tr[];
+    unsigned long long* s_start = (unsigned long long*)s_tr;
+    unsigned long long* s_end = s_start + 1;
+    uint32_t* s_cnt = (uint32_t*)(s_tr + 16);   // timed, spans, the root-most span's sorted position, its head
+    uint32_t* s_wave = (uint32_t*)(s_tr + 32);  // the prefix sum's totals per wave (T / 64 <= 4 of them)
+    const uint32_t q = list[blockIdx.x];
+    const uint32_t n = counts[q];
+    const unsigned long long r0 = base[q];
+    if (n == 0 || r0 + n > rows.n) return;  // (not a staged trace: never on a work list)
+    const bool fits = n <= cap && n <= kSpTrMaxRows && n <= (uint32_t)(T * I);
+    SpTrRows t;
+    t.span = (unsigned long long*)(s_tr + kTrLdsHead);
+    t.parent = t.span + cap;
+    t.first = t.parent + cap;
+    t.last = t.first + cap;
+    t.svc = (uint32_t*)(t.last + cap);
+    t.fl = t.svc + cap;
+    t.ppos = t.fl + cap;
+    t.npos = t.ppos + cap;
+    t.nsvc = t.npos + cap;
+    t.bits = t.nsvc + cap;
+    t.ord = (uint16_t*)(t.bits + cap);
+    t.head = t.ord + cap;
+    t.phead = t.head + cap;
+    t.jump = t.phead + cap;
+    t.dist = t.jump + cap;
+    t.n = n;
+    uint32_t P = 2;
+    while (P < n && P < cap) P <<= 1;
+    if (threadIdx.x == 0) {
+        *s_start = kSpNone;
+        *s_end = 0ull;
+        s_cnt[0] = s_cnt[1] = 0u;
+        s_cnt[2] = s_cnt[3] = kTrNone;
+    }
+    __syncthreads();
+    // 1. the rows into LDS (the raw times of untimed rows too: the canonical order reads them), the reductions
+    unsigned long long lo = kSpNone, hi = 0ull;
+    bool any = false;
+    for (uint32_t i = threadIdx.x; i < n; i += T) {
+        const unsigned long long at = r0 + i;
+        const uint32_t f = rows.fl[at];
+        const bool timed = f & ZK_F_HAS_ANNOTATIONS;
+        if (timed || fits) {
+            const unsigned long long a = (unsigned long long)rows.first[at] ^ kSpSign;
+            const unsigned long long z = (unsigned long long)rows.last[at] ^ kSpSign;
+            if (timed) {
+                lo = a < lo ? a : lo;
+                hi = z > hi ? z : hi;
+                any = true;
+            }
+            if (fits) {
+                t.span[i] = rows.span[at];
+                t.parent[i] = rows.parent[at];
+                t.first[i] = a;
+                t.last[i] = z;
+                t.svc[i] = rows.svc[at];
+                t.fl[i] = f;
+                t.ppos[i] = t.npos[i] = kTrNone;
+                t.nsvc[i] = 0u;
+                t.bits[i] = 0u;
+                t.phead[i] = kTrNoRow;
+            }
+        }
+    }
+    if (fits)
+        for (uint32_t i = threadIdx.x; i < P; i += T) t.ord[i] = (uint16_t)i;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long ol = __shfl_down(lo, off), oh = __shfl_down(hi, off);
+        lo = ol < lo ? ol : lo;
+        hi = oh > hi ? oh : hi;
+    }
+    const bool wave_any = __ballot(any) != 0ull;
+    if (lane_id() == 0 && wave_any) {
+        atomicMin(s_start, lo);
+        atomicMax(s_end, hi);
+        atomicOr(&s_cnt[0], 1u);
+    }
+    __syncthreads();
+    zk_sp_trace hd;
+    hd.trace_id = ids[q];
+    hd.start = s_cnt[0] ? (long long)(*s_start ^ kSpSign) : 0;
+    hd.end = s_cnt[0] ? (long long)(*s_end ^ kSpSign) : 0;
+    hd.root_most = 0ull;
+    hd.fragments = n;
+    hd.spans = hd.services = 0u;
+    hd.state = ZK_SP_TR_FOUND | (s_cnt[0] ? ZK_SP_TR_TIMED : 0u);
+    if (!fits) {
+        hd.state |= ZK_SP_TR_OVERFLOW;
+        if (threadIdx.x == 0) heads[q] = hd;
+        return;
+    }
+    // 2. canonical order: the rows of a span lie together, the first with a parent and the first named first
+    sp_tr_sort<T, sp_tr_canonical>(t, P);
+    // 3. the fold. Every row finds its span's head; its own times become its contribution to the span's.
+    uint32_t head_of[I];
+#pragma unroll
+    for (int k = 0; k < I; ++k) {
+        const uint32_t p = threadIdx.x + (uint32_t)k * T;
+        head_of[k] = kTrNoRow;
+        if (p < n) {
+            const uint32_t r = t.ord[p];
+            const uint32_t a = sp_tr_lower(t, t.span[r], p);
+            const uint32_t h = t.ord[a];
+            head_of[k] = h;
+            t.head[r] = (uint16_t)h;
+            if (!(t.fl[r] & ZK_F_HAS_ANNOTATIONS)) {
+                t.first[r] = kSpNone;
+                t.last[r] = 0ull;
+            }
+            if (a == p) {
+                t.bits[r] = kTrHead;
+                atomicAdd(&s_cnt[1], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    // only heads are updated, and only with atomics; what the others read here does not change
+#pragma unroll
+    for (int k = 0; k < I; ++k) {
+        const uint32_t p = threadIdx.x + (uint32_t)k * T;
+        if (p < n) {
+            const uint32_t r = t.ord[p], h = head_of[k], f = t.fl[r];
+            if (f & ZK_F_HAS_ANNOTATIONS) {
+                if (h != r) {
+                    atomicMin(&t.first[h], t.first[r]);
+                    atomicMax(&t.last[h], t.last[r]);
+                }
+                atomicOr(&t.bits[h], kTrSpanTimed);
+            }
+            if (f & ZK_F_HAS_PARENT) atomicMin(&t.ppos[h], p);
+            if (f >> ZK_F_NAME_SHIFT) atomicMin(&t.npos[h], p);
+        }
+    }
+    __syncthreads();
+    // 4. per span (its head's thread): the parent id, the parent's head by binary search, the name id. A head
+    // reads and writes rows of its own span alone, and every head's span id.
+#pragma unroll
+    for (int k = 0; k < I; ++k) {
+        const uint32_t p = threadIdx.x + (uint32_t)k * T;
+        if (p < n && head_of[k] == t.ord[p]) {
+            const uint32_t h = head_of[k];
+            const uint32_t pp = t.ppos[h], np = t.npos[h];
+            if (pp < n) {
+                const unsigned long long pid = t.parent[t.ord[pp]];
+                t.parent[h] = pid;
+                const uint32_t a = sp_tr_lower(t, pid, n);
+                if (a < n && t.span[t.ord[a]] == pid) t.phead[h] = t.ord[a];
+            }
+            t.npos[h] = np < n ? t.fl[t.ord[np]] >> ZK_F_NAME_SHIFT : 0u;
+        }
+    }
+    __syncthreads();
+    // 5. span order; equal (span, service) pairs lie together
+    sp_tr_sort<T, sp_tr_span_order>(t, P);
+    // 6. over the sorted positions, I consecutive ones per thread: a span's first position, a pair's first
+    // position (counted into the span), the first span without a parent; the prefix sum of both marks
+    // (16 bits each in one word: at most n <= 2048 of either)
+    uint32_t mark[I], sum = 0u;
+#pragma unroll
+    for (int k = 0; k < I; ++k) {
+        const uint32_t p = threadIdx.x * (uint32_t)I + (uint32_t)k;
+        mark[k] = 0u;
+        if (p < n) {
+            const uint32_t r = t.ord[p], h = t.head[r];
+            const uint32_t prev = p ? t.ord[p - 1] : r;
+            const bool start = p == 0 || t.head[prev] != h;
+            const bool pair = sp_tr_has_svc(t.fl[r]) && (start || !sp_tr_has_svc(t.fl[prev]) || t.svc[prev] != t.svc[r]);
+            if (pair) atomicAdd(&t.nsvc[h], 1u);
+            if (start && t.ppos[h] == kTrNone) atomicMin(&s_cnt[2], p);
+            mark[k] = (start ? 1u : 0u) | (pair ? 0x10000u : 0u);
+            sum += mark[k];
+        }
+    }
+    uint32_t inc = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(inc, d);
+        if ((int)lane_id() >= d) inc += o;
+    }
+    if (lane_id() == 63) s_wave[threadIdx.x >> 6] = inc;
+    __syncthreads();
+    // 7. the root-most span: the first span in span order without a parent, else one lane walks up from the
+    // first span through the parents the trace holds, to a span without one here or to the first it meets twice
+    if (threadIdx.x == 0) {
+        uint32_t s;
+        if (s_cnt[2] < n) {
+            s = t.head[t.ord[s_cnt[2]]];
+        } else {
+            s = t.head[t.ord[0]];
+            for (uint32_t step = 0; step < n && t.phead[s] != kTrNoRow && !(t.bits[s] & kTrSeen); ++step) {
+                t.bits[s] |= kTrSeen;
+                s = t.phead[s];
+            }
+        }
+        s_cnt[3] = s;
+    }
+    __syncthreads();
+    const uint32_t root = s_cnt[3], S = s_cnt[1];
+    // 8. the depths by pointer doubling over the heads: (jump, dist) = an ancestor and the hops to it. The
+    // root-most span and a span whose parent is not in the trace (or is itself) are terminals, jump = self.
+    // After ceil(log2(S)) rounds every chain that ends has reached its terminal; one that does not (a cycle
+    // away from the root-most span) has dist <= 2^rounds <= 2048.
+    for (uint32_t r = threadIdx.x; r < n; r += T)
+        if (t.bits[r] & kTrHead) {
+            const bool term = r == root || t.phead[r] == kTrNoRow;
+            t.jump[r] = (uint16_t)(term ? r : t.phead[r]);
+            t.dist[r] = term ? 0 : 1;
+        }
+    __syncthreads();
+    for (uint32_t reach = 1; reach < S; reach <<= 1) {
+        uint16_t nj[I], nd[I];
+#pragma unroll
+        for (int k = 0; k < I; ++k) {
+            const uint32_t r = threadIdx.x + (uint32_t)k * T;
+            nj[k] = kTrNoRow;
+            nd[k] = 0;
+            if (r < n && (t.bits[r] & kTrHead)) {
+                const uint32_t j = t.jump[r], jj = t.jump[j];
+                if (jj != j) {
+                    nj[k] = (uint16_t)jj;
+                    nd[k] = (uint16_t)(t.dist[r] + t.dist[j]);
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < I; ++k) {
+            const uint32_t r = threadIdx.x + (uint32_t)k * T;
+            if (nj[k] != kTrNoRow) {
+                t.jump[r] = nj[k];
+                t.dist[r] = nd[k];
+            }
+        }
+        __syncthreads();
+    }
+    // 9. the spans and the pairs behind the trace's own row base (places < n: r0 + n <= rows.n)
+    uint32_t before = inc - sum;
+    for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) before += s_wave[w];
+#pragma unroll
+    for (int k = 0; k < I; ++k) {
+        const uint32_t p = threadIdx.x * (uint32_t)I + (uint32_t)k;
+        if (p < n) {
+            const uint32_t r = t.ord[p];
+            const uint32_t si = before & 0xFFFFu, pi = before >> 16;
+            if ((mark[k] & 1u) && si < n) {
+                const uint32_t h = t.head[r];
+                const bool timed = t.bits[h] & kTrSpanTimed, has_parent = t.ppos[h] != kTrNone;
+                zk_sp_span o;
+                o.span_id = t.span[h];
+                o.parent_id = has_parent ? t.parent[h] : 0ull;
+                o.first = timed ? (long long)(t.first[h] ^ kSpSign) : 0;
+                o.last = timed ? (long long)(t.last[h] ^ kSpSign) : 0;
+                o.name = t.npos[h];
+                o.depth = t.jump[h] == root ? (uint32_t)t.dist[h] + 1u : 0u;
+                o.services = t.nsvc[h];
+                o.bits = (has_parent ? ZK_SP_SPAN_HAS_PARENT : 0u) | (timed ? ZK_SP_SPAN_TIMED : 0u) |
+                         (t.phead[h] != kTrNoRow ? ZK_SP_SPAN_PARENT_FOUND : 0u) | (h == root ? ZK_SP_SPAN_ROOT_MOST : 0u);
+                o_spans[r0 + si] = o;
+            }
+            if ((mark[k] & 0x10000u) && pi < n) o_svc[r0 + pi] = t.svc[r];
+            before += mark[k];
+        }
+    }
+    if (threadIdx.x == 0) {
+        uint32_t all = 0u;
+        for (uint32_t w = 0; w < (uint32_t)(T / 64); ++w) all += s_wave[w];
+        hd.root_most = t.span[root];
+        hd.spans = all & 0xFFFFu;
+        hd.services = all >> 16;
+        heads[q] = hd;
+    }
+}
+
 // ---- expiry --------------------------------------------------------------------------------------------
 // A segment as the expiry's passes see it: its columns and where its mark words begin.
 struct SpXSeg {
@@ -791,7 +1183,10 @@ struct zk_sp {
     void* rows = nullptr;    // the write pass's rows, seven columns
     void* sum_heads = nullptr;  // the summaries' heads (ZK_SP_MAX_IDS of them)
     void* ents = nullptr;       // the summaries' entries at their rows' bases: first, last [8 B], service [4 B]
-    size_t stage_bytes = 0, mplan_bytes = 0, rows_bytes = 0, ents_bytes = 0;
+    void* tr_heads = nullptr;   // the merged traces' heads (ZK_SP_MAX_IDS of them)
+    void* tr_out = nullptr;     // their spans [48 B], then their services [4 B], at their rows' bases
+    size_t stage_bytes = 0, mplan_bytes = 0, rows_bytes = 0, ents_bytes = 0, tr_bytes = 0;
+    std::vector<uint8_t> tr_host;
     std::vector<uint32_t> sum_counts_host, sum_list_host;
     std::vector<uint8_t> ents_host;
     std::vector<uint32_t> counts_host, cursor_host, off_host;  // (queued copies read the last two: they change only behind a synchronisation)
@@ -958,6 +1353,52 @@ zk_status check_ask(zk_sp* h, const uint64_t* ids, uint32_t n, uint32_t flags) {
     if (flags & ~ZK_BATCH_DEVICE_PTRS) return sfail(h, ZK_ERR_INVALID_ARG, "unknown flag");
     if (n > ZK_SP_MAX_IDS) return sfail(h, ZK_ERR_INVALID_ARG, "more than ZK_SP_MAX_IDS ids");
     if (n && !ids) return sfail(h, ZK_ERR_INVALID_ARG, "null argument");
+    return ZK_OK;
+}
+
+// The passes zk_sp_summaries and zk_sp_traces share: the count pass, the rows' bases, the two work lists (the
+// traces a wave takes, then the ones a workgroup takes; big_rows = the LDS rows of the workgroups' launch,
+// sized by the longest trace among them of at most max_rows rows), and the write pass into the handle's
+// staging, queued. total == 0: nothing was found and nothing is queued. counts = h->sum_counts_host.
+struct SpStaged {
+    uint64_t total = 0;
+    uint32_t n_wave = 0, n_group = 0, big_rows = kSpSumWave;
+    SpCols dev = {};
+};
+
+zk_status stage_traces(zk_sp* h, const uint64_t* ids, uint32_t n, uint32_t flags, uint32_t max_rows, SpStaged* s) {
+    zk_status st;
+    uint32_t parts = 1;
+    h->sum_counts_host.resize(n);
+    const uint32_t* counts = h->sum_counts_host.data();
+    if ((st = find_count(h, ids, n, flags, h->sum_counts_host.data(), &parts)) != ZK_OK) return st;
+    h->base_host.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        h->base_host[i] = s->total;
+        s->total += counts[i];
+    }
+    if (s->total == 0) return ZK_OK;
+    h->sum_list_host.clear();
+    for (uint32_t i = 0; i < n; ++i)
+        if (counts[i] && counts[i] <= (uint32_t)kSpSumWave) h->sum_list_host.push_back(i);
+    s->n_wave = (uint32_t)h->sum_list_host.size();
+    for (uint32_t i = 0; i < n; ++i)
+        if (counts[i] > (uint32_t)kSpSumWave) {
+            h->sum_list_host.push_back(i);
+            if (counts[i] <= max_rows)
+                while (s->big_rows < counts[i]) s->big_rows <<= 1;
+        }
+    s->n_group = (uint32_t)h->sum_list_host.size() - s->n_wave;
+    if ((st = grow(h, &h->rows, &h->rows_bytes, Block::cols_bytes(s->total), "the gathered rows (48 B each)")) != ZK_OK) return st;
+    uint8_t* qb = (uint8_t*)h->q;
+    s->dev = Block::view(h->rows, s->total, false);
+    SP_HIP(h, hipMemcpyAsync(qb + kQBaseAt, h->base_host.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    SP_HIP(h, hipMemcpyAsync(qb + kQListAt, h->sum_list_host.data(), h->sum_list_host.size() * 4, hipMemcpyHostToDevice, h->stream));
+    SP_HIP(h, hipMemsetAsync(qb + kQCursorAt, 0, (size_t)n * 4, h->stream));
+    SP_HIP(h, launch_checked("k_sp_find_write", k_sp_find_write, dim3(n, (uint32_t)h->segs.size(), parts), dim3(kSpWG), 0, h->stream,
+                             (const SpCols*)(qb + kQSegsAt), (const unsigned long long*)(qb + kQIdsAt),
+                             (const uint32_t*)(qb + kQCountsAt), (uint32_t*)(qb + kQCursorAt),
+                             (const unsigned long long*)(qb + kQBaseAt), s->dev));
     return ZK_OK;
 }
 
@@ -1170,7 +1611,7 @@ zk_status zk_sp_destroy(zk_sp* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     free_segments(h);
-    for (void* p : {h->obs, h->stage, h->mplan, h->q, h->rows, h->xplan, h->sum_heads, h->ents})
+    for (void* p : {h->obs, h->stage, h->mplan, h->q, h->rows, h->xplan, h->sum_heads, h->ents, h->tr_heads, h->tr_out})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : h->oev)
         if (e) (void)hipEventDestroy(e);
@@ -1480,39 +1921,18 @@ zk_status zk_sp_summaries(zk_sp* h, const uint64_t* ids, uint32_t n, uint32_t fl
     memset(heads, 0, (size_t)n * sizeof(zk_sp_summary));
     if (h->segs.empty()) return ZK_OK;
     SP_HIP(h, hipSetDevice(h->device));
-    // the two passes of zk_sp_gather: the rows of the asked traces into the handle's staging
-    uint32_t parts = 1;
-    h->sum_counts_host.resize(n);
-    uint32_t* counts = h->sum_counts_host.data();
-    if ((st = find_count(h, ids, n, flags, counts, &parts)) != ZK_OK) return st;
-    h->base_host.resize(n);
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        h->base_host[i] = total;
-        total += counts[i];
-    }
-    if (total == 0) return ZK_OK;
-    // the work lists: the traces a wave takes, then the ones a workgroup takes; the workgroups' LDS is sized
-    // by the longest trace among them that is merged on the device
-    h->sum_list_host.clear();
-    for (uint32_t i = 0; i < n; ++i)
-        if (counts[i] && counts[i] <= (uint32_t)kSpSumWave) h->sum_list_host.push_back(i);
-    const uint32_t n_wave = (uint32_t)h->sum_list_host.size();
-    uint32_t big_rows = kSpSumWave;
-    for (uint32_t i = 0; i < n; ++i)
-        if (counts[i] > (uint32_t)kSpSumWave) {
-            h->sum_list_host.push_back(i);
-            if (counts[i] <= kSpSumMaxRows)
-                while (big_rows < counts[i]) big_rows <<= 1;
-        }
-    const uint32_t n_group = (uint32_t)h->sum_list_host.size() - n_wave;
-    const size_t e8 = Block::col8(total);
+    // the two passes of zk_sp_gather and the work lists: the rows of the asked traces into the handle's staging
     if (!h->sum_heads && (st = alloc(h, &h->sum_heads, ZK_SP_MAX_IDS * sizeof(zk_sp_summary), "the summaries' heads")) != ZK_OK) return st;
-    if ((st = grow(h, &h->rows, &h->rows_bytes, Block::cols_bytes(total), "the gathered rows (48 B each)")) != ZK_OK) return st;
+    SpStaged sg;
+    if ((st = stage_traces(h, ids, n, flags, kSpSumMaxRows, &sg)) != ZK_OK) return st;
+    const uint64_t total = sg.total;
+    if (total == 0) return ZK_OK;
+    const uint32_t* counts = h->sum_counts_host.data();
+    const size_t e8 = Block::col8(total);
     if ((st = grow(h, &h->ents, &h->ents_bytes, 2 * e8 + Block::col4(total), "the summaries' entries (20 B per row)")) != ZK_OK) return st;
     uint8_t* qb = (uint8_t*)h->q;
-    const SpCols dev = Block::view(h->rows, total, false);
-    const uint32_t G = (uint32_t)h->segs.size();
+    const SpCols dev = sg.dev;
+    const uint32_t n_wave = sg.n_wave, n_group = sg.n_group, big_rows = sg.big_rows;
     zk_sp_summary* d_heads = (zk_sp_summary*)h->sum_heads;
     long long* d_first = (long long*)h->ents;
     long long* d_last = (long long*)((uint8_t*)h->ents + e8);
@@ -1521,12 +1941,7 @@ zk_status zk_sp_summaries(zk_sp* h, const uint64_t* ids, uint32_t n, uint32_t fl
     const unsigned long long* d_ids = (const unsigned long long*)(qb + kQIdsAt);
     const uint32_t* d_counts = (const uint32_t*)(qb + kQCountsAt);
     const unsigned long long* d_base = (const unsigned long long*)(qb + kQBaseAt);
-    SP_HIP(h, hipMemcpyAsync(qb + kQBaseAt, h->base_host.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
-    SP_HIP(h, hipMemcpyAsync(qb + kQListAt, h->sum_list_host.data(), h->sum_list_host.size() * 4, hipMemcpyHostToDevice, h->stream));
-    SP_HIP(h, hipMemsetAsync(qb + kQCursorAt, 0, (size_t)n * 4, h->stream));
     SP_HIP(h, hipMemsetAsync(d_heads, 0, (size_t)n * sizeof(zk_sp_summary), h->stream));
-    SP_HIP(h, launch_checked("k_sp_find_write", k_sp_find_write, dim3(n, G, parts), dim3(kSpWG), 0, h->stream,
-                             (const SpCols*)(qb + kQSegsAt), d_ids, d_counts, (uint32_t*)(qb + kQCursorAt), d_base, dev));
     SP_HIP(h, launch_checked("k_sp_summarize (a wave per trace)", k_sp_summarize<kSpSumWave, 1>, dim3(n_wave), dim3(kSpSumWave),
                              sp_sum_lds(kSpSumWave), h->stream, dev, d_list, d_ids, d_counts, d_base, (uint32_t)kSpSumWave, d_heads,
                              d_svc, d_first, d_last));
@@ -1563,6 +1978,83 @@ zk_status zk_sp_summaries(zk_sp* h, const uint64_t* ids, uint32_t n, uint32_t fl
         memcpy(out->first + at, s_first + from, c * 8);
         memcpy(out->last + at, s_last + from, c * 8);
         at += c;
+    }
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_sp_traces(zk_sp* h, const uint64_t* ids, uint32_t n, uint32_t flags, zk_sp_trace* heads, zk_sp_span* spans,
+                       uint64_t cap_spans, uint32_t* services, uint64_t cap_services, uint64_t n_out[2]) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (!n_out) return sfail(h, ZK_ERR_INVALID_ARG, "null argument");
+    zk_status st = check_ask(h, ids, n, flags);
+    if (st != ZK_OK) return st;
+    if (n && !heads) return sfail(h, ZK_ERR_INVALID_ARG, "null argument");
+    if ((cap_spans && !spans) || (cap_services && !services)) return sfail(h, ZK_ERR_INVALID_ARG, "null output column");
+    n_out[0] = n_out[1] = 0;
+    if (n == 0) return ZK_OK;
+    memset(heads, 0, (size_t)n * sizeof(zk_sp_trace));
+    if (h->segs.empty()) return ZK_OK;
+    SP_HIP(h, hipSetDevice(h->device));
+    // zk_sp_summaries' passes and work lists: the rows of the asked traces into the handle's staging
+    if (!h->tr_heads && (st = alloc(h, &h->tr_heads, ZK_SP_MAX_IDS * sizeof(zk_sp_trace), "the merged traces' heads")) != ZK_OK) return st;
+    SpStaged sg;
+    if ((st = stage_traces(h, ids, n, flags, kSpTrMaxRows, &sg)) != ZK_OK) return st;
+    const uint64_t total = sg.total;
+    if (total == 0) return ZK_OK;
+    const uint32_t* counts = h->sum_counts_host.data();
+    const size_t span_bytes = al256((size_t)total * sizeof(zk_sp_span));
+    if ((st = grow(h, &h->tr_out, &h->tr_bytes, span_bytes + Block::col4(total), "the merged spans and their services (52 B per row)")) != ZK_OK) return st;
+    uint8_t* qb = (uint8_t*)h->q;
+    const SpCols dev = sg.dev;
+    const uint32_t n_wave = sg.n_wave, n_group = sg.n_group, big_rows = sg.big_rows;
+    zk_sp_trace* d_heads = (zk_sp_trace*)h->tr_heads;
+    zk_sp_span* d_spans = (zk_sp_span*)h->tr_out;
+    uint32_t* d_svc = (uint32_t*)((uint8_t*)h->tr_out + span_bytes);
+    const uint32_t* d_list = (const uint32_t*)(qb + kQListAt);
+    const unsigned long long* d_ids = (const unsigned long long*)(qb + kQIdsAt);
+    const uint32_t* d_counts = (const uint32_t*)(qb + kQCountsAt);
+    const unsigned long long* d_base = (const unsigned long long*)(qb + kQBaseAt);
+    SP_HIP(h, hipMemsetAsync(d_heads, 0, (size_t)n * sizeof(zk_sp_trace), h->stream));
+    SP_HIP(h, launch_checked("k_sp_trace (a wave per trace)", k_sp_trace<kSpSumWave, 1>, dim3(n_wave), dim3(kSpSumWave),
+                             sp_tr_lds(kSpSumWave), h->stream, dev, d_list, d_ids, d_counts, d_base, (uint32_t)kSpSumWave, d_heads,
+                             d_spans, d_svc));
+    SP_HIP(h, launch_checked("k_sp_trace (a workgroup per trace)", k_sp_trace<kSpWG, kSpSumItems>, dim3(n_group), dim3(kSpWG),
+                             sp_tr_lds(big_rows), h->stream, dev, d_list + n_wave, d_ids, d_counts, d_base, big_rows, d_heads,
+                             d_spans, d_svc));
+    // only the heads cross before both totals are known
+    SP_HIP(h, hipMemcpyAsync(heads, d_heads, (size_t)n * sizeof(zk_sp_trace), hipMemcpyDeviceToHost, h->stream));
+    if (h->timing) SP_HIP(h, hipEventRecord(h->qev[1], h->stream));
+    SP_HIP(h, hipStreamSynchronize(h->stream));
+    h->qtimed = h->timing;
+    uint64_t need_spans = 0, need_svc = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (heads[i].spans > counts[i] || heads[i].services > counts[i])
+            return sfail(h, ZK_ERR_HIP, "a merged trace has more spans or services than its trace has rows");
+        need_spans += heads[i].spans;
+        need_svc += heads[i].services;
+    }
+    n_out[0] = need_spans;
+    n_out[1] = need_svc;
+    if (need_spans > cap_spans || need_svc > cap_services)
+        return sfail(h, ZK_ERR_CAPACITY, "the outputs hold fewer spans or services than the asked traces have");
+    if (need_spans == 0) return ZK_OK;
+    // the staged spans and services in one copy, then each trace's packed behind the ones before it
+    const size_t bytes = span_bytes + (size_t)total * 4;
+    h->tr_host.resize(bytes);
+    SP_HIP(h, hipMemcpyAsync(h->tr_host.data(), h->tr_out, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (h->timing) SP_HIP(h, hipEventRecord(h->qev[1], h->stream));
+    SP_HIP(h, hipStreamSynchronize(h->stream));
+    const zk_sp_span* s_spans = (const zk_sp_span*)h->tr_host.data();
+    const uint32_t* s_svc = (const uint32_t*)(h->tr_host.data() + span_bytes);
+    uint64_t at = 0, at_svc = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t c = heads[i].spans, v = heads[i].services, from = h->base_host[i];
+        if (c) memcpy(spans + at, s_spans + from, c * sizeof(zk_sp_span));
+        if (v) memcpy(services + at_svc, s_svc + from, v * 4);
+        at += c;
+        at_svc += v;
     }
     return ZK_OK;
     ZK_GUARD_END

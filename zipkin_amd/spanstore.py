@@ -13,6 +13,7 @@ service_id, flags) of Python ints, in the header's canonical order.
 from __future__ import annotations
 
 import ctypes as C
+import gc
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -29,6 +30,11 @@ Row = Tuple[int, int, int, int, int, int, int]
 SUMMARY_HEAD = np.dtype([("trace_id", np.uint64), ("start", np.int64), ("end", np.int64), ("fragments", np.uint32),
                          ("spans", np.uint32), ("span_ts", np.uint32), ("state", np.uint32)])
 ENTRY_COLUMNS = (("service_id", np.uint32), ("first", np.int64), ("last", np.int64))
+# zk_sp_trace, the 48-byte head of one asked id, and zk_sp_span, one merged span (48 bytes)
+TRACE_HEAD = np.dtype([("trace_id", np.uint64), ("start", np.int64), ("end", np.int64), ("root_most", np.uint64),
+                       ("fragments", np.uint32), ("spans", np.uint32), ("services", np.uint32), ("state", np.uint32)])
+TRACE_SPAN = np.dtype([("span_id", np.uint64), ("parent_id", np.uint64), ("first", np.int64), ("last", np.int64),
+                       ("name", np.uint32), ("depth", np.uint32), ("services", np.uint32), ("bits", np.uint32)])
 
 
 def _wrap64(x: int) -> int:
@@ -95,6 +101,18 @@ class Trace:
         self._services = None if services is None else list(services)
         self._span_names = None if span_names is None else list(span_names)
         self.spans: List[Span] = self._merge()
+        self._given = None
+
+    @classmethod
+    def of_merged(cls, spans: Sequence[Span], root_most: Optional[int], depths: Optional[Dict[int, int]]) -> "Trace":
+        """A Trace from spans that are merged and in span order already (zk_sp_traces' answer), with the
+        root-most span's id and the span depths that came with them: rows is None, and getRootMostSpan and
+        toSpanDepths hand back what was given."""
+        t = cls.__new__(cls)
+        t.rows, t._services, t._span_names = None, None, None
+        t.spans = list(spans)
+        t._given = (root_most, depths)
+        return t
 
     def _service(self, i: int):
         if self._services is None:
@@ -148,6 +166,8 @@ class Trace:
         """The root span, else (Trace.scala:70-85) from the first span upwards through the parents the
         trace holds, to the last one found. A parent chain that closes on itself ends where it would
         repeat (the reference does not terminate on one)."""
+        if self._given is not None:
+            return None if not self.spans else self.getSpanById(self._given[0])
         root = self.getRootSpan()
         if root is not None or not self.spans:
             return root
@@ -157,6 +177,11 @@ class Trace:
             seen.add(s.id)
             s = by_id[s.parent]
         return s
+
+    def getRootSpans(self) -> List[Span]:
+        """Trace.scala:77-78: the spans whose parent is none or not a span of this trace, in span order."""
+        by_id = self.getIdToSpanMap()
+        return [s for s in self.spans if s.parent is None or s.parent not in by_id]
 
     def getIdToChildrenMap(self) -> Dict[int, List[Span]]:
         """parent id -> its child spans, in span order."""
@@ -169,6 +194,8 @@ class Trace:
     def toSpanDepths(self) -> Optional[Dict[int, int]]:
         """span id -> depth in the tree under the root-most span, which is at depth 1; None for a trace
         without spans. A span reached twice keeps its first depth."""
+        if self._given is not None:
+            return self._given[1]
         root = self.getRootMostSpan()
         if root is None:
             return None
@@ -232,6 +259,19 @@ class TraceSummary(NamedTuple):
         if trace.id is None or t is None:
             return None
         return TraceSummary(trace.id, t.start, t.end, _to_int(_wrap64(t.end - t.start)), trace.spanTimestamps(), [])
+
+
+class TraceCombo(NamedTuple):
+    """The reference's TraceCombo(trace, traceSummary, traceTimeline, spanDepths). timeline is always None:
+    a record carries no annotation text to lay out."""
+    trace: Trace
+    summary: Optional[TraceSummary]
+    timeline: None
+    span_depths: Optional[Dict[int, int]]
+
+    @staticmethod
+    def of(trace: Trace) -> "TraceCombo":
+        return TraceCombo(trace, TraceSummary.of(trace), None, trace.toSpanDepths())
 
 
 class TraceSpanStore:
@@ -441,6 +481,91 @@ class TraceSpanStore:
                 at += c
         return out
 
+    def traces(self, ids):
+        """(heads, spans, services) for at most ZK_SP_MAX_IDS ids (zk_sp_traces): heads, a TRACE_HEAD array in
+        the order asked; the merged spans of all asked traces one after another, each trace's in span order
+        (a TRACE_SPAN array of exactly the total); and the spans' service ids, a uint32 column. The sizing
+        call, then the call that fills."""
+        keep, ptr, n, flags = self._ask(ids)
+        heads = np.zeros(n, TRACE_HEAD)
+        total = (C.c_uint64 * 2)()
+        st = self._L.zk_sp_traces(self._h, ptr, n, flags, heads.ctypes.data, None, 0, None, 0, total)
+        if st not in (_abi.ZK_OK, _abi.ZK_ERR_CAPACITY):
+            self._check(st)
+        spans, services = np.zeros(total[0], TRACE_SPAN), np.zeros(total[1], np.uint32)
+        if st == _abi.ZK_ERR_CAPACITY:
+            self._check(self._L.zk_sp_traces(self._h, ptr, n, flags, heads.ctypes.data, spans.ctypes.data, len(spans),
+                                             services.ctypes.data, len(services), total))
+        return heads, spans, services
+
+    def _combos_on_device(self, ids) -> List[TraceCombo]:
+        """getTraceCombosByIds from traces(): spans, summary and depths of a trace from one answer. Names and
+        services go through the dictionaries as in Trace._name and Trace._service. The Span and SpanTimestamp
+        tuples of a whole chunk are built column by column; per trace only slices are taken. The cyclic
+        collector is paused meanwhile: the tuples cannot form cycles, and at 4096 ids its passes over the
+        growing lists were two thirds of the call."""
+        out: List[TraceCombo] = []
+        paused = gc.isenabled()
+        gc.disable()
+        try:
+            for part in self._chunks(ids):
+                self._combos_of(out, *self.traces(part))
+        finally:
+            if paused:
+                gc.enable()
+        return out
+
+    def _combos_of(self, out: List[TraceCombo], heads, spans, services) -> None:
+        """The TraceCombos of one traces() answer, appended to out."""
+        namer = Trace((), self.services, self.span_names)
+        svc = services.tolist() if self.services is None else [namer._service(i) for i in services.tolist()]
+        names = spans["name"].tolist()
+        if self.span_names is not None:
+            names = [namer._name(i) for i in names]
+        bits = spans["bits"]
+        timed = (bits & _abi.ZK_SP_SPAN_TIMED) != 0
+        timed_l = timed.tolist()
+        sid = spans["span_id"].tolist()
+        parent = [p if b else None for p, b in zip(spans["parent_id"].tolist(), ((bits & _abi.ZK_SP_SPAN_HAS_PARENT) != 0).tolist())]
+        first = [v if t else None for v, t in zip(spans["first"].tolist(), timed_l)]
+        last = [v if t else None for v, t in zip(spans["last"].tolist(), timed_l)]
+        depth = spans["depth"].tolist()
+        k = spans["services"].astype(np.int64)
+        svc_end = np.cumsum(k)
+        mine = [tuple(svc[a:b]) for a, b in zip((svc_end - k).tolist(), svc_end.tolist())]
+        c = heads["spans"].astype(np.int64)
+        merged = list(map(Span, np.repeat(heads["trace_id"], c).tolist(), sid, parent, names, first, last, mine))
+        # one SpanTimestamp per (span, service) pair of a timed span, in the pairs' order
+        pair_span = np.repeat(np.arange(len(spans)), k)
+        keep = timed[pair_span]
+        pair_span = pair_span[keep]
+        stamps = list(map(SpanTimestamp, [svc[i] for i in np.nonzero(keep)[0].tolist()],
+                          spans["first"][pair_span].tolist(), spans["last"][pair_span].tolist()))
+        stamp_at = np.concatenate(([0], np.cumsum(np.where(timed, k, 0)))).tolist()
+        at = 0
+        for tid, start, end, root, _, n_spans, _, state in heads.tolist():
+            if state & _abi.ZK_SP_TR_OVERFLOW:  # a trace too long for the device merge: the host path
+                out += self.getTraceCombosByIds([tid])
+                continue
+            if not state & _abi.ZK_SP_TR_FOUND:
+                continue
+            to = at + n_spans
+            depths = {i: d for i, d in zip(sid[at:to], depth[at:to]) if d}
+            summary = None
+            if state & _abi.ZK_SP_TR_TIMED:
+                summary = TraceSummary(tid, start, end, _to_int(_wrap64(end - start)), stamps[stamp_at[at]:stamp_at[to]], [])
+            out.append(TraceCombo(Trace.of_merged(merged[at:to], root, depths), summary, None, depths))
+            at = to
+
+    def getTraceCombosByIds(self, ids, on_device: bool = False) -> List[TraceCombo]:
+        """QueryService.getTraceCombosByIds: one TraceCombo (the trace, its summary, no timeline, its span
+        depths) per asked id that was found, in the order asked; summary is None for a trace without a timed
+        fragment. on_device: spans, summary and depths are merged on the device (zk_sp_traces) and no
+        fragment crosses to the host; the answer is the same."""
+        if on_device:
+            return self._combos_on_device(ids)
+        return [TraceCombo.of(t) for t in self.getTracesByIds(ids)]
+
     def getTraceSummariesByIds(self, ids, on_device: bool = False) -> List[TraceSummary]:
         """QueryService.getTraceSummariesByIds: the summaries in the order asked; ids that are not found
         and traces without a timed fragment (TraceSummary.apply yields None) are left out. on_device:
@@ -464,7 +589,7 @@ class TraceSpanStore:
         return dict(zip(self.EXPIRE_PHASES, out))
 
     def query_ms(self) -> float:
-        """Time (ms) on the handle's stream of the last exist, gather or summaries (zk_sp_query_ms;
+        """Time (ms) on the handle's stream of the last exist, gather, summaries or traces (zk_sp_query_ms;
         timing=True)."""
         ms = C.c_double()
         self._check(self._L.zk_sp_query_ms(self._h, C.byref(ms)))
