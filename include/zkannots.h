@@ -1,0 +1,156 @@
+/*
+ * zkannots.h -- the annotation store by trace id: a span's time annotations in HBM, next to the span store.
+ *
+ * The reference's query service folds its adjusters over a trace before it answers (QueryService.scala:
+ * 295-355; the web front end asks for Adjust.TimeSkew on every trace call), and builds a TraceTimeline from
+ * every span's annotations. Both need what the 48-B record of zkagg.h drops: each annotation's own
+ * timestamp, the kind of its value and its host. This handle keeps one 44-B ROW per time annotation of an
+ * accepted span, findable by trace id, and hands the rows of the asked traces back; the adjuster and the
+ * timeline are built on the host over them (zipkin_amd/annotstore.py, spanstore.py). Binary annotations are
+ * not kept.
+ *
+ * A row, seven columns, 44 bytes:
+ *   trace_id    u64
+ *   span_id     u64
+ *   ts          i64   the annotation's timestamp
+ *   value       u64   zk_hash_string of the value (the decoder keeps the string: zk_ingest_string)
+ *   ipv4        u32   the host's ipv4, as the thrift i32's bits; 0 without a host
+ *   service_id  u32   the host's service (dictionary id); 0 without a host
+ *   bits        u32   bits 0..2 the KIND (0 other, 1 cs, 2 cr, 3 sr, 4 ss); bit 3 ZK_AN_HAS_HOST;
+ *                     bits 16..31 the host's port (the thrift i16's bits)
+ *
+ * Semantics
+ *  - EVERY observed row is kept. The store is a MULTISET of rows, like the span store: observing a batch
+ *    again adds it again. Batches and rows may come in any order; a trace may be spread over any number of
+ *    batches.
+ *  - Legal: traceIds 0 and 2^64 - 1, ts at INT64_MIN / INT64_MAX, any 32-bit ipv4, service_id and bits.
+ *  - CANONICAL ORDER: the rows of one trace are returned ascending lexicographically by
+ *    (span_id unsigned, ts signed, kind, value, ipv4, port, service_id, HAS_HOST), and last by the
+ *    whole `bits` word (its bits 4..15 are reserved: kept and returned as given). Every answer is so a
+ *    function of the multiset alone.
+ *
+ * Layout
+ *  - One zk_an_observe makes one SEGMENT: the batch's rows grouped by BUCKET. The bucket function is THE
+ *    SPAN STORE'S,
+ *        bucket = zk_mix64(trace_id ^ ZK_SP_SALT) >> 52          (ZK_AN_BUCKETS = ZK_SP_BUCKETS = 4096)
+ *    so a trace's spans and annotations carry the same bucket number in both stores, and a later joint
+ *    kernel can rely on that. Seven columns, 44 B per entry, each column 256-B aligned. The host keeps each
+ *    segment's offsets[4097]; a copy of them (4 B each) lies behind the segment's columns for the lookups.
+ *    The order inside a bucket's slice is not reproducible.
+ *  - At most ZK_AN_MAX_SEGMENTS segments exist: an observe that would make one more first merges all
+ *    segments into one (each bucket's slices concatenated in segment order into a freshly sized segment,
+ *    then the old ones freed). zk_an_compact does the same on request.
+ *  - At most 2^32 - 1 entries per handle: a batch that would exceed it is ZK_ERR_CAPACITY and changes
+ *    nothing.
+ *  - A refused allocation is ZK_ERR_CAPACITY and leaves the handle exactly as it was: nothing is freed
+ *    before its replacement is complete.
+ *  - No expiry yet. A trace's end equals the maximum ts of its rows, so the span store's rule can later be
+ *    applied from this store's own entries.
+ *
+ * Conventions are those of zkspans.h: every entry point returns zk_status; a handle is not thread-safe; all
+ * device work of a handle is ordered on one HIP stream; nothing is allocated before the first observe. Every
+ * call refuses a NULL handle or argument with ZK_ERR_INVALID_ARG before any device is touched; errors go to
+ * zk_an_last_error. ONE DIFFERENCE: zk_an_create touches no device either. The device is opened (and must
+ * be a gfx950: ZK_ERR_NO_DEVICE otherwise) by the first observe that carries rows, so an empty store answers
+ * zk_an_info and zk_an_gather on a machine without a device.
+ */
+#ifndef ZKANNOTS_H
+#define ZKANNOTS_H
+
+#include "zkagg.h"
+#include "zkspans.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define ZK_AN_BUCKETS 4096u
+#define ZK_AN_MAX_SEGMENTS 64u
+/* the most ids one zk_an_gather asks */
+#define ZK_AN_MAX_IDS 4096u
+/* bytes of one row */
+#define ZK_AN_ROW_BYTES 44u
+
+/* zk_an_cols.bits */
+#define ZK_AN_KIND_MASK  7u
+#define ZK_AN_KIND_OTHER 0u
+#define ZK_AN_KIND_CS    1u
+#define ZK_AN_KIND_CR    2u
+#define ZK_AN_KIND_SR    3u
+#define ZK_AN_KIND_SS    4u
+#define ZK_AN_HAS_HOST   8u
+#define ZK_AN_PORT_SHIFT 16u
+
+typedef struct zk_an_config {
+    int32_t  device;   /* HIP device ordinal */
+    uint32_t timing;   /* 1: record HIP events (zk_an_observe_ms, zk_an_query_ms) */
+    void*    stream;   /* hipStream_t to run on, or NULL for a private stream */
+    uint32_t reserved[8];
+} zk_an_config;
+
+/* seven parallel columns: zk_an_observe's input (host or device), zk_an_gather's output (host) */
+typedef struct zk_an_cols {
+    uint64_t* trace_id;
+    uint64_t* span_id;
+    int64_t*  ts;
+    uint64_t* value;
+    uint32_t* ipv4;
+    uint32_t* service_id;
+    uint32_t* bits;
+} zk_an_cols;
+
+typedef struct zk_an zk_an;
+
+zk_status   zk_an_create(const zk_an_config* cfg, zk_an** out);
+zk_status   zk_an_destroy(zk_an* an);
+const char* zk_an_last_error(const zk_an* an);
+
+/* Add a batch of n rows as one segment. All seven columns of `in` are read. flags: ZK_BATCH_DEVICE_PTRS:
+   `in` holds device pointers; without it `in` is host memory, staged (44 B per row), and the call waits for
+   its staging copy. No other flag is accepted. A count kernel over trace_id (8 B per row) builds the
+   4096-bin histogram; the call synchronises once, to read the counts it sizes the segment by (a merge, see
+   Layout, synchronises once more). The scatter of the seven columns (44 B read and 44 B written per row,
+   trace_id read once more) is queued on the handle's stream behind that: DEVICE columns must stay as they
+   are until the handle's next synchronising call (zk_an_info, zk_an_gather, zk_an_compact, zk_an_observe).
+   A row whose place falls outside its bucket's slice (it cannot while the columns stay as they were) is
+   dropped, never written elsewhere. n == 0 is ZK_OK; n >= 2^32 is ZK_ERR_UNSUPPORTED. */
+zk_status   zk_an_observe(zk_an* an, const zk_an_cols* in, uint64_t n, uint32_t flags);
+/* Empty the store: every segment is freed. */
+zk_status   zk_an_reset(zk_an* an);
+/* Merge all segments into one (see Layout): 44 B read and 44 B written per entry. Fewer than two segments:
+   nothing to do. Synchronises. */
+zk_status   zk_an_compact(zk_an* an);
+/* entries in the store, segments, bytes of HBM the segments hold. Any of the three pointers may be NULL.
+   Synchronises. */
+zk_status   zk_an_info(zk_an* an, uint64_t* entries, uint64_t* segments, uint64_t* bytes);
+/* The rows of the asked traces: zk_sp_gather's contract.
+     ids     n trace ids: device memory under ZK_BATCH_DEVICE_PTRS (no other flag is accepted), else host.
+     n       1..ZK_AN_MAX_IDS; more is ZK_ERR_INVALID_ARG; 0 is ZK_OK with *n_out = 0.
+     counts  a HOST array of n entries: counts[i] = the rows of ids[i] (0: none).
+     out     seven HOST columns of `cap` entries each. The rows of ids[0] come first, then those of ids[1],
+             and so on; a duplicated id gets its rows again; inside one trace the rows are in CANONICAL
+             ORDER (the host sorts them). out, or any of its columns, may be NULL only when cap == 0.
+     n_out   the total number of rows, the sum of counts.
+   When cap is below the total the call returns ZK_ERR_CAPACITY with *n_out set to the needed total and
+   counts written; no row is written. cap == 0 with NULL columns is the sizing call. An empty store answers
+   without a device pass.
+   Two device passes: the count pass (a workgroup per asked id, segment and part of the slice reads the
+   trace_id slice of the id's bucket; a slice longer than 4096 entries is split over several workgroups),
+   one synchronisation and the host's prefix sum, then the write pass, which reads the same slices again
+   and appends every matching row (all seven columns, 44 B) behind its asked id's offset, a wave's matches
+   with one atomic. A trace may be of any length: no pass keeps a trace's rows in LDS. Staging for the rows
+   (44 B each) is allocated on first use and grown; a refused allocation is ZK_ERR_CAPACITY. Synchronises. */
+zk_status   zk_an_gather(zk_an* an, const uint64_t* ids, uint32_t n, uint32_t flags, uint32_t* counts,
+                         zk_an_cols* out, uint64_t cap, uint64_t* n_out);
+/* Device time in ms of the last zk_an_observe that added a segment: the count, the sizing step (the counts'
+   copy and, when the segment bound was met, the merge), the scatter. Needs zk_an_config.timing; waits for
+   the scatter. */
+zk_status   zk_an_observe_ms(zk_an* an, double out[3]);
+/* Time in ms on the handle's stream of the last zk_an_gather that ran a pass, from its first pass to its
+   last copy (the host's prefix sum included, the host's sort not). Needs zk_an_config.timing. */
+zk_status   zk_an_query_ms(zk_an* an, double* ms);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* ZKANNOTS_H */

@@ -130,6 +130,42 @@ typedef struct zk_ingest_index_items {
 zk_status zk_ingest_spans_indexed(zk_ingest* ing, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
                                   uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
                                   zk_ingest_index_items* ix);
+/* caller buffers for the rows of the annotation store (zkannots.h): seven parallel HOST columns, laid out
+ * as zk_an_cols, then their capacity and count */
+typedef struct zk_ingest_annotation_rows {
+    uint64_t* trace_id;
+    uint64_t* span_id;
+    int64_t*  ts;          /* the annotation's timestamp */
+    uint64_t* value;       /* zk_hash_string(value); the string is kept: zk_ingest_string */
+    uint32_t* ipv4;        /* the host's ipv4 (Endpoint field 1, the i32's bits); 0 without a host */
+    uint32_t* service_id;  /* the host's service id; 0 without a host */
+    uint32_t* bits;        /* ZK_AN_* of zkannots.h: kind, HAS_HOST, the port (Endpoint field 2) in bits 16..31 */
+    uint64_t  cap;         /* rows the arrays hold */
+    uint64_t  n;           /* out (decoder): rows */
+} zk_ingest_annotation_rows;
+
+/* zk_ingest_spans (records, rejection, dictionaries, flags and `items`, which may be NULL, exactly as that
+ * call's for the same arguments, ZK_INGEST_SPAN_NAMES and ZK_INGEST_ONE_THREAD included) that also writes
+ * the annotation store's rows to the HOST columns of `an`: one row per time annotation of every ACCEPTED
+ * span, binary annotations none.
+ *   - Order: record order and, within a record, the annotation list's order (all field-6 lists appended,
+ *     see Wire forms); the same for any thread count.
+ *   - A row's host enters the service dictionary as an item's host does: after the record's own service
+ *     and the record's items, in row order ("Unknown service name" when absent or empty). A row without a
+ *     host has service_id = ipv4 = 0, no HAS_HOST bit and port 0.
+ *   - The value's string is captured: zk_ingest_string(value) returns it. An annotation without a value
+ *     field hashes as "".
+ *   - Wire forms: the endpoint reader also reads field 1 (i32 -> ipv4) and field 2 (i16 -> port). The
+ *     rules below extend to them: within an endpoint the last occurrence wins; a known id with another
+ *     wire type is skipped by its type; within one annotation a later host struct keeps the earlier ipv4
+ *     and port unless it carries its own. (The other decode calls read the two fields and ignore them:
+ *     their outputs are what they were.)
+ *   - an->cap too small: ZK_ERR_CAPACITY; the records and the first cap rows are written and an->n = cap.
+ *   - an and its seven columns must not be NULL (ZK_ERR_INVALID_ARG).
+ * The device decoder does not emit these rows. */
+zk_status zk_ingest_spans_annotated(zk_ingest* ing, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
+                                    uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
+                                    zk_ingest_items* items, zk_ingest_annotation_rows* an);
 /* the value hash of the annotation index: zk_hash_string(s, len) | 1, so it is never 0 (0 asks for any
    value, and marks a time-annotation entry) */
 uint64_t  zk_index_value_hash(const char* s, uint64_t len);

@@ -11,8 +11,9 @@ from .durations import TraceDurationIndex, TraceIdDuration, merge_top  # noqa: F
 from .nameindex import IndexedTraceId, TraceNameIndex, merge_trace_ids  # noqa: F401
 from .annindex import AnnotationItems, DeviceAnnotationItems, TraceAnnotationIndex, get_trace_ids, trace_ids_intersect  # noqa: F401
 from .retention import IndexRetention, SpanRetention  # noqa: F401
-from .spanstore import (SUMMARY_HEAD, TRACE_HEAD, TRACE_SPAN, Span, SpanTimestamp, Timespan, Trace, TraceCombo,  # noqa: F401
-                        TraceSpanStore, TraceSummary)
+from .annotstore import Annotation, AnnotationRows, DeviceAnnotationRows, Endpoint, TraceAnnotationStore  # noqa: F401
+from .spanstore import (SUMMARY_HEAD, TRACE_HEAD, TRACE_SPAN, AnnotatedSpan, Span, SpanTimestamp, TimelineAnnotation,  # noqa: F401
+                        Timespan, TimeSkewAdjuster, Trace, TraceCombo, TraceSpanStore, TraceSummary, TraceTimeline)
 from .windows import WindowedAggregateJob, WindowPartition  # noqa: F401
 from . import table  # noqa: F401
 
@@ -52,5 +53,14 @@ __all__ = [
     "TRACE_HEAD",
     "TRACE_SPAN",
     "TraceCombo",
+    "TraceAnnotationStore",
+    "AnnotationRows",
+    "DeviceAnnotationRows",
+    "Annotation",
+    "Endpoint",
+    "AnnotatedSpan",
+    "TimeSkewAdjuster",
+    "TraceTimeline",
+    "TimelineAnnotation",
     "BYTES_PER_RECORD",
 ]

@@ -427,6 +427,51 @@ class zk_ingest_index_items(C.Structure):
     ]
 
 
+class zk_ingest_annotation_rows(C.Structure):
+    _fields_ = [
+        ("trace_id", C.c_void_p),
+        ("span_id", C.c_void_p),
+        ("ts", C.c_void_p),
+        ("value", C.c_void_p),
+        ("ipv4", C.c_void_p),
+        ("service_id", C.c_void_p),
+        ("bits", C.c_void_p),
+        ("cap", C.c_uint64),
+        ("n", C.c_uint64),
+    ]
+
+
+ZK_AN_BUCKETS = 4096
+ZK_AN_MAX_SEGMENTS = 64
+ZK_AN_MAX_IDS = 4096
+ZK_AN_ROW_BYTES = 44
+ZK_AN_KIND_MASK = 7
+ZK_AN_KIND_OTHER, ZK_AN_KIND_CS, ZK_AN_KIND_CR, ZK_AN_KIND_SR, ZK_AN_KIND_SS = 0, 1, 2, 3, 4
+ZK_AN_HAS_HOST = 8
+ZK_AN_PORT_SHIFT = 16
+
+
+class zk_an_config(C.Structure):
+    _fields_ = [
+        ("device", C.c_int32),
+        ("timing", C.c_uint32),
+        ("stream", C.c_void_p),
+        ("reserved", C.c_uint32 * 8),
+    ]
+
+
+class zk_an_cols(C.Structure):
+    _fields_ = [
+        ("trace_id", C.c_void_p),
+        ("span_id", C.c_void_p),
+        ("ts", C.c_void_p),
+        ("value", C.c_void_p),
+        ("ipv4", C.c_void_p),
+        ("service_id", C.c_void_p),
+        ("bits", C.c_void_p),
+    ]
+
+
 ZK_CODEC_THRIFT = 0
 ZK_CODEC_SNAPPY_THRIFT = 1
 ZK_INGEST_STRICT = 1
@@ -566,6 +611,12 @@ _SIGNATURES = [
         [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(zk_span_cols), _U64P, _U64P,
          C.POINTER(zk_ingest_index_items)],
     ),
+    (
+        "zk_ingest_spans_annotated",
+        C.c_int,
+        [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(zk_span_cols), _U64P, _U64P,
+         C.POINTER(zk_ingest_items), C.POINTER(zk_ingest_annotation_rows)],
+    ),
     ("zk_index_value_hash", C.c_uint64, [C.c_char_p, C.c_uint64]),
     ("zk_ingest_num_services", C.c_int, [_P, _U32P]),
     ("zk_ingest_service_id", C.c_int, [_P, C.c_char_p, C.c_uint64, _U32P]),
@@ -704,6 +755,17 @@ _SIGNATURES = [
     ("zk_sp_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_sp_expire", C.c_int, [_P, C.c_int64, _P, _P, C.c_uint32, _U64P]),
     ("zk_sp_expire_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    # include/zkannots.h: the annotation store by trace id
+    ("zk_an_create", C.c_int, [C.POINTER(zk_an_config), C.POINTER(_P)]),
+    ("zk_an_destroy", C.c_int, [_P]),
+    ("zk_an_last_error", C.c_char_p, [_P]),
+    ("zk_an_observe", C.c_int, [_P, C.POINTER(zk_an_cols), C.c_uint64, C.c_uint32]),
+    ("zk_an_reset", C.c_int, [_P]),
+    ("zk_an_compact", C.c_int, [_P]),
+    ("zk_an_info", C.c_int, [_P, _U64P, _U64P, _U64P]),
+    ("zk_an_gather", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _U32P, C.POINTER(zk_an_cols), C.c_uint64, _U64P]),
+    ("zk_an_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zk_an_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
 ]
 
 SYMBOLS = [s[0] for s in _SIGNATURES]

@@ -35,9 +35,10 @@ SOURCES = [
     "zk_ix.hip",
     "zk_ax.hip",
     "zk_sp.hip",
+    "zk_an.hip",
 ]
 HEADERS = ["zk_internal.h", "zk_cluster.h", "zk_tracegen.h", "zk_sketch_internal.h", "zk_rt_internal.h", "zk_block.h", "zk_launch.h", "zk_comm.h", "zk_rl_internal.h", "zk_lh_internal.h", "zk_lh_snapshot.h", "zk_td_select.h", "zk_ix_select.h", "zk_hist.h", "zk_expire.h", "zk_seg_index.h"]
-PUBLIC_HEADERS = ["zkagg.h", "zksketch.h", "zkstore.h", "zkingest.h", "zkcomm.h", "zkwindow.h", "zkduration.h", "zkindex.h", "zkannindex.h", "zkspans.h"]
+PUBLIC_HEADERS = ["zkagg.h", "zksketch.h", "zkstore.h", "zkingest.h", "zkcomm.h", "zkwindow.h", "zkduration.h", "zkindex.h", "zkannindex.h", "zkspans.h", "zkannots.h"]
 LIB = PKG / "libzkagg.so"
 ARCH = os.environ.get("ZK_OFFLOAD_ARCH", "gfx950")
 

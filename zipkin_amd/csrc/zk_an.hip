@@ -1,0 +1,741 @@
+// zk_an.hip — the annotation store by trace id (include/zkannots.h): segments of 44-B annotation rows
+// grouped by the span store's 12-bit hash of the trace id in HBM, and the lookup of asked traces' rows.
+//
+// A segment is one allocation of seven columns, trace_id, span_id, ts, value [8 B], ipv4, service_id,
+// bits [4 B], each 256-B aligned, then off[4097] (u32): the entries of bucket b lie at [off[b], off[b + 1]).
+// The host keeps the same offsets. The plan is zk_sp.hip's, kernel for kernel; this file shares none of its
+// code, so the span store's kernels stay as they were.
+//
+//   k_an_count    the batch's rows per bucket: a per-workgroup LDS histogram of 4096 bins (16 KB), lanes of
+//                 a wave that share a bin added once, flushed with atomics. 8 B per row.
+//   (host)        the counts' exclusive scan = the segment's offsets; they also start the cursors.
+//   k_an_scatter  a workgroup owns a stretch of the batch and walks it twice: an LDS histogram of its rows'
+//                 buckets, ONE returning atomic per workgroup and bucket with rows to claim that many places
+//                 behind the bucket's cursor, then every row again, its rank inside the workgroup from LDS
+//                 (32 KB of LDS, so five workgroups share a CU). trace_id is read twice, 44 B per row read
+//                 and 44 B written.
+//   k_an_merge    one old segment's entries into the merged one: an entry's bucket from its trace id, its
+//                 place = the bucket's base for this segment + the entry's index in the old slice.
+//   k_an_find_count, k_an_find_write   zk_an_gather's passes: a workgroup per (asked id, segment, part of
+//                 the slice) walks the trace_id slice of the id's bucket; the write pass appends a wave's
+//                 matching rows behind the asked id's offset with one returning atomic per wave. Nothing of
+//                 a trace is held in LDS: a trace may be of any length.
+//
+// Every store is bounded: the scatter and the merge drop a place outside the bucket's slice of the segment
+// they write (it cannot arise while the columns stay as they were between the count and the scatter, which
+// the header asks of the caller), the lookups clamp a slice to its segment and drop a row at or past its
+// asked id's count or the output's size.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <algorithm>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "zk_guard.h"
+#include "zk_hist.h"
+#include "zk_launch.h"
+#include "zk_tracegen.h"
+#include "zkannots.h"
+
+namespace zk {
+namespace {
+
+constexpr int kAnWG = 256;
+constexpr uint32_t kAnBins = ZK_AN_BUCKETS;
+constexpr uint32_t kAnMaxGrid = 4096;
+constexpr uint32_t kAnHistGrid = 1024;        // k_an_count: every workgroup flushes up to 4096 bins
+constexpr uint32_t kAnScatterPerWG = 16384;   // k_an_scatter: rows per workgroup at least (4096 atomics each at most)
+constexpr uint64_t kAnMaxEntries = 0xFFFFFFFFull;
+constexpr int kAnCntItems = 4;                // k_an_count: rows per thread and step
+constexpr uint32_t kAnCntTile = kAnWG * kAnCntItems;
+constexpr uint32_t kAnPart = 4096;            // the lookups: a slice longer than this is split over workgroups
+constexpr uint32_t kAnMaxParts = 64;
+constexpr uint64_t kAnMaxFindGrid = 1ull << 20;
+constexpr unsigned long long kAnSalt = ZK_SP_SALT;   // the span store's bucket function, on purpose
+
+static_assert(kAnBins == 4096 && ZK_AN_BUCKETS == ZK_SP_BUCKETS, "the bucket is the span store's: the hash's 12 highest bits");
+static_assert(ZK_AN_ROW_BYTES == 4 * 8 + 3 * 4, "a row's seven columns");
+static_assert(sizeof(zk_an_cols) == 56 && sizeof(zk_an_config) == 48, "the ABI's layouts");
+
+__host__ __device__ inline uint32_t an_bucket(unsigned long long id) { return (uint32_t)(zk_mix64(id ^ kAnSalt) >> 52); }
+
+// a segment's columns and offsets as the kernels see them (const), or as the scatter and the merge write them
+struct AnCols {
+    unsigned long long* tid;
+    unsigned long long* span;
+    long long* ts;
+    unsigned long long* val;
+    uint32_t* ip;
+    uint32_t* svc;
+    uint32_t* bits;
+    uint32_t* off;  // [kAnBins + 1] (a segment), or nullptr (a batch, the lookups' output)
+    unsigned long long n;
+};
+static_assert(sizeof(AnCols) == 72, "the segment table's stride");
+
+// the lookups' block: the asked ids, their counts, the write pass's cursors, the rows' bases, the segments
+constexpr size_t kQIdsAt = 0;
+constexpr size_t kQCountsAt = kQIdsAt + ZK_AN_MAX_IDS * 8;
+constexpr size_t kQCursorAt = kQCountsAt + ZK_AN_MAX_IDS * 4;
+constexpr size_t kQBaseAt = kQCursorAt + ZK_AN_MAX_IDS * 4;
+constexpr size_t kQSegsAt = kQBaseAt + ZK_AN_MAX_IDS * 8;
+constexpr size_t kQBytes = kQSegsAt + ZK_AN_MAX_SEGMENTS * sizeof(AnCols);
+// the observe's block: the counts, then the cursors
+constexpr size_t kObsCursorAt = kAnBins * 4;
+constexpr size_t kObsBytes = 2 * kAnBins * 4;
+
+uint32_t an_grid(uint64_t items, uint32_t cap = kAnMaxGrid) {
+    const uint64_t g = (items + kAnWG - 1) / kAnWG;
+    return (uint32_t)(g < 1 ? 1 : g > cap ? cap : g);
+}
+
+// ---- observe -------------------------------------------------------------------------------------------
+// counts[b] += the rows of bucket b. The loop's bounds are the same for all threads of a workgroup, so
+// every lane reaches the ballots.
+__global__ __launch_bounds__(kAnWG) void k_an_count(const unsigned long long* __restrict__ tid, unsigned long long n,
+                                                    uint32_t* __restrict__ counts) {
+    __shared__ uint32_t s_hist[kAnBins];
+    for (uint32_t b = threadIdx.x; b < kAnBins; b += kAnWG) s_hist[b] = 0u;
+    __syncthreads();
+    const unsigned long long stride = (unsigned long long)gridDim.x * kAnCntTile;
+    for (unsigned long long base = (unsigned long long)blockIdx.x * kAnCntTile; base < n; base += stride) {
+        unsigned long long t[kAnCntItems];  // (the tile's loads first, then the ballots)
+#pragma unroll
+        for (int j = 0; j < kAnCntItems; ++j) {
+            const unsigned long long i = base + (unsigned long long)j * kAnWG + threadIdx.x;
+            t[j] = i < n ? tid[i] : 0ull;
+        }
+#pragma unroll
+        for (int j = 0; j < kAnCntItems; ++j)
+            hist_add(s_hist, base + (unsigned long long)j * kAnWG + threadIdx.x < n, an_bucket(t[j]));
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < kAnBins; b += kAnWG) {
+        const uint32_t c = s_hist[b];
+        if (c) atomicAdd(&counts[b], c);
+    }
+}
+
+// Workgroup w owns rows [w * chunk, (w + 1) * chunk) (chunk a multiple of the workgroup). cursor[b] starts
+// at the segment's off[b]; a place at or past off[b + 1] is dropped.
+__global__ __launch_bounds__(kAnWG) void k_an_scatter(AnCols in, unsigned long long chunk, uint32_t* __restrict__ cursor, AnCols out) {
+    __shared__ uint32_t s_cnt[kAnBins];   // the stretch's rows per bucket, then the ranks given out
+    __shared__ uint32_t s_base[kAnBins];  // where the workgroup's places of a bucket begin
+    const unsigned long long lo = (unsigned long long)blockIdx.x * chunk;
+    const unsigned long long hi = lo + chunk < in.n ? lo + chunk : in.n;
+    for (uint32_t b = threadIdx.x; b < kAnBins; b += kAnWG) s_cnt[b] = 0u;
+    __syncthreads();
+    for (unsigned long long base = lo; base < hi; base += kAnCntTile) {
+        unsigned long long t[kAnCntItems];
+#pragma unroll
+        for (int j = 0; j < kAnCntItems; ++j) {
+            const unsigned long long i = base + (unsigned long long)j * kAnWG + threadIdx.x;
+            t[j] = i < hi ? in.tid[i] : 0ull;
+        }
+#pragma unroll
+        for (int j = 0; j < kAnCntItems; ++j)
+            hist_add(s_cnt, base + (unsigned long long)j * kAnWG + threadIdx.x < hi, an_bucket(t[j]));
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < kAnBins; b += kAnWG) {
+        const uint32_t c = s_cnt[b];
+        s_base[b] = c ? atomicAdd(&cursor[b], c) : 0u;
+        s_cnt[b] = 0u;
+    }
+    __syncthreads();
+    for (unsigned long long base = lo; base < hi; base += kAnWG) {
+        const unsigned long long i = base + threadIdx.x;
+        const bool valid = i < hi;
+        const unsigned long long t = valid ? in.tid[i] : 0ull;
+        const uint32_t b = an_bucket(t);
+        const uint32_t rank = hist_rank(s_cnt, valid, b);
+        if (valid) {
+            const unsigned long long at = (unsigned long long)s_base[b] + rank;
+            if (at < (unsigned long long)out.off[b + 1] && at < out.n) {
+                out.tid[at] = t;
+                out.span[at] = in.span[i];
+                out.ts[at] = in.ts[i];
+                out.val[at] = in.val[i];
+                out.ip[at] = in.ip[i];
+                out.svc[at] = in.svc[i];
+                out.bits[at] = in.bits[i];
+            }
+        }
+    }
+}
+
+// dst_base[b]: where this old segment's slice of bucket b begins in the merged segment
+__global__ __launch_bounds__(kAnWG) void k_an_merge(AnCols src, const uint32_t* __restrict__ dst_base, AnCols dst) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * kAnWG;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * kAnWG + threadIdx.x; i < src.n; i += stride) {
+        const unsigned long long t = src.tid[i];
+        const uint32_t b = an_bucket(t);
+        const unsigned long long so = src.off[b];
+        if (i < so || i >= (unsigned long long)src.off[b + 1]) continue;  // (not in its bucket's slice: never a scattered entry)
+        const unsigned long long at = (unsigned long long)dst_base[b] + (i - so);
+        if (at < (unsigned long long)dst.off[b + 1] && at < dst.n) {
+            dst.tid[at] = t;
+            dst.span[at] = src.span[i];
+            dst.ts[at] = src.ts[i];
+            dst.val[at] = src.val[i];
+            dst.ip[at] = src.ip[i];
+            dst.svc[at] = src.svc[i];
+            dst.bits[at] = src.bits[i];
+        }
+    }
+}
+
+// ---- the lookups ---------------------------------------------------------------------------------------
+// The grid: x the asked id, y the segment, z the part of the slice. [*a, *e) = this workgroup's stretch of
+// the trace_id slice of the id's bucket, clamped to the segment; false when it is empty. The same for all
+// threads of a workgroup.
+__device__ inline bool an_stretch(const AnCols& sg, unsigned long long id, unsigned long long* a, unsigned long long* e) {
+    const uint32_t b = an_bucket(id);
+    unsigned long long lo = sg.off[b], hi = sg.off[b + 1];
+    if (hi > sg.n) hi = sg.n;
+    if (lo >= hi) return false;
+    const unsigned long long parts = gridDim.z;
+    const unsigned long long part = (((hi - lo) + parts - 1) / parts + kAnWG - 1) / kAnWG * kAnWG;
+    *a = lo + (unsigned long long)blockIdx.z * part;
+    if (*a >= hi) return false;
+    *e = *a + part < hi ? *a + part : hi;
+    return true;
+}
+
+// counts[q] += the entries of segment blockIdx.y whose trace id is ids[q]
+__global__ __launch_bounds__(kAnWG) void k_an_find_count(const AnCols* __restrict__ segs, const unsigned long long* __restrict__ ids,
+                                                         uint32_t* __restrict__ counts) {
+    const AnCols sg = segs[blockIdx.y];
+    const unsigned long long id = ids[blockIdx.x];
+    unsigned long long a, e;
+    if (!an_stretch(sg, id, &a, &e)) return;
+    uint32_t c = 0;
+    for (unsigned long long i = a + threadIdx.x; i < e; i += kAnWG) c += sg.tid[i] == id ? 1u : 0u;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
+    if (lane_id() == 0 && c) atomicAdd(&counts[blockIdx.x], c);
+}
+
+// The matching rows behind base[q]: a wave draws its matches' places with one returning atomic on cursor[q]
+// (from 0); a place at or past counts[q], or a row at or past out.n, is dropped. The loop's bounds are the
+// same for all threads of a workgroup, so every lane reaches the ballot and the shuffle.
+__global__ __launch_bounds__(kAnWG) void k_an_find_write(const AnCols* __restrict__ segs, const unsigned long long* __restrict__ ids,
+                                                         const uint32_t* __restrict__ counts, uint32_t* __restrict__ cursor,
+                                                         const unsigned long long* __restrict__ base, AnCols out) {
+    const AnCols sg = segs[blockIdx.y];
+    const uint32_t q = blockIdx.x;
+    const unsigned long long id = ids[q];
+    unsigned long long a, e;
+    if (!an_stretch(sg, id, &a, &e)) return;
+    const uint32_t limit = counts[q];
+    const unsigned long long row0 = base[q];
+    for (unsigned long long tile = a; tile < e; tile += kAnWG) {
+        const unsigned long long i = tile + threadIdx.x;
+        const bool hit = i < e && sg.tid[i] == id;
+        const unsigned long long m = __ballot(hit);
+        if (!m) continue;  // (wave-uniform)
+        const int lead = __ffsll((long long)m) - 1;
+        uint32_t first = 0;
+        if ((int)lane_id() == lead) first = atomicAdd(&cursor[q], (uint32_t)__popcll(m));
+        first = __shfl(first, lead);
+        if (hit) {
+            const unsigned long long r = (unsigned long long)first + rank_in(m);
+            const unsigned long long at = row0 + r;
+            if (r < limit && at < out.n) {
+                out.tid[at] = id;
+                out.span[at] = sg.span[i];
+                out.ts[at] = sg.ts[i];
+                out.val[at] = sg.val[i];
+                out.ip[at] = sg.ip[i];
+                out.svc[at] = sg.svc[i];
+                out.bits[at] = sg.bits[i];
+            }
+        }
+    }
+}
+
+size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+
+// seven columns of n entries in one block, each 256-B aligned; with_off: off[4097] behind them
+struct Block {
+    static size_t col8(uint64_t n) { return al256((size_t)n * 8); }
+    static size_t col4(uint64_t n) { return al256((size_t)n * 4); }
+    static size_t cols_bytes(uint64_t n) { return 4 * col8(n) + 3 * col4(n); }
+    static AnCols view(void* block, uint64_t n, bool with_off) {
+        uint8_t* p = (uint8_t*)block;
+        const size_t a8 = col8(n), a4 = col4(n);
+        return AnCols{(unsigned long long*)p, (unsigned long long*)(p + a8), (long long*)(p + 2 * a8),
+                      (unsigned long long*)(p + 3 * a8), (uint32_t*)(p + 4 * a8), (uint32_t*)(p + 4 * a8 + a4),
+                      (uint32_t*)(p + 4 * a8 + 2 * a4), with_off ? (uint32_t*)(p + 4 * a8 + 3 * a4) : nullptr,
+                      (unsigned long long)n};
+    }
+};
+
+struct Segment {
+    void* block = nullptr;
+    size_t bytes = 0;
+    uint64_t n = 0;
+    std::vector<uint32_t> off;  // kAnBins + 1
+
+    static size_t bytes_for(uint64_t n) { return Block::cols_bytes(n) + al256((kAnBins + 1) * 4); }
+    AnCols cols() const { return Block::view(block, n, true); }
+};
+
+}  // namespace
+}  // namespace zk
+
+using namespace zk;
+
+struct zk_an {
+    int device = 0;
+    bool opened = false;     // the device is checked and the stream exists (the first observe with rows)
+    hipStream_t stream = nullptr, own = nullptr;
+    bool timing = false;
+    std::vector<Segment> segs;
+    uint64_t entries = 0;
+    void* obs = nullptr;     // the observe's counts and cursors (kObsBytes)
+    void* stage = nullptr;   // the seven columns of a host batch
+    void* mplan = nullptr;   // a merge's bases, per old segment
+    void* q = nullptr;       // the lookups' block (kQBytes)
+    void* rows = nullptr;    // the write pass's rows, seven columns
+    size_t stage_bytes = 0, mplan_bytes = 0, rows_bytes = 0;
+    std::vector<uint32_t> counts_host, cursor_host, off_host;  // (queued copies read the last two: they change only behind a synchronisation)
+    std::vector<uint32_t> mplan_host, moff_host;
+    std::vector<uint64_t> ids_host, base_host;
+    std::vector<AnCols> segs_host;
+    std::vector<uint8_t> rows_host;
+    hipEvent_t oev[4] = {};  // around the passes of the last observe (zk_an_observe_ms)
+    hipEvent_t qev[2] = {};  // around the last lookup (zk_an_query_ms)
+    bool otimed = false, qtimed = false;
+    std::string err;
+};
+
+namespace {
+
+zk_status afail(zk_an* h, zk_status s, const std::string& m) {
+    if (h) h->err = m;
+    return s;
+}
+
+#define AN_HIP(h, call)                                                                            \
+    do {                                                                                           \
+        hipError_t _e = (call);                                                                    \
+        if (_e != hipSuccess) return afail(h, is_refusal(_e) ? ZK_ERR_CAPACITY : ZK_ERR_HIP,       \
+                                           std::string(#call) + ": " + launch_error_str(_e));      \
+    } while (0)
+
+// the first call that needs the device: it must be a gfx950; the private stream is made here
+zk_status open_device(zk_an* h) {
+    if (h->opened) return ZK_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0 || h->device >= ndev) {
+        (void)hipGetLastError();
+        return afail(h, ZK_ERR_NO_DEVICE, "no such HIP device");
+    }
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) return afail(h, ZK_ERR_NO_DEVICE, "no such HIP device");
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return afail(h, ZK_ERR_NO_DEVICE, "the device is not a gfx950");
+    AN_HIP(h, hipSetDevice(h->device));
+    if (!h->stream) {
+        AN_HIP(h, hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
+        h->stream = h->own;
+    }
+    h->opened = true;
+    return ZK_OK;
+}
+
+// a fresh block of `need` bytes; a refused allocation is ZK_ERR_CAPACITY
+zk_status alloc(zk_an* h, void** p, size_t need, const char* what) {
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, need ? need : 8);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (e != hipErrorOutOfMemory) return afail(h, ZK_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+        return afail(h, ZK_ERR_CAPACITY, std::string("no device memory for ") + what);
+    }
+    *p = q;
+    return ZK_OK;
+}
+
+// at least `need` bytes behind *p: a larger block first, then the old one freed (its content is not kept);
+// a refused allocation leaves *p as it was
+zk_status grow(zk_an* h, void** p, size_t* have, size_t need, const char* what) {
+    if (need <= *have && *p) return ZK_OK;
+    void* q = nullptr;
+    const zk_status st = alloc(h, &q, need, what);
+    if (st != ZK_OK) return st;
+    if (*p) {
+        (void)hipStreamSynchronize(h->stream);
+        (void)hipFree(*p);
+    }
+    *p = q;
+    *have = need;
+    return ZK_OK;
+}
+
+void free_segments(zk_an* h) {
+    if (!h->segs.empty()) (void)hipStreamSynchronize(h->stream);
+    for (Segment& g : h->segs)
+        if (g.block) (void)hipFree(g.block);
+    h->segs.clear();
+}
+
+// All segments into one: each bucket's slices concatenated in segment order. Anything refused leaves the
+// store as it was. Synchronises.
+zk_status merge_all(zk_an* h) {
+    const uint32_t G = (uint32_t)h->segs.size();
+    if (G < 2) return ZK_OK;
+    Segment m;
+    m.n = h->entries;
+    m.off.assign(kAnBins + 1, 0);
+    std::vector<uint64_t> wide(kAnBins + 1, 0);
+    for (uint32_t b = 0; b < kAnBins; ++b) {
+        uint64_t c = 0;
+        for (const Segment& sg : h->segs) c += sg.off[b + 1] - sg.off[b];
+        wide[b + 1] = wide[b] + c;
+    }
+    if (wide[kAnBins] != m.n || m.n > kAnMaxEntries) return afail(h, ZK_ERR_HIP, "the segments' offsets do not add up");
+    for (uint32_t b = 0; b <= kAnBins; ++b) m.off[b] = (uint32_t)wide[b];
+    // per old segment: the bases of its slices in the merged segment [kAnBins]
+    h->mplan_host.assign((size_t)kAnBins * G, 0);
+    std::vector<uint32_t> next(m.off.begin(), m.off.begin() + kAnBins);
+    for (uint32_t g = 0; g < G; ++g) {
+        const Segment& sg = h->segs[g];
+        for (uint32_t b = 0; b < kAnBins; ++b) {
+            h->mplan_host[(size_t)kAnBins * g + b] = next[b];
+            next[b] += sg.off[b + 1] - sg.off[b];
+        }
+    }
+    zk_status st = grow(h, &h->mplan, &h->mplan_bytes, (size_t)kAnBins * G * 4, "a merge's bases");
+    if (st != ZK_OK) return st;
+    m.bytes = Segment::bytes_for(m.n);
+    if ((st = alloc(h, &m.block, m.bytes, "the merged segment (44 B per entry)")) != ZK_OK) return st;
+    const AnCols dst = m.cols();
+    h->moff_host = m.off;
+    hipError_t e = hipMemcpyAsync(h->mplan, h->mplan_host.data(), (size_t)kAnBins * G * 4, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dst.off, h->moff_host.data(), (kAnBins + 1) * 4, hipMemcpyHostToDevice, h->stream);
+    for (uint32_t g = 0; g < G && e == hipSuccess; ++g) {
+        const Segment& sg = h->segs[g];
+        e = launch_checked("k_an_merge", k_an_merge, dim3(an_grid(sg.n)), dim3(kAnWG), 0, h->stream, sg.cols(),
+                           (const uint32_t*)h->mplan + (size_t)kAnBins * g, dst);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream);
+        (void)hipFree(m.block);
+        return afail(h, is_refusal(e) ? ZK_ERR_CAPACITY : ZK_ERR_HIP, std::string("merging the segments: ") + launch_error_str(e));
+    }
+    free_segments(h);
+    h->segs.push_back(std::move(m));
+    return ZK_OK;
+}
+
+// The lookups' count pass: the ids into the block (from the host or the device), counts[n] back. *parts =
+// the grid's z of both passes. Synchronises; needs a store with segments.
+zk_status find_count(zk_an* h, const uint64_t* ids, uint32_t n, uint32_t flags, uint32_t* counts, uint32_t* parts) {
+    zk_status st;
+    if (!h->q && (st = alloc(h, &h->q, kQBytes, "the lookups' block")) != ZK_OK) return st;
+    uint8_t* qb = (uint8_t*)h->q;
+    unsigned long long* d_ids = (unsigned long long*)(qb + kQIdsAt);
+    uint32_t* d_counts = (uint32_t*)(qb + kQCountsAt);
+    const uint32_t G = (uint32_t)h->segs.size();
+    // the host needs the ids too: it sizes the grid by the longest asked slice
+    h->ids_host.resize(n);
+    if (flags & ZK_BATCH_DEVICE_PTRS) {
+        AN_HIP(h, hipMemcpyAsync(d_ids, ids, (size_t)n * 8, hipMemcpyDeviceToDevice, h->stream));
+        AN_HIP(h, hipMemcpyAsync(h->ids_host.data(), ids, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+        AN_HIP(h, hipStreamSynchronize(h->stream));
+    } else {
+        memcpy(h->ids_host.data(), ids, (size_t)n * 8);
+        AN_HIP(h, hipMemcpyAsync(d_ids, h->ids_host.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    uint64_t longest = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t b = an_bucket(h->ids_host[i]);
+        for (const Segment& sg : h->segs) longest = std::max<uint64_t>(longest, sg.off[b + 1] - sg.off[b]);
+    }
+    uint64_t z = std::min<uint64_t>(kAnMaxParts, std::max<uint64_t>(1, (longest + kAnPart - 1) / kAnPart));
+    z = std::max<uint64_t>(1, std::min<uint64_t>(z, kAnMaxFindGrid / ((uint64_t)n * G)));
+    *parts = (uint32_t)z;
+    h->segs_host.clear();
+    for (const Segment& sg : h->segs) h->segs_host.push_back(sg.cols());
+    AN_HIP(h, hipMemcpyAsync(qb + kQSegsAt, h->segs_host.data(), G * sizeof(AnCols), hipMemcpyHostToDevice, h->stream));
+    AN_HIP(h, hipMemsetAsync(d_counts, 0, (size_t)n * 4, h->stream));
+    for (hipEvent_t& e : h->qev)
+        if (h->timing && !e) AN_HIP(h, hipEventCreate(&e));
+    h->qtimed = false;
+    if (h->timing) AN_HIP(h, hipEventRecord(h->qev[0], h->stream));
+    AN_HIP(h, launch_checked("k_an_find_count", k_an_find_count, dim3(n, G, *parts), dim3(kAnWG), 0, h->stream,
+                             (const AnCols*)(qb + kQSegsAt), (const unsigned long long*)d_ids, d_counts));
+    AN_HIP(h, hipMemcpyAsync(counts, d_counts, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    AN_HIP(h, hipStreamSynchronize(h->stream));
+    return ZK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+zk_status zk_an_create(const zk_an_config* cfg, zk_an** out) {
+    ZK_GUARD_BEGIN
+    if (!cfg || !out) return ZK_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (cfg->device < 0) return ZK_ERR_INVALID_ARG;
+    zk_an* h = new zk_an();
+    h->device = cfg->device;
+    h->timing = cfg->timing != 0;
+    h->stream = (hipStream_t)cfg->stream;  // (NULL: a private stream, made with the device's first use)
+    *out = h;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_an_destroy(zk_an* h) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (h->opened) {
+        (void)hipSetDevice(h->device);
+        if (h->stream) (void)hipStreamSynchronize(h->stream);
+        free_segments(h);
+        for (void* p : {h->obs, h->stage, h->mplan, h->q, h->rows})
+            if (p) (void)hipFree(p);
+        for (hipEvent_t e : h->oev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : h->qev)
+            if (e) (void)hipEventDestroy(e);
+        if (h->own) (void)hipStreamDestroy(h->own);
+    }
+    delete h;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+const char* zk_an_last_error(const zk_an* h) { return h ? h->err.c_str() : "null handle"; }
+
+zk_status zk_an_observe(zk_an* h, const zk_an_cols* in, uint64_t n, uint32_t flags) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (!in) return afail(h, ZK_ERR_INVALID_ARG, "null argument");
+    if (flags & ~ZK_BATCH_DEVICE_PTRS) return afail(h, ZK_ERR_INVALID_ARG, "unknown batch flag");
+    if (n >= (1ull << 32)) return afail(h, ZK_ERR_UNSUPPORTED, "2^32 rows or more in one batch");
+    if (n == 0) return ZK_OK;
+    if (!in->trace_id || !in->span_id || !in->ts || !in->value || !in->ipv4 || !in->service_id || !in->bits)
+        return afail(h, ZK_ERR_INVALID_ARG, "null column");
+    if (h->entries + n > kAnMaxEntries) return afail(h, ZK_ERR_CAPACITY, "more than 2^32 - 1 entries in one store");
+    zk_status st;
+    if ((st = open_device(h)) != ZK_OK) return st;
+    AN_HIP(h, hipSetDevice(h->device));
+    if (!h->obs && (st = alloc(h, &h->obs, kObsBytes, "the observe's counters")) != ZK_OK) return st;
+    AnCols src{(unsigned long long*)in->trace_id, (unsigned long long*)in->span_id, (long long*)in->ts,
+               (unsigned long long*)in->value, (uint32_t*)in->ipv4, (uint32_t*)in->service_id, (uint32_t*)in->bits, nullptr,
+               (unsigned long long)n};
+    if (!(flags & ZK_BATCH_DEVICE_PTRS)) {
+        // a host batch: the seven columns staged (each 256-B aligned)
+        if ((st = grow(h, &h->stage, &h->stage_bytes, Block::cols_bytes(n), "staging a host batch (44 B per row)")) != ZK_OK)
+            return st;
+        const AnCols s = Block::view(h->stage, n, false);
+        AN_HIP(h, hipMemcpyAsync(s.tid, in->trace_id, n * 8, hipMemcpyHostToDevice, h->stream));
+        AN_HIP(h, hipMemcpyAsync(s.span, in->span_id, n * 8, hipMemcpyHostToDevice, h->stream));
+        AN_HIP(h, hipMemcpyAsync(s.ts, in->ts, n * 8, hipMemcpyHostToDevice, h->stream));
+        AN_HIP(h, hipMemcpyAsync(s.val, in->value, n * 8, hipMemcpyHostToDevice, h->stream));
+        AN_HIP(h, hipMemcpyAsync(s.ip, in->ipv4, n * 4, hipMemcpyHostToDevice, h->stream));
+        AN_HIP(h, hipMemcpyAsync(s.svc, in->service_id, n * 4, hipMemcpyHostToDevice, h->stream));
+        AN_HIP(h, hipMemcpyAsync(s.bits, in->bits, n * 4, hipMemcpyHostToDevice, h->stream));
+        src = s;
+    }
+    uint32_t* counts = (uint32_t*)h->obs;
+    uint32_t* cursor = (uint32_t*)((uint8_t*)h->obs + kObsCursorAt);
+    const bool timing = h->timing;
+    for (hipEvent_t& e : h->oev)
+        if (timing && !e) AN_HIP(h, hipEventCreate(&e));
+    h->otimed = false;
+    AN_HIP(h, hipMemsetAsync(counts, 0, kAnBins * 4, h->stream));
+    if (timing) AN_HIP(h, hipEventRecord(h->oev[0], h->stream));
+    AN_HIP(h, launch_checked("k_an_count", k_an_count, dim3(an_grid((n + kAnCntItems - 1) / kAnCntItems, kAnHistGrid)), dim3(kAnWG), 0,
+                             h->stream, (const unsigned long long*)src.tid, (unsigned long long)n, counts));
+    if (timing) AN_HIP(h, hipEventRecord(h->oev[1], h->stream));
+    h->counts_host.resize(kAnBins);
+    AN_HIP(h, hipMemcpyAsync(h->counts_host.data(), counts, kAnBins * 4, hipMemcpyDeviceToHost, h->stream));
+    AN_HIP(h, hipStreamSynchronize(h->stream));  // the call's one synchronisation (also: the staging copies are done)
+    Segment g;
+    g.off.assign(kAnBins + 1, 0);
+    uint64_t total = 0;
+    for (uint32_t b = 0; b < kAnBins; ++b) {
+        total += h->counts_host[b];
+        if (total > n) return afail(h, ZK_ERR_HIP, "the bucket counts exceed the batch");
+        g.off[b + 1] = (uint32_t)total;
+    }
+    if (total != n) return afail(h, ZK_ERR_HIP, "the bucket counts do not add up to the batch");
+    g.n = n;
+    if (h->segs.size() >= ZK_AN_MAX_SEGMENTS && (st = merge_all(h)) != ZK_OK) return st;
+    g.bytes = Segment::bytes_for(g.n);
+    if ((st = alloc(h, &g.block, g.bytes, "a segment (44 B per entry)")) != ZK_OK) return st;
+    const AnCols dst = g.cols();
+    h->cursor_host.assign(g.off.begin(), g.off.begin() + kAnBins);
+    h->off_host = g.off;
+    uint32_t grid = (uint32_t)((n + kAnScatterPerWG - 1) / kAnScatterPerWG);
+    grid = grid < 1 ? 1 : grid > kAnMaxGrid ? kAnMaxGrid : grid;
+    const uint64_t chunk = ((n + grid - 1) / grid + kAnWG - 1) / kAnWG * kAnWG;
+    hipError_t e = hipMemcpyAsync(cursor, h->cursor_host.data(), kAnBins * 4, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dst.off, h->off_host.data(), (kAnBins + 1) * 4, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && timing) e = hipEventRecord(h->oev[2], h->stream);
+    if (e == hipSuccess)
+        e = launch_checked("k_an_scatter", k_an_scatter, dim3(grid), dim3(kAnWG), 0, h->stream, src, (unsigned long long)chunk, cursor, dst);
+    if (e == hipSuccess && timing) e = hipEventRecord(h->oev[3], h->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream);
+        (void)hipFree(g.block);
+        return afail(h, is_refusal(e) ? ZK_ERR_CAPACITY : ZK_ERR_HIP, std::string("k_an_scatter: ") + launch_error_str(e));
+    }
+    h->entries += g.n;
+    h->segs.push_back(std::move(g));
+    h->otimed = timing;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_an_observe_ms(zk_an* h, double out[3]) {
+    ZK_GUARD_BEGIN
+    if (!h || !out) return ZK_ERR_INVALID_ARG;
+    if (!h->otimed) return afail(h, ZK_ERR_INVALID_ARG, "no timed observe has added a segment (zk_an_config.timing)");
+    AN_HIP(h, hipSetDevice(h->device));
+    AN_HIP(h, hipEventSynchronize(h->oev[3]));
+    for (int k = 0; k < 3; ++k) {
+        float ms = 0.f;
+        AN_HIP(h, hipEventElapsedTime(&ms, h->oev[k], h->oev[k + 1]));
+        out[k] = ms;
+    }
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_an_reset(zk_an* h) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (h->segs.empty()) return ZK_OK;
+    AN_HIP(h, hipSetDevice(h->device));
+    free_segments(h);
+    h->entries = 0;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_an_compact(zk_an* h) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (h->segs.size() < 2) return ZK_OK;
+    AN_HIP(h, hipSetDevice(h->device));
+    return merge_all(h);
+    ZK_GUARD_END
+}
+
+zk_status zk_an_info(zk_an* h, uint64_t* entries, uint64_t* segments, uint64_t* bytes) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (!h->segs.empty()) {
+        AN_HIP(h, hipSetDevice(h->device));
+        AN_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    uint64_t b = 0;
+    for (const Segment& g : h->segs) b += g.bytes;
+    if (entries) *entries = h->entries;
+    if (segments) *segments = h->segs.size();
+    if (bytes) *bytes = b;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_an_gather(zk_an* h, const uint64_t* ids, uint32_t n, uint32_t flags, uint32_t* counts, zk_an_cols* out, uint64_t cap,
+                       uint64_t* n_out) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (!n_out) return afail(h, ZK_ERR_INVALID_ARG, "null argument");
+    if (flags & ~ZK_BATCH_DEVICE_PTRS) return afail(h, ZK_ERR_INVALID_ARG, "unknown flag");
+    if (n > ZK_AN_MAX_IDS) return afail(h, ZK_ERR_INVALID_ARG, "more than ZK_AN_MAX_IDS ids");
+    if (n && !ids) return afail(h, ZK_ERR_INVALID_ARG, "null argument");
+    if (n && !counts) return afail(h, ZK_ERR_INVALID_ARG, "null argument");
+    if (cap && (!out || !out->trace_id || !out->span_id || !out->ts || !out->value || !out->ipv4 || !out->service_id || !out->bits))
+        return afail(h, ZK_ERR_INVALID_ARG, "null output column");
+    *n_out = 0;
+    if (n == 0) return ZK_OK;
+    memset(counts, 0, (size_t)n * 4);
+    if (h->segs.empty()) return ZK_OK;
+    AN_HIP(h, hipSetDevice(h->device));
+    zk_status st;
+    uint32_t parts = 1;
+    if ((st = find_count(h, ids, n, flags, counts, &parts)) != ZK_OK) return st;
+    h->base_host.resize(n);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        h->base_host[i] = total;
+        total += counts[i];
+    }
+    *n_out = total;
+    if (total > cap) return afail(h, ZK_ERR_CAPACITY, "the output columns hold fewer rows than the asked traces have");
+    if (total == 0) return ZK_OK;
+    if ((st = grow(h, &h->rows, &h->rows_bytes, Block::cols_bytes(total), "the gathered rows (44 B each)")) != ZK_OK) return st;
+    h->rows_host.resize(Block::cols_bytes(total));
+    uint8_t* qb = (uint8_t*)h->q;
+    const AnCols dev = Block::view(h->rows, total, false);
+    const uint32_t G = (uint32_t)h->segs.size();
+    AN_HIP(h, hipMemcpyAsync(qb + kQBaseAt, h->base_host.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    AN_HIP(h, hipMemsetAsync(qb + kQCursorAt, 0, (size_t)n * 4, h->stream));
+    AN_HIP(h, launch_checked("k_an_find_write", k_an_find_write, dim3(n, G, parts), dim3(kAnWG), 0, h->stream,
+                             (const AnCols*)(qb + kQSegsAt), (const unsigned long long*)(qb + kQIdsAt),
+                             (const uint32_t*)(qb + kQCountsAt), (uint32_t*)(qb + kQCursorAt),
+                             (const unsigned long long*)(qb + kQBaseAt), dev));
+    // the seven columns lie back to back, each 256-B aligned, in the device block and in the host's copy
+    AN_HIP(h, hipMemcpyAsync(h->rows_host.data(), h->rows, Block::cols_bytes(total), hipMemcpyDeviceToHost, h->stream));
+    if (h->timing) AN_HIP(h, hipEventRecord(h->qev[1], h->stream));
+    AN_HIP(h, hipStreamSynchronize(h->stream));
+    h->qtimed = h->timing;
+    // every trace's rows into CANONICAL order (the trace id is the asked one)
+    const AnCols r = Block::view(h->rows_host.data(), total, false);
+    static thread_local std::vector<uint64_t> perm;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t at = h->base_host[i], c = counts[i];
+        if (!c) continue;
+        perm.resize(c);
+        std::iota(perm.begin(), perm.end(), at);
+        std::sort(perm.begin(), perm.end(), [&r](uint64_t x, uint64_t y) {
+            if (r.span[x] != r.span[y]) return r.span[x] < r.span[y];
+            if (r.ts[x] != r.ts[y]) return r.ts[x] < r.ts[y];
+            const uint32_t bx = r.bits[x], by = r.bits[y];
+            if ((bx & ZK_AN_KIND_MASK) != (by & ZK_AN_KIND_MASK)) return (bx & ZK_AN_KIND_MASK) < (by & ZK_AN_KIND_MASK);
+            if (r.val[x] != r.val[y]) return r.val[x] < r.val[y];
+            if (r.ip[x] != r.ip[y]) return r.ip[x] < r.ip[y];
+            if ((bx >> ZK_AN_PORT_SHIFT) != (by >> ZK_AN_PORT_SHIFT)) return (bx >> ZK_AN_PORT_SHIFT) < (by >> ZK_AN_PORT_SHIFT);
+            if (r.svc[x] != r.svc[y]) return r.svc[x] < r.svc[y];
+            if ((bx & ZK_AN_HAS_HOST) != (by & ZK_AN_HAS_HOST)) return (bx & ZK_AN_HAS_HOST) < (by & ZK_AN_HAS_HOST);
+            return bx < by;
+        });
+        for (uint64_t k = 0; k < c; ++k) {
+            const uint64_t s = perm[k], d = at + k;
+            out->trace_id[d] = r.tid[s];
+            out->span_id[d] = r.span[s];
+            out->ts[d] = r.ts[s];
+            out->value[d] = r.val[s];
+            out->ipv4[d] = r.ip[s];
+            out->service_id[d] = r.svc[s];
+            out->bits[d] = r.bits[s];
+        }
+    }
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_an_query_ms(zk_an* h, double* ms) {
+    ZK_GUARD_BEGIN
+    if (!h || !ms) return ZK_ERR_INVALID_ARG;
+    if (!h->qtimed) return afail(h, ZK_ERR_INVALID_ARG, "no timed lookup has run a pass (zk_an_config.timing)");
+    AN_HIP(h, hipSetDevice(h->device));
+    float f = 0.f;
+    AN_HIP(h, hipEventElapsedTime(&f, h->qev[0], h->qev[1]));
+    *ms = f;
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+}  // extern "C"

@@ -193,6 +193,8 @@ struct Host {
     bool present = false;
     const char* svc = nullptr;  // null: absent field
     uint32_t svc_len = 0;
+    int32_t ipv4 = 0;  // field 1 (read for the annotation rows only)
+    int16_t port = 0;  // field 2
 };
 struct Ann {
     int64_t ts = 0;
@@ -232,6 +234,10 @@ void read_endpoint(Rd& r, Host* h) {
         const int16_t id = r.i16();
         if (id == 3 && t == T_STRING)
             r.str(&h->svc, &h->svc_len);
+        else if (id == 1 && t == T_I32)
+            h->ipv4 = r.i32();
+        else if (id == 2 && t == T_I16)
+            h->port = r.i16();
         else
             r.skip(t);
     }
@@ -381,6 +387,7 @@ struct Decoded {
     uint32_t kv0, kv_n, ann0, ann_n;
     int32_t span_name;  // ZK_INGEST_SPAN_NAMES: index into DecodeRange::span_names, -1: no name (id 0)
     uint32_t ix0 = 0, ix_n = 0;  // zk_ingest_spans_indexed: the record's entries in DecodeRange::ix
+    uint32_t an0 = 0, an_n = 0;  // zk_ingest_spans_annotated: the record's rows in DecodeRange::rows
 };
 // an entry of the annotation index before its service id is known
 struct IxItem {
@@ -388,11 +395,18 @@ struct IxItem {
     uint64_t val;  // 0: a time annotation
     int64_t ts;
 };
+// a row of the annotation store (zkannots.h) before its service id is known
+struct AnRow {
+    Item value;  // the host's name (-1: no host), the value's string and its hash
+    int64_t ts;
+    uint32_t ipv4, bits;
+};
 struct DecodeRange {
     uint64_t lo = 0, hi = 0;
     std::vector<Decoded> recs;
     std::vector<Item> kv, ann;
     std::vector<IxItem> ix;
+    std::vector<AnRow> rows;
     std::vector<std::string> names, strs;
     std::unordered_map<std::string, int32_t> name_ix;
     std::unordered_map<uint64_t, uint32_t> str_ix;
@@ -424,7 +438,8 @@ struct DecodeRange {
         span_names.push_back(std::move(s));
         return ix;
     }
-    Item item(const Host& h, const char* s, uint32_t l) {
+    Item item(const Host& h, const char* s, uint32_t l) { return item_of(name(h), s, l); }
+    Item item_of(int32_t host_name, const char* s, uint32_t l) {
         const uint64_t hash = zk_hash_string(s, l);
         auto it = str_ix.find(hash);
         uint32_t ix;
@@ -435,7 +450,7 @@ struct DecodeRange {
             str_ix.emplace(hash, ix);
             strs.emplace_back(s ? s : "", s ? l : 0);
         }
-        return Item{name(h), ix, hash};
+        return Item{host_name, ix, hash};
     }
 };
 
@@ -449,7 +464,7 @@ bool is_client_name(const Host& h) {
 
 // want_ix: 0 no index entries, 1 with the shouldIndex rule, 2 without it
 void decode_range(const uint8_t* buf, const uint64_t* offsets, uint32_t codec, bool strict, bool want_kv,
-                  bool want_ann, bool want_names, int want_ix, DecodeRange* d) {
+                  bool want_ann, bool want_names, int want_ix, bool want_rows, DecodeRange* d) {
     std::vector<uint8_t> scratch;
     SpanT s;
     std::vector<const Ann*> distinct;
@@ -579,6 +594,20 @@ void decode_range(const uint8_t* buf, const uint64_t* offsets, uint32_t codec, b
                     if (b.host.present)
                         d->ix.push_back(IxItem{d->item(b.host, b.key, b.key_len), zk_index_value_hash(b.value, b.value_len), last});
         }
+        // ---- the annotation store's rows: one per annotation, in the list's order ----
+        rec.an0 = (uint32_t)d->rows.size();
+        if (want_rows)
+            for (const Ann& a : s.anns) {
+                uint32_t bits = 0;
+                if (is_core(a.value, a.value_len))
+                    bits = a.value[0] == 'c' ? (a.value[1] == 's' ? 1u : 2u) : (a.value[1] == 'r' ? 3u : 4u);
+                if (a.host.present) bits |= 8u | ((uint32_t)(uint16_t)a.host.port << 16);
+                // (the value's item first: name() of the host then follows it, as for the other items)
+                const Item it = d->item_of(-1, a.value, a.value_len);
+                d->rows.push_back(AnRow{Item{a.host.present ? d->name(a.host) : -1, it.str, it.hash}, a.ts,
+                                        a.host.present ? (uint32_t)a.host.ipv4 : 0u, bits});
+            }
+        rec.an_n = (uint32_t)d->rows.size() - rec.an0;
         rec.kv_n = (uint32_t)d->kv.size() - rec.kv0;
         rec.ann_n = (uint32_t)d->ann.size() - rec.ann0;
         rec.ix_n = (uint32_t)d->ix.size() - rec.ix0;
@@ -749,15 +778,16 @@ const char* zk_ingest_last_error(const zk_ingest* g) { return g ? g->err.c_str()
 
 uint64_t zk_index_value_hash(const char* s, uint64_t len) { return zk_hash_string(s, len) | 1ull; }
 
-// zk_ingest_spans (ix == nullptr) and zk_ingest_spans_indexed (items == nullptr)
+// zk_ingest_spans (ix == nullptr), zk_ingest_spans_indexed (items == nullptr) and zk_ingest_spans_annotated (an)
 static zk_status ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
                               uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
-                              zk_ingest_items* items, zk_ingest_index_items* ix) {
+                              zk_ingest_items* items, zk_ingest_index_items* ix, zk_ingest_annotation_rows* an = nullptr) {
     ZK_GUARD_BEGIN
     if (!g || !n_out || !n_rejected) return ZK_ERR_INVALID_ARG;
     *n_out = *n_rejected = 0;
     if (items) items->kv_n = items->ann_n = 0;
     if (ix) ix->n = 0;
+    if (an) an->n = 0;
     if (n == 0) return ZK_OK;
     if (!buf || !offsets || !out || !out->trace_id || !out->span_id || !out->parent_id || !out->first_ts ||
         !out->last_ts || !out->service_id || !out->flags)
@@ -785,7 +815,7 @@ static zk_status ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* 
         d.lo = n * t / T;
         d.hi = n * (t + 1) / T;
         try {
-            decode_range(buf, offsets, codec, strict, want_kv, want_ann, want_names, want_ix, &d);
+            decode_range(buf, offsets, codec, strict, want_kv, want_ann, want_names, want_ix, an != nullptr, &d);
         } catch (...) {
             d.err_index = d.lo;
             d.err_status = ZK_ERR_CAPACITY;
@@ -872,6 +902,22 @@ static zk_status ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* 
                 keep(it.key);
                 ++ix->n;
             }
+            for (uint32_t q = r.an0; q < r.an0 + r.an_n; ++q) {
+                if (an->n >= an->cap) {
+                    item_overflow = true;
+                    continue;
+                }
+                const AnRow& it = d.rows[q];
+                an->trace_id[an->n] = r.tid;
+                an->span_id[an->n] = r.sid;
+                an->ts[an->n] = it.ts;
+                an->value[an->n] = it.value.hash;
+                an->ipv4[an->n] = it.ipv4;
+                an->service_id[an->n] = it.value.name >= 0 ? id_of(it.value.name) : 0u;
+                an->bits[an->n] = it.bits;
+                keep(it.value);
+                ++an->n;
+            }
         }
         *n_rejected += d.rejected;
         if (d.err_index != UINT64_MAX) {  // the first error of the batch (ranges are in input order)
@@ -899,6 +945,14 @@ zk_status zk_ingest_spans_indexed(zk_ingest* g, const uint8_t* buf, const uint64
                                   zk_ingest_index_items* ix) {
     if (!ix || !ix->service || !ix->key || !ix->val || !ix->ts || !ix->trace_id) return ZK_ERR_INVALID_ARG;
     return ingest_spans(g, buf, offsets, n, codec, flags, out, n_out, n_rejected, nullptr, ix);
+}
+
+zk_status zk_ingest_spans_annotated(zk_ingest* g, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
+                                    uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
+                                    zk_ingest_items* items, zk_ingest_annotation_rows* an) {
+    if (!an || !an->trace_id || !an->span_id || !an->ts || !an->value || !an->ipv4 || !an->service_id || !an->bits)
+        return ZK_ERR_INVALID_ARG;
+    return ingest_spans(g, buf, offsets, n, codec, flags, out, n_out, n_rejected, items, nullptr, an);
 }
 
 zk_status zk_ingest_num_services(const zk_ingest* g, uint32_t* n) {

@@ -130,6 +130,35 @@ class SpanDecoder:
         self._check(st)
         return cols.take(slice(0, nout.value)), int(nrej.value), items
 
+    def decode_annotated(self, blobs, *, snappy: bool = True, strict: bool = True, span_names: bool = False,
+                         row_cap: int | None = None, one_thread: bool = False):
+        """decode() that also returns the annotation store's rows (zk_ingest_spans_annotated):
+        (SpanColumns, rejected, annotstore.AnnotationRows), one row per time annotation of every accepted
+        span, in record order and the annotation list's order. row_cap: the rows to allow for (default 8
+        per fragment, at least 16); a batch with more raises ZK_ERR_CAPACITY, and the exception's `rows`
+        then holds the first row_cap rows. A batch that may hold more says so with row_cap."""
+        from .annotstore import AnnotationRows
+
+        buf, offsets, n = _pack(blobs)
+        cols = SpanColumns.empty(n)
+        nout, nrej = C.c_uint64(), C.c_uint64()
+        cap = int(row_cap) if row_cap is not None else max(16, 8 * n)
+        rows = AnnotationRows.empty(cap)
+        an = rows.ingest_abi(cap=cap, n=0)
+        codec = _abi.ZK_CODEC_SNAPPY_THRIFT if snappy else _abi.ZK_CODEC_THRIFT
+        flags = (_abi.ZK_INGEST_STRICT if strict else 0) | (_abi.ZK_INGEST_ONE_THREAD if one_thread else 0)
+        flags |= _abi.ZK_INGEST_SPAN_NAMES if span_names else 0
+        ab = cols.abi()
+        st = self._L.zk_ingest_spans_annotated(self._h, buf.ctypes.data, offsets.ctypes.data, n, codec, flags,
+                                               C.byref(ab), C.byref(nout), C.byref(nrej), None, C.byref(an))
+        rows = rows.take(slice(0, int(an.n)))
+        if st == _abi.ZK_ERR_CAPACITY:
+            e = _abi.ZkError(st, self._L.zk_ingest_last_error(self._h).decode() or _abi.status_str(st))
+            e.rows = rows
+            raise e
+        self._check(st)
+        return cols.take(slice(0, nout.value)), int(nrej.value), rows
+
     @property
     def num_services(self) -> int:
         n = C.c_uint32()

@@ -9,6 +9,11 @@ getTraceSummariesByIds without another store.
 
 A trace's fragments travel as a list of ROWS, tuples (trace_id, span_id, parent_id, first_ts, last_ts,
 service_id, flags) of Python ints, in the header's canonical order.
+
+With a TraceAnnotationStore (annotstore.py) beside it, a Trace also carries every span's annotations, and the
+query service's adjusters and timelines are built over them on the host: TimeSkewAdjuster
+(TimeSkewAdjuster.scala), TraceTimeline (TraceTimeline.scala), adjust= and annotations= on the by-id calls, and
+getTraceTimelinesByIds.
 """
 from __future__ import annotations
 
@@ -19,6 +24,8 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import _abi
+from .annotstore import (KIND_CR, KIND_CS, KIND_NAMES, KIND_SR, KIND_SS, LOOPBACK_IPV4, Annotation, AnnotationRow, Endpoint,
+                         annotation_key)
 from .columns import COLUMNS, DeviceColumns
 
 INT64_MIN, INT64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -67,6 +74,13 @@ class Span(NamedTuple):
     services: tuple
 
 
+class AnnotatedSpan(Span):
+    """A Span of a Trace that was given annotation rows: the same seven fields (it compares as a Span), and
+    `annotations`, the span's list of Annotation (canonical order as stored; list order after an adjuster)."""
+
+    annotations: List[Annotation]
+
+
 class SpanTimestamp(NamedTuple):
     """The reference's SpanTimestamp(name, startTimestamp, endTimestamp); name is the service."""
     name: Union[int, str]
@@ -93,15 +107,54 @@ class Trace:
     name id = the first non-zero one in canonical order; services = the ascending set of service_id over
     the fragments with ZK_F_SVC_CLIENT | ZK_F_SVC_SERVER. Spans are sorted by first, an untimed span as
     INT64_MAX (Trace.scala:38-43); ties go by span id ascending as unsigned (the reference's tie order is
-    a HashMap's: a stated choice)."""
+    a HashMap's: a stated choice).
+
+    annotations: the trace's annotation rows (annotstore.AnnotationRow, any order; rows of a span id the
+    trace has no record of are ignored). Every span is then an AnnotatedSpan that carries its annotations as
+    a list in canonical order, `annotations` maps span id -> that list, and the first and last of a span
+    that has annotation rows are the minimum and maximum ts of those rows; a span without rows keeps its
+    record times. Services, parent and name stay the records' rules. Without it `annotations` is None and
+    nothing changes."""
 
     def __init__(self, rows: Sequence[Row], services: Optional[Sequence[str]] = None,
-                 span_names: Optional[Sequence[str]] = None):
+                 span_names: Optional[Sequence[str]] = None, annotations: Optional[Sequence[AnnotationRow]] = None):
         self.rows: List[Row] = sorted((tuple(int(v) for v in r) for r in rows), key=canonical_key)
         self._services = None if services is None else list(services)
         self._span_names = None if span_names is None else list(span_names)
+        self.annotations: Optional[Dict[int, List[Annotation]]] = None
         self.spans: List[Span] = self._merge()
         self._given = None
+        if annotations is not None:
+            by_span: Dict[int, List[Annotation]] = {}
+            for r in sorted((tuple(int(v) for v in r) for r in annotations), key=annotation_key):
+                by_span.setdefault(r[1], []).append(Annotation.of_row(r))
+            self._annotate({s.id: by_span.get(s.id, []) for s in self.spans})
+
+    def _annotate(self, anns: Dict[int, List[Annotation]]) -> None:
+        """Every span of anns (the others are dropped) as an AnnotatedSpan with its list, the times of a
+        span with annotations from them, and the spans in span order again."""
+        spans = []
+        for s in self.spans:
+            if s.id not in anns:
+                continue
+            a = anns[s.id]
+            first, last = (min(x.ts for x in a), max(x.ts for x in a)) if a else (s.first, s.last)
+            n = AnnotatedSpan(s.trace_id, s.id, s.parent, s.name, first, last, s.services)
+            n.annotations = a
+            spans.append(n)
+        spans.sort(key=lambda s: (INT64_MAX if s.first is None else s.first, s.id))
+        self.spans = spans
+        self.annotations = {s.id: s.annotations for s in spans}
+
+    def with_annotations(self, anns: Dict[int, List[Annotation]]) -> "Trace":
+        """A Trace of this one's spans that anns names, each with the list anns gives it (an adjuster's
+        result): the trace rebuilt from them, so span times and span order follow the new lists."""
+        t = Trace.__new__(Trace)
+        t.rows = None if self.rows is None else [r for r in self.rows if r[1] in anns]
+        t._services, t._span_names, t._given = self._services, self._span_names, None
+        t.spans = list(self.spans)
+        t._annotate(anns)
+        return t
 
     @classmethod
     def of_merged(cls, spans: Sequence[Span], root_most: Optional[int], depths: Optional[Dict[int, int]]) -> "Trace":
@@ -109,7 +162,7 @@ class Trace:
         root-most span's id and the span depths that came with them: rows is None, and getRootMostSpan and
         toSpanDepths hand back what was given."""
         t = cls.__new__(cls)
-        t.rows, t._services, t._span_names = None, None, None
+        t.rows, t._services, t._span_names, t.annotations = None, None, None, None
         t.spans = list(spans)
         t._given = (root_most, depths)
         return t
@@ -261,17 +314,170 @@ class TraceSummary(NamedTuple):
         return TraceSummary(trace.id, t.start, t.end, _to_int(_wrap64(t.end - t.start)), trace.spanTimestamps(), [])
 
 
+def _jvm_half(x: int) -> int:
+    """x / 2 as the JVM divides a Long: truncated toward zero."""
+    q = abs(x) >> 1
+    return -q if x < 0 else q
+
+
+class TimeSkewAdjuster:
+    """TimeSkewAdjuster.scala over a Trace that carries annotations: the clock skew between a span's client
+    and server side is taken out of the server's annotations, from the root down. All arithmetic is the
+    JVM's (Long wraps, / 2 truncates toward zero).
+
+    Where the reference depends on arrival or hash order, these are STATED CHOICES: the children of a span
+    are the spans whose parent is its id, in span order; "first with a value" (getAnnotation) is the first in
+    the span's list and "last with a value" (getAnnotationsAsMap) the last; the list is in canonical order,
+    which breaks the ties of equal timestamps. Injected annotations carry the hashes of "sr" and "ss"."""
+
+    NAME = "TIME_SKEW"
+
+    @staticmethod
+    def skew(cs: int, cr: int, sr: int, ss: int, endpoint: Optional[Endpoint]) -> Optional[Tuple[Endpoint, int]]:
+        cd, sd = _wrap64(cr - cs), _wrap64(ss - sr)
+        if sd > cd or (cs < sr and cr > ss):  # the server side is longer: invalid; or already inside: no skew
+            return None
+        latency = _jvm_half(_wrap64(cd - sd))
+        skew = _wrap64(_wrap64(sr - latency) - cs)
+        if skew == 0 or endpoint is None:
+            return None
+        return endpoint, skew
+
+    @staticmethod
+    def _shift(anns: List[Annotation], endpoint: Endpoint, skew: int) -> None:
+        if skew == 0:
+            return
+        for i, a in enumerate(anns):
+            if a.host is not None and (a.host.ipv4 == endpoint.ipv4 or
+                                       (a.kind in (KIND_CS, KIND_CR) and a.host.ipv4 == LOOPBACK_IPV4)):
+                anns[i] = a._replace(ts=_wrap64(a.ts - skew))
+
+    @staticmethod
+    def _first(anns: List[Annotation], kinds: tuple) -> Optional[Annotation]:
+        return next((a for a in anns if a.kind in kinds), None)
+
+    @classmethod
+    def adjust(cls, trace: Trace) -> Trace:
+        """The trace with the skews taken out. Root: the first span in span order without a parent; without
+        one the trace is returned as it is, with one the result holds only the spans under it (the reference
+        rebuilds the trace from the root's tree). The walk is iterative: a chain of any length is fine."""
+        from .ingest import hash_string
+
+        root = trace.getRootSpan()
+        if root is None:
+            return trace
+        given = trace.annotations or {}
+        anns: Dict[int, List[Annotation]] = {s.id: list(given.get(s.id, ())) for s in trace.spans}
+        children = trace.getIdToChildrenMap()
+        h_sr, h_ss = hash_string("sr"), hash_string("ss")
+        out: Dict[int, List[Annotation]] = {}
+        stack: List[Tuple[int, Optional[Tuple[Endpoint, int]]]] = [(root.id, None)]
+        while stack:
+            sid, prev = stack.pop()
+            if sid in out:
+                continue
+            a = out[sid] = anns[sid]
+            kids = children.get(sid, [])
+            if prev is not None:  # 1. the skew handed down by the parent
+                cls._shift(a, *prev)
+            count = [0] * 8
+            for x in a:
+                count[x.kind] += 1
+            if max(count[KIND_CS:KIND_SS + 1]) <= 1 and count[KIND_CS] and count[KIND_CR] and \
+                    not (count[KIND_SR] and count[KIND_SS]) and kids:  # 2. a client-only span with children
+                lead = cls._first(anns[kids[0].id], (KIND_CS, KIND_CR))
+                endpoint = None if lead is None else lead.host
+                cs, cr = cls._first(a, (KIND_CS,)), cls._first(a, (KIND_CR,))
+                a.append(Annotation(cs.ts, h_sr, KIND_SR, endpoint))
+                a.append(Annotation(cr.ts, h_ss, KIND_SS, endpoint))
+                for k in kids:
+                    ka = anns[k.id]
+                    kcs, kcr = cls._first(ka, (KIND_CS,)), cls._first(ka, (KIND_CR,))
+                    if kcs is not None and kcr is not None:
+                        sk = cls.skew(cs.ts, cr.ts, kcs.ts, kcr.ts, endpoint)
+                        if sk is not None:
+                            cls._shift(ka, *sk)
+            last = {x.kind: x for x in a if KIND_CS <= x.kind <= KIND_SS}  # 3. the span's own skew
+            own = None
+            if len(last) == 4:
+                own = cls.skew(last[KIND_CS].ts, last[KIND_CR].ts, last[KIND_SR].ts, last[KIND_SS].ts, last[KIND_SR].host)
+                if own is not None:
+                    cls._shift(a, *own)
+            stack.extend((k.id, own) for k in reversed(kids))
+        return trace.with_annotations(out)
+
+
+ADJUSTERS = {"NOTHING": lambda trace: trace, "TIME_SKEW": TimeSkewAdjuster.adjust}
+
+
+def apply_adjusters(trace: Trace, adjust: Sequence[str]) -> Trace:
+    """The adjusters folded over the trace in order, as QueryService folds its own."""
+    for name in adjust:
+        trace = ADJUSTERS[name](trace)
+    return trace
+
+
+class TimelineAnnotation(NamedTuple):
+    """The reference's TimelineAnnotation, flat: the annotation's ts and value (the hash, or the text with
+    a decoder), its host (ipv4, port, and service: the id, or the name with a dictionary), and its span's
+    id, parent and name. Without a host: Endpoint.Unknown's zeros, and "Unknown" for a service name."""
+    ts: int
+    value: Union[int, str]
+    ipv4: int
+    port: int
+    service: Union[int, str]
+    span_id: int
+    parent_id: Optional[int]
+    span_name: Union[int, str, None]
+
+
+class TraceTimeline(NamedTuple):
+    """The reference's TraceTimeline(traceId, rootSpanId, annotations, binaryAnnotations).
+    binary_annotations is always []: the annotation store keeps none (a stated departure)."""
+    trace_id: int
+    root_span_id: int
+    annotations: List[TimelineAnnotation]
+    binary_annotations: list
+
+    @staticmethod
+    def of(trace: Trace, decoder=None, services: Optional[Sequence[str]] = None) -> Optional["TraceTimeline"]:
+        """TraceTimeline.apply: None for a trace without spans; else all annotations of all spans (the spans
+        in span order, each span's list in its order), sorted by ts with a STABLE sort, which is the stated
+        order of equal timestamps. decoder: anything with .string(hash) (a SpanDecoder) turns values into
+        text (a core annotation's is its kind's). services: the service dictionary, by id, as it stands."""
+        if not trace.spans:
+            return None
+        given = trace.annotations or {}
+        out: List[TimelineAnnotation] = []
+        for s in trace.spans:
+            for a in given.get(s.id, ()):
+                value: Union[int, str] = a.value
+                if decoder is not None:
+                    value = KIND_NAMES[a.kind] if a.kind else decoder.string(a.value)
+                if a.host is None:
+                    ipv4, port, svc = 0, 0, (0 if services is None else "Unknown")
+                else:
+                    ipv4, port, svc = a.host.ipv4, a.host.port, a.host.service_id
+                    if services is not None:
+                        if svc >= len(services):
+                            raise ValueError("a service id beyond the services dictionary")
+                        svc = services[svc]
+                out.append(TimelineAnnotation(a.ts, value, ipv4, port, svc, s.id, s.parent, s.name))
+        out.sort(key=lambda t: t.ts)
+        return TraceTimeline(trace.id, trace.getRootMostSpan().id, out, [])
+
+
 class TraceCombo(NamedTuple):
-    """The reference's TraceCombo(trace, traceSummary, traceTimeline, spanDepths). timeline is always None:
-    a record carries no annotation text to lay out."""
+    """The reference's TraceCombo(trace, traceSummary, traceTimeline, spanDepths). timeline is None unless
+    the trace was built with an annotation store's rows: a record carries no annotations to lay out."""
     trace: Trace
     summary: Optional[TraceSummary]
-    timeline: None
+    timeline: Optional[TraceTimeline]
     span_depths: Optional[Dict[int, int]]
 
     @staticmethod
-    def of(trace: Trace) -> "TraceCombo":
-        return TraceCombo(trace, TraceSummary.of(trace), None, trace.toSpanDepths())
+    def of(trace: Trace, timeline: Optional[TraceTimeline] = None) -> "TraceCombo":
+        return TraceCombo(trace, TraceSummary.of(trace), timeline, trace.toSpanDepths())
 
 
 class TraceSpanStore:
@@ -438,9 +644,41 @@ class TraceSpanStore:
         found = self.getSpansByTraceIds([trace_id])
         return found[0] if found else []
 
-    def getTracesByIds(self, ids) -> List[Trace]:
-        """One Trace per asked id that was found, in the order asked."""
-        return [Trace(rows, self.services, self.span_names) for rows in self.getSpansByTraceIds(ids)]
+    @staticmethod
+    def _adjusters(adjust, annotations) -> tuple:
+        """adjust as a tuple of known names; a non-empty one needs an annotation store."""
+        adjust = (adjust,) if isinstance(adjust, str) else tuple(adjust)
+        for name in adjust:
+            if name not in ADJUSTERS:
+                raise ValueError(f"unknown adjuster {name!r}: NOTHING or TIME_SKEW")
+        if adjust and annotations is None:
+            raise ValueError("adjust needs annotations=, a TraceAnnotationStore")
+        return adjust
+
+    def getTracesByIds(self, ids, adjust: Sequence[str] = (), annotations=None) -> List[Trace]:
+        """One Trace per asked id that was found, in the order asked. annotations: a TraceAnnotationStore;
+        every Trace then carries its annotations (Trace's annotations=). adjust: a sequence of "NOTHING" /
+        "TIME_SKEW", folded over each trace in order as QueryService folds its adjusters; it needs
+        annotations=. A trace that has no rows in the annotation store is returned unadjusted."""
+        adjust = self._adjusters(adjust, annotations)
+        found = self.getSpansByTraceIds(ids)
+        if annotations is None:
+            return [Trace(rows, self.services, self.span_names) for rows in found]
+        theirs = annotations.getAnnotationsByTraceIds([rows[0][0] for rows in found])
+        out = []
+        for rows, a in zip(found, theirs):
+            t = Trace(rows, self.services, self.span_names, annotations=a)
+            out.append(apply_adjusters(t, adjust) if a else t)
+        return out
+
+    def getTraceTimelinesByIds(self, ids, adjust: Sequence[str] = (), annotations=None, decoder=None) -> List[TraceTimeline]:
+        """QueryService.getTraceTimelinesByIds: the timeline of every asked trace that was found, in the
+        order asked, after the adjusters. annotations=, a TraceAnnotationStore, is required. decoder: turns
+        the values into text (TraceTimeline.of); service names come from the store's services dictionary."""
+        if annotations is None:
+            raise ValueError("timelines need annotations=, a TraceAnnotationStore")
+        lines = (TraceTimeline.of(t, decoder, self.services) for t in self.getTracesByIds(ids, adjust, annotations))
+        return [t for t in lines if t is not None]
 
     def summaries(self, ids):
         """(heads, entries) for at most ZK_SP_MAX_IDS ids (zk_sp_summaries): heads, a SUMMARY_HEAD array in
@@ -557,23 +795,36 @@ class TraceSpanStore:
             out.append(TraceCombo(Trace.of_merged(merged[at:to], root, depths), summary, None, depths))
             at = to
 
-    def getTraceCombosByIds(self, ids, on_device: bool = False) -> List[TraceCombo]:
-        """QueryService.getTraceCombosByIds: one TraceCombo (the trace, its summary, no timeline, its span
+    def _host_only(self, on_device: bool, adjust, annotations) -> bool:
+        """Whether a call goes the host's way: always with an annotation store (the adjusters and the
+        timeline are built on the host). on_device together with TIME_SKEW is refused, not ignored."""
+        adjust = self._adjusters(adjust, annotations)
+        if on_device and "TIME_SKEW" in adjust:
+            raise ValueError("TIME_SKEW is adjusted on the host: on_device=True cannot be combined with it")
+        return annotations is not None or not on_device
+
+    def getTraceCombosByIds(self, ids, on_device: bool = False, adjust: Sequence[str] = (), annotations=None) -> List[TraceCombo]:
+        """QueryService.getTraceCombosByIds: one TraceCombo (the trace, its summary, its timeline, its span
         depths) per asked id that was found, in the order asked; summary is None for a trace without a timed
         fragment. on_device: spans, summary and depths are merged on the device (zk_sp_traces) and no
-        fragment crosses to the host; the answer is the same."""
-        if on_device:
+        fragment crosses to the host; the answer is the same. adjust, annotations: as for getTracesByIds;
+        with an annotation store the host path is used and timeline is filled, without one it is None."""
+        if not self._host_only(on_device, adjust, annotations):
             return self._combos_on_device(ids)
-        return [TraceCombo.of(t) for t in self.getTracesByIds(ids)]
+        traces = self.getTracesByIds(ids, adjust, annotations)
+        if annotations is None:
+            return [TraceCombo.of(t) for t in traces]
+        return [TraceCombo.of(t, TraceTimeline.of(t, None, self.services)) for t in traces]
 
-    def getTraceSummariesByIds(self, ids, on_device: bool = False) -> List[TraceSummary]:
+    def getTraceSummariesByIds(self, ids, on_device: bool = False, adjust: Sequence[str] = (), annotations=None) -> List[TraceSummary]:
         """QueryService.getTraceSummariesByIds: the summaries in the order asked; ids that are not found
         and traces without a timed fragment (TraceSummary.apply yields None) are left out. on_device:
         the summaries are merged on the device (zk_sp_summaries) and only they cross to the host; the
-        answer is the same."""
-        if on_device:
+        answer is the same. adjust, annotations: as for getTracesByIds; with an annotation store the host
+        path is used."""
+        if not self._host_only(on_device, adjust, annotations):
             return self._summaries_on_device(ids)
-        return [s for s in (TraceSummary.of(t) for t in self.getTracesByIds(ids)) if s is not None]
+        return [s for s in (TraceSummary.of(t) for t in self.getTracesByIds(ids, adjust, annotations)) if s is not None]
 
     # ---- timing ----------------------------------------------------------------------------------------
     def observe_ms(self) -> dict:
