@@ -44,8 +44,27 @@
  *    nothing.
  *  - A refused allocation is ZK_ERR_CAPACITY and leaves the handle exactly as it was: nothing is freed
  *    before its replacement is complete.
- *  - No expiry yet. A trace's end equals the maximum ts of its rows, so the span store's rule can later be
- *    applied from this store's own entries.
+ *
+ * Expiry (zk_an_expire; the span store's rule, zkspans.h "Expiry", applied from this store's own rows)
+ *  - A trace goes or stays WHOLE. end(trace) = the maximum ts over all the trace's rows in the whole
+ *    store, over all segments. Every row is timed: there is no untimed case here. A trace survives exactly
+ *    when end(trace) >= cutoff(trace); end == cutoff stays.
+ *  - A trace whose rows all have ts == INT64_MIN has end = INT64_MIN: it goes at any cutoff above INT64_MIN.
+ *  - cutoff(trace) = min_end, unless the call carries a pin for the trace id: then the pin's own min_end,
+ *    which may be lower or higher than the default.
+ *  - min_end == INT64_MIN with no pins removes nothing and rewrites nothing (segments, bytes and
+ *    allocations stay); INT64_MAX keeps only the traces whose end is INT64_MAX.
+ *  - After a call the store is indistinguishable, through zk_an_gather and zk_an_info's entries, from a
+ *    fresh store that observed only the surviving rows. The cut is made once: a later observe of older
+ *    rows enters the store again.
+ *  - INVARIANT: a zk_sp (zkspans.h) and this store fed from the same zk_ingest_spans_annotated batches
+ *    (every record into the one, every row into the other) and cut with the same min_end and the same pins
+ *    hold the same traces: the ids with rows here are exactly the span store's surviving traces that have a
+ *    timed fragment with at least one annotation. The decoder's last_ts of a record is the maximum ts of
+ *    its annotations, and a record is timed exactly when it has annotations, so both stores compute the
+ *    same end for such a trace.
+ *  - Legal as before: trace ids 0 and 2^64 - 1, ts at the int64 bounds, a trace of any length spread over
+ *    any number of segments.
  *
  * Conventions are those of zkspans.h: every entry point returns zk_status; a handle is not thread-safe; all
  * device work of a handle is ordered on one HIP stream; nothing is allocated before the first observe. Every
@@ -70,6 +89,8 @@ extern "C" {
 #define ZK_AN_MAX_IDS 4096u
 /* bytes of one row */
 #define ZK_AN_ROW_BYTES 44u
+/* the most pins one zk_an_expire carries */
+#define ZK_AN_MAX_PINS 4096u
 
 /* zk_an_cols.bits */
 #define ZK_AN_KIND_MASK  7u
@@ -83,9 +104,10 @@ extern "C" {
 
 typedef struct zk_an_config {
     int32_t  device;   /* HIP device ordinal */
-    uint32_t timing;   /* 1: record HIP events (zk_an_observe_ms, zk_an_query_ms) */
+    uint32_t timing;   /* 1: record HIP events (zk_an_observe_ms, zk_an_query_ms, zk_an_expire_ms) */
     void*    stream;   /* hipStream_t to run on, or NULL for a private stream */
-    uint32_t reserved[8];
+    uint32_t expire_chunk; /* zk_an_expire: entries per range of buckets at most; 0: the default, 2^24 */
+    uint32_t reserved[7];
 } zk_an_config;
 
 /* seven parallel columns: zk_an_observe's input (host or device), zk_an_gather's output (host) */
@@ -111,7 +133,8 @@ const char* zk_an_last_error(const zk_an* an);
    4096-bin histogram; the call synchronises once, to read the counts it sizes the segment by (a merge, see
    Layout, synchronises once more). The scatter of the seven columns (44 B read and 44 B written per row,
    trace_id read once more) is queued on the handle's stream behind that: DEVICE columns must stay as they
-   are until the handle's next synchronising call (zk_an_info, zk_an_gather, zk_an_compact, zk_an_observe).
+   are until the handle's next synchronising call (zk_an_info, zk_an_gather, zk_an_compact, zk_an_expire,
+   zk_an_observe).
    A row whose place falls outside its bucket's slice (it cannot while the columns stay as they were) is
    dropped, never written elsewhere. n == 0 is ZK_OK; n >= 2^32 is ZK_ERR_UNSUPPORTED. */
 zk_status   zk_an_observe(zk_an* an, const zk_an_cols* in, uint64_t n, uint32_t flags);
@@ -149,6 +172,44 @@ zk_status   zk_an_observe_ms(zk_an* an, double out[3]);
 /* Time in ms on the handle's stream of the last zk_an_gather that ran a pass, from its first pass to its
    last copy (the host's prefix sum included, the host's sort not). Needs zk_an_config.timing. */
 zk_status   zk_an_query_ms(zk_an* an, double* ms);
+
+/* Expire whole traces by their end (see Expiry).
+     min_end       the default cutoff.
+     pin_ids, pin_min_end   n_pins HOST entries: trace pin_ids[i] is judged by pin_min_end[i]. n_pins == 0
+                   allows NULL arrays; n_pins > 0 with a NULL array, more than ZK_AN_MAX_PINS, or an id
+                   given twice, is ZK_ERR_INVALID_ARG and changes nothing. A pin for an id that is not in
+                   the store is ignored.
+     removed       the entries (rows) removed.
+   An empty store, and min_end == INT64_MIN without pins, are ZK_OK with *removed = 0 and no device pass:
+   nothing is reallocated or freed, and a handle that never opened a device answers without one.
+   A trace's rows share one bucket but may lie in every segment, so its end is folded over the store
+   before a row is judged. The 4096 buckets are cut into consecutive RANGES of at most
+   zk_an_config.expire_chunk entries over all segments (one bucket above that is a range of its own); a
+   range is one contiguous slice of every segment. Per range a scratch table {key, end} (16 B per slot;
+   slots a power of two >= 2 x the range's entries and >= 1024; trace id 0 apart, in a slot behind the
+   table; home slot = zk_mix64(trace_id ^ ZK_SP_END_SALT) & (slots - 1), apart from the bucket salt: a
+   range of buckets shares the bucket hash's high bits) is cleared, then
+     k_an_end_fold   reads trace_id and ts of the range's slices (16 B per entry; there is no flags column
+                     to read): claims the key, folds the end with a 64-bit atomic max; a wave folds the
+                     runs of equal ids among its 64 entries first, one table update each;
+     k_an_end_pins   keeps, beside the table, the verdict of every pinned id it finds there, and replaces
+                     the id's end by all ones, which sends the mark pass to the verdicts;
+     k_an_end_mark   reads trace_id again (8 B per entry), probes, writes one bit per entry (a wave's ballot
+                     as one 64-bit word) and adds the survivors per (segment, bucket).
+   The scratch is bounded by the range, not by the store; the marks take entries / 8 bytes. One copy of
+   the survivor counts and ONE synchronisation follow. Segments where nothing goes are untouched and not
+   read again; segments where everything goes are freed; the survivors of all other segments are written
+   (k_an_expire_rewrite: the mark bits, and the seven columns of survivors only), grouped by bucket, into
+   ONE new segment that takes the first of their places: the segment count never grows. When nothing goes
+   nothing is rewritten, reallocated or freed. A refused allocation is ZK_ERR_CAPACITY and leaves the
+   handle exactly as it was: nothing is freed or swapped in before every replacement is complete.
+   Synchronises. */
+zk_status   zk_an_expire(zk_an* an, int64_t min_end, const uint64_t* pin_ids, const int64_t* pin_min_end,
+                         uint32_t n_pins, uint64_t* removed);
+/* Device time in ms of the last zk_an_expire that ran a pass: the end-table passes of all ranges, the
+   sizing step (the counts' copy and the synchronisation), the rewrite. Needs zk_an_config.timing; an error
+   without it, or before an expiry that ran a pass. */
+zk_status   zk_an_expire_ms(zk_an* an, double out[3]);
 
 #ifdef __cplusplus
 }

@@ -445,6 +445,7 @@ ZK_AN_BUCKETS = 4096
 ZK_AN_MAX_SEGMENTS = 64
 ZK_AN_MAX_IDS = 4096
 ZK_AN_ROW_BYTES = 44
+ZK_AN_MAX_PINS = 4096
 ZK_AN_KIND_MASK = 7
 ZK_AN_KIND_OTHER, ZK_AN_KIND_CS, ZK_AN_KIND_CR, ZK_AN_KIND_SR, ZK_AN_KIND_SS = 0, 1, 2, 3, 4
 ZK_AN_HAS_HOST = 8
@@ -456,7 +457,8 @@ class zk_an_config(C.Structure):
         ("device", C.c_int32),
         ("timing", C.c_uint32),
         ("stream", C.c_void_p),
-        ("reserved", C.c_uint32 * 8),
+        ("expire_chunk", C.c_uint32),
+        ("reserved", C.c_uint32 * 7),
     ]
 
 
@@ -766,6 +768,8 @@ _SIGNATURES = [
     ("zk_an_gather", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _U32P, C.POINTER(zk_an_cols), C.c_uint64, _U64P]),
     ("zk_an_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_an_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zk_an_expire", C.c_int, [_P, C.c_int64, _P, _P, C.c_uint32, _U64P]),
+    ("zk_an_expire_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
 ]
 
 SYMBOLS = [s[0] for s in _SIGNATURES]

@@ -10,7 +10,7 @@ the timeline over them are in spanstore.py.
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, NamedTuple, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -134,13 +134,15 @@ class TraceAnnotationStore:
     device: the first observe that carries rows opens it."""
 
     OBSERVE_PHASES = ("count", "size", "scatter")
+    EXPIRE_PHASES = ("ends", "size", "rewrite")
 
-    def __init__(self, device: int = 0, timing: bool = False, stream: Optional[int] = None):
+    def __init__(self, device: int = 0, timing: bool = False, stream: Optional[int] = None, expire_chunk: int = 0):
         self._L = _abi.lib()
         cfg = _abi.zk_an_config()
         cfg.device = device
         cfg.timing = 1 if timing else 0
         cfg.stream = stream
+        cfg.expire_chunk = expire_chunk  # expire's entries per range of buckets at most (0: 2^24)
         h = C.c_void_p()
         st = self._L.zk_an_create(C.byref(cfg), C.byref(h))
         if st != _abi.ZK_OK:
@@ -174,7 +176,7 @@ class TraceAnnotationStore:
         """Add a batch's rows (AnnotationRows or DeviceAnnotationRows, any order) as one segment
         (zk_an_observe). Observing a batch again adds it again. sync=False leaves the scatter queued on the
         handle's stream: device columns must then stay as they are until the next call that synchronises
-        (info, gather, compact, observe)."""
+        (info, gather, compact, expire, observe)."""
         flags = 0
         ab = rows.abi()
         if isinstance(rows, DeviceAnnotationRows):
@@ -193,6 +195,21 @@ class TraceAnnotationStore:
     def compact(self) -> None:
         """Merge all segments into one (zk_an_compact)."""
         self._check(self._L.zk_an_compact(self._h))
+
+    def expire(self, min_end: int, pins: Optional[Dict[int, int]] = None) -> int:
+        """Remove every trace whose end (the maximum ts of its rows) is below its cutoff, whole
+        (zk_an_expire): the cutoff is min_end, or pins[trace_id] for a pinned trace. The rows removed. More
+        than ZK_AN_MAX_PINS pins are refused: a second call would judge the first call's pinned traces by
+        the default."""
+        pins = {} if pins is None else dict(pins)
+        if len(pins) > _abi.ZK_AN_MAX_PINS:
+            raise ValueError("more than ZK_AN_MAX_PINS pins in one expiry")
+        ids = np.array([int(k) & _M64 for k in pins], np.uint64)
+        cuts = np.array([int(v) for v in pins.values()], np.int64)
+        removed = C.c_uint64()
+        self._check(self._L.zk_an_expire(self._h, int(min_end), ids.ctypes.data if len(ids) else None,
+                                         cuts.ctypes.data if len(ids) else None, len(ids), C.byref(removed)))
+        return int(removed.value)
 
     def info(self) -> dict:
         """{"entries", "segments", "bytes"} (zk_an_info); synchronises."""
@@ -255,6 +272,12 @@ class TraceAnnotationStore:
         out = (C.c_double * len(self.OBSERVE_PHASES))()
         self._check(self._L.zk_an_observe_ms(self._h, out))
         return dict(zip(self.OBSERVE_PHASES, out))
+
+    def expire_ms(self) -> dict:
+        """Device time (ms) of the passes of the last expire that ran one (zk_an_expire_ms; timing=True)."""
+        out = (C.c_double * len(self.EXPIRE_PHASES))()
+        self._check(self._L.zk_an_expire_ms(self._h, out))
+        return dict(zip(self.EXPIRE_PHASES, out))
 
     def query_ms(self) -> float:
         """Time (ms) on the handle's stream of the last gather (zk_an_query_ms; timing=True)."""

@@ -20,11 +20,17 @@
 //                 the slice) walks the trace_id slice of the id's bucket; the write pass appends a wave's
 //                 matching rows behind the asked id's offset with one returning atomic per wave. Nothing of
 //                 a trace is held in LDS: a trace may be of any length.
+//   k_an_end_fold, k_an_end_pins, k_an_end_mark, k_an_expire_rewrite   zk_an_expire's passes: per range of
+//                 buckets a scratch table {trace id, end} is folded from trace_id and ts (16 B per entry), the
+//                 pinned ids get their verdicts, every entry gets one mark bit and the survivors are counted
+//                 per (segment, bucket); then the survivors of the mixed segments are scattered, as
+//                 k_an_scatter does, into one new segment.
 //
 // Every store is bounded: the scatter and the merge drop a place outside the bucket's slice of the segment
 // they write (it cannot arise while the columns stay as they were between the count and the scatter, which
 // the header asks of the caller), the lookups clamp a slice to its segment and drop a row at or past its
-// asked id's count or the output's size.
+// asked id's count or the output's size, and the expiry's probes stay inside their table (at most `slots`
+// steps), its mark words inside the segment's and its rewrite inside the new segment's slices.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -54,10 +60,19 @@ constexpr uint32_t kAnPart = 4096;            // the lookups: a slice longer tha
 constexpr uint32_t kAnMaxParts = 64;
 constexpr uint64_t kAnMaxFindGrid = 1ull << 20;
 constexpr unsigned long long kAnSalt = ZK_SP_SALT;   // the span store's bucket function, on purpose
+constexpr unsigned long long kAnEndSalt = ZK_SP_END_SALT;  // the expiry's scratch table: apart from the bucket salt
+constexpr unsigned long long kAnSign = 1ull << 63;   // ts ^ sign: the unsigned order is the signed one
+constexpr unsigned long long kAnNone = ~0ull;
+constexpr uint64_t kAnExpireChunk = 1ull << 24;      // zk_an_config.expire_chunk's default
+constexpr uint64_t kAnEndMinSlots = 1024;
+constexpr uint32_t kAnEndGrid = 4096;                // the end-table passes: workgroups per segment at most
+constexpr uint32_t kAnMaxItems = 4096;               // the rewrite's work items at most, plus one per segment
 
 static_assert(kAnBins == 4096 && ZK_AN_BUCKETS == ZK_SP_BUCKETS, "the bucket is the span store's: the hash's 12 highest bits");
 static_assert(ZK_AN_ROW_BYTES == 4 * 8 + 3 * 4, "a row's seven columns");
 static_assert(sizeof(zk_an_cols) == 56 && sizeof(zk_an_config) == 48, "the ABI's layouts");
+static_assert(kAnEndSalt != kAnSalt, "a range's ids share the bucket hash's high bits");
+static_assert(kAnScatterPerWG % kAnWG == 0 && kAnWG % 64 == 0, "a wave's 64 entries share a mark word");
 
 __host__ __device__ inline uint32_t an_bucket(unsigned long long id) { return (uint32_t)(zk_mix64(id ^ kAnSalt) >> 52); }
 
@@ -85,6 +100,18 @@ constexpr size_t kQBytes = kQSegsAt + ZK_AN_MAX_SEGMENTS * sizeof(AnCols);
 // the observe's block: the counts, then the cursors
 constexpr size_t kObsCursorAt = kAnBins * 4;
 constexpr size_t kObsBytes = 2 * kAnBins * 4;
+// the expiry's block: the segments (80 B each), the survivors [segment][bucket], the new segment's
+// cursors, the full-table counter, the pins (ids ascending, cuts, verdicts), the rewrite's work items
+constexpr size_t kXSegsAt = 0;
+constexpr size_t kXSurvAt = kXSegsAt + ZK_AN_MAX_SEGMENTS * 80;
+constexpr size_t kXCursorAt = kXSurvAt + (size_t)ZK_AN_MAX_SEGMENTS * kAnBins * 4;
+constexpr size_t kXFullAt = kXCursorAt + kAnBins * 4;
+constexpr size_t kXPinIdsAt = kXFullAt + 256;
+constexpr size_t kXPinCutsAt = kXPinIdsAt + ZK_AN_MAX_PINS * 8;
+constexpr size_t kXVerdictAt = kXPinCutsAt + ZK_AN_MAX_PINS * 8;
+constexpr size_t kXItemsAt = kXVerdictAt + ZK_AN_MAX_PINS * 4;
+constexpr size_t kXBytes = kXItemsAt + (size_t)(kAnMaxItems + ZK_AN_MAX_SEGMENTS) * 8;
+static_assert(kXSurvAt % 256 == 0 && kXPinIdsAt % 256 == 0 && kXItemsAt % 8 == 0, "the expiry block's alignment");
 
 uint32_t an_grid(uint64_t items, uint32_t cap = kAnMaxGrid) {
     const uint64_t g = (items + kAnWG - 1) / kAnWG;
@@ -256,6 +283,215 @@ __global__ __launch_bounds__(kAnWG) void k_an_find_write(const AnCols* __restric
     }
 }
 
+// ---- expiry --------------------------------------------------------------------------------------------
+// A segment as the expiry's passes see it: its columns and where its mark words begin.
+struct AnXSeg {
+    AnCols c;
+    unsigned long long mark_at;
+};
+struct AnItem {
+    uint32_t seg, chunk;
+};
+static_assert(sizeof(AnXSeg) == 80 && sizeof(AnItem) == 8, "the expiry plan's layouts");
+
+__device__ inline unsigned long long an_end_home(unsigned long long id, unsigned long long slots) {
+    return zk_mix64(id ^ kAnEndSalt) & (slots - 1ull);
+}
+
+// [*lo, *hi): the slice of buckets [b0, b1) (b0 < b1 <= kAnBins) in the segment, clamped to it
+__device__ inline void an_range(const AnCols& sg, uint32_t b0, uint32_t b1, unsigned long long* lo, unsigned long long* hi) {
+    unsigned long long a = sg.off[b0], e = sg.off[b1];
+    if (e > sg.n) e = sg.n;
+    if (a > e) a = e;
+    *lo = a;
+    *hi = e;
+}
+
+// The slot of `id` in the scratch table (slots a power of two; tab[2 * s] the key, tab[2 * s + 1] the end;
+// trace id 0 has the slot behind the table, its key held as 1), or kAnNone when it is not there. A probe
+// ends at an empty slot or after `slots` steps.
+__device__ inline unsigned long long an_end_find(const unsigned long long* tab, unsigned long long slots, unsigned long long id) {
+    if (id == 0ull) return tab[2 * slots] != 0ull ? slots : kAnNone;
+    unsigned long long s = an_end_home(id, slots);
+    for (unsigned long long tries = 0; tries < slots; ++tries) {
+        const unsigned long long k = tab[2 * s];
+        if (k == id) return s;
+        if (k == 0ull) return kAnNone;
+        s = (s + 1ull) & (slots - 1ull);
+    }
+    return kAnNone;
+}
+
+// end[trace] = max over the entries of the range's slices of ts ^ sign (every row is timed; the table is
+// cleared to zeros, the key of INT64_MIN). grid.y = the segment. A wave owns rows of 64 consecutive entries
+// and folds each RUN of equal trace ids in a row first (a segmented max over the lanes, log2 steps): only
+// a run's first lane goes to the table. One span's annotations are adjacent in a batch and the scatter
+// keeps a batch's neighbours neighbours inside a bucket's slice, so runs are the common case. The plain
+// loads are hints: a key never changes once claimed and an end only rises, so a stale word costs an atomic,
+// never an answer. A table that ran full (it cannot at load <= 1/2) is counted in *full. The rows' bounds
+// are wave-uniform, so every lane reaches the shuffles.
+__global__ __launch_bounds__(kAnWG) void k_an_end_fold(const AnXSeg* __restrict__ segs, uint32_t b0, uint32_t b1,
+                                                       unsigned long long* tab, unsigned long long slots,
+                                                       unsigned long long* __restrict__ full) {
+    const AnCols sg = segs[blockIdx.y].c;
+    unsigned long long lo, hi;
+    an_range(sg, b0, b1, &lo, &hi);
+    const unsigned long long stride = (unsigned long long)gridDim.x * kAnWG;
+    const uint32_t lane = lane_id();
+    for (unsigned long long base = lo + (unsigned long long)blockIdx.x * kAnWG + (threadIdx.x - lane); base < hi; base += stride) {
+        const unsigned long long i = base + lane;
+        const bool valid = i < hi;
+        const unsigned long long id = valid ? sg.tid[i] : 0ull;
+        unsigned long long val = valid ? (unsigned long long)sg.ts[i] ^ kAnSign : 0ull;
+        // (an invalid lane has val 0, the floor: whichever run takes it in changes nothing)
+        const unsigned long long prev = __shfl_up(id, 1);
+        const bool head = valid && (lane == 0 || prev != id);
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned long long oid = __shfl_down(id, off), oval = __shfl_down(val, off);
+            if (lane + off < 64 && oid == id && oval > val) val = oval;
+        }
+        if (!head) continue;
+        const unsigned long long want = id ? id : 1ull;
+        unsigned long long s = id ? an_end_home(id, slots) : slots, tries = 0;
+        for (; tries < slots; ++tries) {
+            unsigned long long* p = tab + 2 * s;
+            unsigned long long k = p[0];
+            if (k == 0ull) {
+                k = atomicCAS(p, 0ull, want);
+                if (k == 0ull) k = want;
+            }
+            if (k == want) {
+                if (p[1] < val) atomicMax(p + 1, val);
+                break;
+            }
+            s = (s + 1ull) & (slots - 1ull);
+        }
+        if (tries == slots) atomicAdd(full, 1ull);
+    }
+}
+
+// One thread per pin (ids ascending): a pinned id of this range that is in the table gets its verdict,
+// 1 = goes, 2 = stays (0: never met), and its end becomes all ones, which sends the mark pass to the
+// verdicts. A pin's id lies in one bucket, so in one range: a verdict is written once.
+__global__ __launch_bounds__(kAnWG) void k_an_end_pins(const unsigned long long* __restrict__ ids,
+                                                       const unsigned long long* __restrict__ cuts, uint32_t n, uint32_t b0,
+                                                       uint32_t b1, unsigned long long* tab, unsigned long long slots,
+                                                       uint32_t* __restrict__ verdict) {
+    const uint32_t p = blockIdx.x * kAnWG + threadIdx.x;
+    if (p >= n) return;
+    const unsigned long long id = ids[p];
+    const uint32_t b = an_bucket(id);
+    if (b < b0 || b >= b1) return;
+    const unsigned long long s = an_end_find(tab, slots, id);
+    if (s == kAnNone) return;
+    verdict[p] = tab[2 * s + 1] >= cuts[p] ? 2u : 1u;
+    tab[2 * s + 1] = kAnNone;
+}
+
+// Entry i of the range's slice of segment blockIdx.y survives when its trace's end is >= cut, or by its
+// pin's verdict. A wave owns the 64 entries of one mark word (the slice's edges inside a word are masked
+// out, and words of different ranges are ORed: the ranges run one after another), writes its ballot with
+// one atomic and adds its survivors to surv[segment][bucket], the lanes of one bucket at once. All bounds
+// of the loop are wave-uniform, so every lane reaches the ballots.
+__global__ __launch_bounds__(kAnWG) void k_an_end_mark(const AnXSeg* __restrict__ segs, uint32_t b0, uint32_t b1,
+                                                       const unsigned long long* __restrict__ tab, unsigned long long slots,
+                                                       unsigned long long cut, const unsigned long long* __restrict__ pin_ids,
+                                                       const uint32_t* __restrict__ verdict, uint32_t n_pins,
+                                                       unsigned long long* __restrict__ marks, uint32_t* __restrict__ surv) {
+    const AnXSeg xs = segs[blockIdx.y];
+    const AnCols sg = xs.c;
+    unsigned long long lo, hi;
+    an_range(sg, b0, b1, &lo, &hi);
+    if (lo >= hi) return;
+    const unsigned long long w_hi = (hi + 63ull) >> 6, wstride = (unsigned long long)gridDim.x * (kAnWG / 64);
+    for (unsigned long long w = (lo >> 6) + (unsigned long long)blockIdx.x * (kAnWG / 64) + (threadIdx.x >> 6); w < w_hi; w += wstride) {
+        const unsigned long long i = (w << 6) + lane_id();
+        bool alive = false;
+        uint32_t b = 0;
+        if (i >= lo && i < hi) {
+            const unsigned long long id = sg.tid[i];
+            b = an_bucket(id);
+            const unsigned long long s = b >= b0 && b < b1 ? an_end_find(tab, slots, id) : kAnNone;
+            if (s != kAnNone) {
+                const unsigned long long e = tab[2 * s + 1];
+                alive = e >= cut;
+                if (e == kAnNone && n_pins) {  // a pinned trace, or an end at INT64_MAX (which stays at any cut)
+                    uint32_t a = 0, z = n_pins;
+                    while (a < z) {
+                        const uint32_t mid = (a + z) >> 1;
+                        if (pin_ids[mid] < id) a = mid + 1; else z = mid;
+                    }
+                    if (a < n_pins && pin_ids[a] == id && verdict[a]) alive = verdict[a] == 2u;
+                }
+            }
+        }
+        const unsigned long long m = __ballot(alive);
+        if (!m) continue;  // (wave-uniform)
+        if ((int)lane_id() == __ffsll((long long)m) - 1) atomicOr(&marks[xs.mark_at + w], m);  // (i < hi <= n: a word of this segment)
+        bool todo = alive;
+        for (;;) {  // every turn settles at least one lane
+            const unsigned long long mm = __ballot(todo);
+            if (!mm) break;
+            const int lead = __ffsll((long long)mm) - 1;
+            const uint32_t lb = __shfl(b, lead);
+            const unsigned long long same = __ballot(todo && b == lb);
+            if ((int)lane_id() == lead) atomicAdd(&surv[(size_t)blockIdx.y * kAnBins + lb], (uint32_t)__popcll(same));  // (lb < kAnBins)
+            if (b == lb) todo = false;
+        }
+    }
+}
+
+// k_an_scatter over a stretch of an old segment, for the marked entries only: the mark bits are read for
+// every entry, trace_id (twice) and the other six columns for survivors. cursor[b] starts at the new
+// segment's off[b]; a place at or past off[b + 1] is dropped.
+__global__ __launch_bounds__(kAnWG) void k_an_expire_rewrite(const AnXSeg* __restrict__ segs, const AnItem* __restrict__ items,
+                                                             unsigned long long chunk, const unsigned long long* __restrict__ marks,
+                                                             uint32_t* __restrict__ cursor, AnCols out) {
+    __shared__ uint32_t s_cnt[kAnBins];
+    __shared__ uint32_t s_base[kAnBins];
+    const AnItem it = items[blockIdx.x];
+    const AnXSeg xs = segs[it.seg];
+    const AnCols in = xs.c;
+    const unsigned long long lo = (unsigned long long)it.chunk * chunk;  // (a multiple of the workgroup: a wave's 64 entries share a mark word)
+    if (lo >= in.n) return;  // (the same for the whole workgroup)
+    const unsigned long long hi = lo + chunk < in.n ? lo + chunk : in.n;
+    for (uint32_t b = threadIdx.x; b < kAnBins; b += kAnWG) s_cnt[b] = 0u;
+    __syncthreads();
+    for (unsigned long long base = lo; base < hi; base += kAnWG) {
+        const unsigned long long i = base + threadIdx.x;
+        const bool keep = i < hi && ((marks[xs.mark_at + (i >> 6)] >> (i & 63ull)) & 1ull);
+        const unsigned long long t = keep ? in.tid[i] : 0ull;
+        hist_add(s_cnt, keep, an_bucket(t));
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < kAnBins; b += kAnWG) {
+        const uint32_t c = s_cnt[b];
+        s_base[b] = c ? atomicAdd(&cursor[b], c) : 0u;
+        s_cnt[b] = 0u;
+    }
+    __syncthreads();
+    for (unsigned long long base = lo; base < hi; base += kAnWG) {
+        const unsigned long long i = base + threadIdx.x;
+        const bool keep = i < hi && ((marks[xs.mark_at + (i >> 6)] >> (i & 63ull)) & 1ull);
+        const unsigned long long t = keep ? in.tid[i] : 0ull;
+        const uint32_t b = an_bucket(t);
+        const uint32_t rank = hist_rank(s_cnt, keep, b);
+        if (keep) {
+            const unsigned long long at = (unsigned long long)s_base[b] + rank;
+            if (at < (unsigned long long)out.off[b + 1] && at < out.n) {
+                out.tid[at] = t;
+                out.span[at] = in.span[i];
+                out.ts[at] = in.ts[i];
+                out.val[at] = in.val[i];
+                out.ip[at] = in.ip[i];
+                out.svc[at] = in.svc[i];
+                out.bits[at] = in.bits[i];
+            }
+        }
+    }
+}
+
 size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 
 // seven columns of n entries in one block, each 256-B aligned; with_off: off[4097] behind them
@@ -308,7 +544,14 @@ struct zk_an {
     std::vector<uint8_t> rows_host;
     hipEvent_t oev[4] = {};  // around the passes of the last observe (zk_an_observe_ms)
     hipEvent_t qev[2] = {};  // around the last lookup (zk_an_query_ms)
-    bool otimed = false, qtimed = false;
+    hipEvent_t xev[4] = {};  // around the passes of the last expiry (zk_an_expire_ms)
+    bool otimed = false, qtimed = false, xtimed = false;
+    uint64_t expire_chunk = 0;  // entries per range of buckets at most
+    void* xplan = nullptr;      // the expiry's block (kXBytes)
+    std::vector<AnXSeg> xsegs_host;
+    std::vector<AnItem> xitems_host;
+    std::vector<uint32_t> xsurv_host, xcursor_host, xoff_host;
+    std::vector<unsigned long long> xpin_ids_host, xpin_cuts_host;
     std::string err;
 };
 
@@ -474,6 +717,178 @@ zk_status find_count(zk_an* h, const uint64_t* ids, uint32_t n, uint32_t flags, 
     return ZK_OK;
 }
 
+// a range of buckets [b0, b1) and its entries over all segments
+struct AnRange {
+    uint32_t b0, b1;
+    uint64_t entries;
+};
+
+// zk_an_expire behind its argument checks (a store with segments; the pins ascending by id, their cuts
+// as keys, in the handle's vectors). Per range of buckets the end table's three passes, then the one
+// synchronisation that sizes the rest, then the segments sorted into untouched (no entry goes: not read
+// again), gone (every entry goes: freed) and mixed (their survivors rewritten into ONE new segment, which
+// takes the place of the first of them). Nothing is freed and no bookkeeping changes before the new
+// segment is complete; anything refused leaves the store as it was. The table and the marks are scratch
+// of this call.
+zk_status expire(zk_an* h, unsigned long long cut, uint64_t* removed_out, void** table, void** marks) {
+    const uint32_t G = (uint32_t)h->segs.size(), P = (uint32_t)h->xpin_ids_host.size();
+    // the ranges: consecutive buckets while their entries over all segments stay inside the chunk
+    std::vector<AnRange> ranges;
+    uint64_t most = 0;
+    for (uint32_t b = 0; b < kAnBins; ++b) {
+        uint64_t c = 0;
+        for (const Segment& sg : h->segs) c += sg.off[b + 1] - sg.off[b];
+        if (ranges.empty() || (ranges.back().entries && ranges.back().entries + c > h->expire_chunk))
+            ranges.push_back(AnRange{b, b + 1, c});
+        else {
+            ranges.back().b1 = b + 1;
+            ranges.back().entries += c;
+        }
+        most = std::max(most, ranges.back().entries);
+    }
+    const auto slots_for = [](uint64_t entries) {
+        uint64_t s = kAnEndMinSlots;
+        while (s < 2 * entries) s <<= 1;
+        return s;
+    };
+    zk_status st;
+    if (!h->xplan && (st = alloc(h, &h->xplan, kXBytes, "the expiry's block")) != ZK_OK) return st;
+    if ((st = alloc(h, table, (size_t)(slots_for(most) + 1) * 16, "the expiry's end table (16 B per slot)")) != ZK_OK) return st;
+    h->xsegs_host.clear();
+    uint64_t words = 0;
+    for (const Segment& sg : h->segs) {
+        h->xsegs_host.push_back(AnXSeg{sg.cols(), (unsigned long long)words});
+        words += (sg.n + 63) / 64;
+    }
+    if ((st = alloc(h, marks, (size_t)words * 8, "the expiry's marks (1 bit per entry)")) != ZK_OK) return st;
+    uint8_t* xp = (uint8_t*)h->xplan;
+    const AnXSeg* segs = (const AnXSeg*)(xp + kXSegsAt);
+    uint32_t* surv = (uint32_t*)(xp + kXSurvAt);
+    uint32_t* cursor = (uint32_t*)(xp + kXCursorAt);
+    unsigned long long* full = (unsigned long long*)(xp + kXFullAt);
+    const unsigned long long* pin_ids = (const unsigned long long*)(xp + kXPinIdsAt);
+    const unsigned long long* pin_cuts = (const unsigned long long*)(xp + kXPinCutsAt);
+    uint32_t* verdict = (uint32_t*)(xp + kXVerdictAt);
+    const AnItem* items = (const AnItem*)(xp + kXItemsAt);
+    unsigned long long* tab = (unsigned long long*)*table;
+    unsigned long long* mk = (unsigned long long*)*marks;
+    const bool timing = h->timing;
+    for (hipEvent_t& e : h->xev)
+        if (timing && !e) AN_HIP(h, hipEventCreate(&e));
+    AN_HIP(h, hipMemcpyAsync(xp + kXSegsAt, h->xsegs_host.data(), G * sizeof(AnXSeg), hipMemcpyHostToDevice, h->stream));
+    AN_HIP(h, hipMemsetAsync(surv, 0, (size_t)G * kAnBins * 4, h->stream));
+    AN_HIP(h, hipMemsetAsync(full, 0, 8, h->stream));
+    AN_HIP(h, hipMemsetAsync(mk, 0, (size_t)words * 8, h->stream));
+    if (P) {
+        AN_HIP(h, hipMemcpyAsync(xp + kXPinIdsAt, h->xpin_ids_host.data(), (size_t)P * 8, hipMemcpyHostToDevice, h->stream));
+        AN_HIP(h, hipMemcpyAsync(xp + kXPinCutsAt, h->xpin_cuts_host.data(), (size_t)P * 8, hipMemcpyHostToDevice, h->stream));
+        AN_HIP(h, hipMemsetAsync(verdict, 0, (size_t)P * 4, h->stream));
+    }
+    if (timing) AN_HIP(h, hipEventRecord(h->xev[0], h->stream));
+    for (const AnRange& r : ranges) {
+        if (!r.entries) continue;
+        const uint64_t slots = slots_for(r.entries);
+        uint64_t longest = 0;  // the range's longest slice in one segment sizes the grid's x
+        for (const Segment& sg : h->segs) longest = std::max<uint64_t>(longest, sg.off[r.b1] - sg.off[r.b0]);
+        const dim3 grid(an_grid(longest, kAnEndGrid), G);
+        AN_HIP(h, hipMemsetAsync(tab, 0, (size_t)(slots + 1) * 16, h->stream));
+        AN_HIP(h, launch_checked("k_an_end_fold", k_an_end_fold, grid, dim3(kAnWG), 0, h->stream, segs, r.b0, r.b1, tab,
+                                 (unsigned long long)slots, full));
+        if (P)
+            AN_HIP(h, launch_checked("k_an_end_pins", k_an_end_pins, dim3(an_grid(P)), dim3(kAnWG), 0, h->stream, pin_ids, pin_cuts, P,
+                                     r.b0, r.b1, tab, (unsigned long long)slots, verdict));
+        AN_HIP(h, launch_checked("k_an_end_mark", k_an_end_mark, grid, dim3(kAnWG), 0, h->stream, segs, r.b0, r.b1,
+                                 (const unsigned long long*)tab, (unsigned long long)slots, cut, pin_ids, (const uint32_t*)verdict, P, mk,
+                                 surv));
+    }
+    if (timing) AN_HIP(h, hipEventRecord(h->xev[1], h->stream));
+    h->xsurv_host.resize((size_t)G * kAnBins);
+    unsigned long long ran_full = 0;
+    AN_HIP(h, hipMemcpyAsync(h->xsurv_host.data(), surv, (size_t)G * kAnBins * 4, hipMemcpyDeviceToHost, h->stream));
+    AN_HIP(h, hipMemcpyAsync(&ran_full, full, 8, hipMemcpyDeviceToHost, h->stream));
+    AN_HIP(h, hipStreamSynchronize(h->stream));  // the sizing synchronisation
+    if (ran_full) return afail(h, ZK_ERR_HIP, "the expiry's end table ran full (the sizing rule was broken)");
+    std::vector<uint64_t> keep(G, 0);
+    std::vector<uint32_t> mixed;
+    uint64_t removed = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        const Segment& sg = h->segs[g];
+        for (uint32_t b = 0; b < kAnBins; ++b) {
+            const uint64_t c = h->xsurv_host[(size_t)g * kAnBins + b];
+            if (c > (uint64_t)(sg.off[b + 1] - sg.off[b])) return afail(h, ZK_ERR_HIP, "the expiry counted more survivors than a slice holds");
+            keep[g] += c;
+        }
+        removed += sg.n - keep[g];
+        if (keep[g] != 0 && keep[g] != sg.n) mixed.push_back(g);
+    }
+    if (removed == 0) {  // nothing goes: nothing is rewritten, reallocated or freed
+        if (timing) AN_HIP(h, hipEventRecord(h->xev[2], h->stream));
+        if (timing) AN_HIP(h, hipEventRecord(h->xev[3], h->stream));
+        h->xtimed = timing;
+        return ZK_OK;
+    }
+    Segment m;
+    uint64_t chunk = kAnScatterPerWG;
+    if (!mixed.empty()) {
+        m.off.assign(kAnBins + 1, 0);
+        for (uint32_t b = 0; b < kAnBins; ++b) {
+            uint64_t c = 0;
+            for (uint32_t g : mixed) c += h->xsurv_host[(size_t)g * kAnBins + b];
+            m.off[b + 1] = (uint32_t)(m.off[b] + c);  // (below the store's entries, which fit)
+        }
+        m.n = m.off[kAnBins];
+        m.bytes = Segment::bytes_for(m.n);
+        const auto items_at = [&](uint64_t c) {
+            uint64_t w = 0;
+            for (uint32_t g : mixed) w += (h->segs[g].n + c - 1) / c;
+            return w;
+        };
+        while (items_at(chunk) > kAnMaxItems + mixed.size()) chunk *= 2;
+        h->xitems_host.clear();
+        for (uint32_t g : mixed)
+            for (uint64_t c = 0; c * chunk < h->segs[g].n; ++c) h->xitems_host.push_back(AnItem{g, (uint32_t)c});
+        if ((st = alloc(h, &m.block, m.bytes, "the survivors' segment (44 B per entry)")) != ZK_OK) return st;
+        h->xcursor_host.assign(m.off.begin(), m.off.begin() + kAnBins);
+        h->xoff_host = m.off;
+    }
+    hipError_t e = hipSuccess;
+    if (!mixed.empty()) {
+        const AnCols dst = m.cols();
+        e = hipMemcpyAsync(xp + kXItemsAt, h->xitems_host.data(), h->xitems_host.size() * sizeof(AnItem), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(cursor, h->xcursor_host.data(), kAnBins * 4, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dst.off, h->xoff_host.data(), (kAnBins + 1) * 4, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess && timing) e = hipEventRecord(h->xev[2], h->stream);
+        if (e == hipSuccess)
+            e = launch_checked("k_an_expire_rewrite", k_an_expire_rewrite, dim3((uint32_t)h->xitems_host.size()), dim3(kAnWG), 0,
+                               h->stream, segs, items, (unsigned long long)chunk, (const unsigned long long*)mk, cursor, dst);
+    } else if (timing) {
+        e = hipEventRecord(h->xev[2], h->stream);
+    }
+    if (e == hipSuccess && timing) e = hipEventRecord(h->xev[3], h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream);
+        if (m.block) (void)hipFree(m.block);
+        return afail(h, is_refusal(e) ? ZK_ERR_CAPACITY : ZK_ERR_HIP, std::string("rewriting the survivors: ") + launch_error_str(e));
+    }
+    // the new segment is complete: the gone and the mixed segments leave
+    std::vector<Segment> left;
+    for (uint32_t g = 0; g < G; ++g) {
+        Segment& sg = h->segs[g];
+        if (keep[g] == sg.n) {
+            left.push_back(std::move(sg));
+            continue;
+        }
+        (void)hipFree(sg.block);
+        if (!mixed.empty() && g == mixed[0]) left.push_back(std::move(m));
+    }
+    h->segs = std::move(left);
+    h->entries -= removed;
+    h->xtimed = timing;
+    *removed_out = removed;
+    return ZK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -486,6 +901,7 @@ zk_status zk_an_create(const zk_an_config* cfg, zk_an** out) {
     zk_an* h = new zk_an();
     h->device = cfg->device;
     h->timing = cfg->timing != 0;
+    h->expire_chunk = cfg->expire_chunk ? cfg->expire_chunk : kAnExpireChunk;
     h->stream = (hipStream_t)cfg->stream;  // (NULL: a private stream, made with the device's first use)
     *out = h;
     return ZK_OK;
@@ -499,11 +915,13 @@ zk_status zk_an_destroy(zk_an* h) {
         (void)hipSetDevice(h->device);
         if (h->stream) (void)hipStreamSynchronize(h->stream);
         free_segments(h);
-        for (void* p : {h->obs, h->stage, h->mplan, h->q, h->rows})
+        for (void* p : {h->obs, h->stage, h->mplan, h->q, h->rows, h->xplan})
             if (p) (void)hipFree(p);
         for (hipEvent_t e : h->oev)
             if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : h->qev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : h->xev)
             if (e) (void)hipEventDestroy(e);
         if (h->own) (void)hipStreamDestroy(h->own);
     }
@@ -628,6 +1046,55 @@ zk_status zk_an_compact(zk_an* h) {
     if (h->segs.size() < 2) return ZK_OK;
     AN_HIP(h, hipSetDevice(h->device));
     return merge_all(h);
+    ZK_GUARD_END
+}
+
+zk_status zk_an_expire(zk_an* h, int64_t min_end, const uint64_t* pin_ids, const int64_t* pin_min_end, uint32_t n_pins,
+                       uint64_t* removed) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (!removed) return afail(h, ZK_ERR_INVALID_ARG, "null argument");
+    *removed = 0;
+    if (n_pins > ZK_AN_MAX_PINS) return afail(h, ZK_ERR_INVALID_ARG, "more than ZK_AN_MAX_PINS pins");
+    if (n_pins && (!pin_ids || !pin_min_end)) return afail(h, ZK_ERR_INVALID_ARG, "null argument");
+    // the pins ascending by id (the mark pass searches them), their cuts as keys
+    static thread_local std::vector<uint32_t> order;
+    order.resize(n_pins);
+    std::iota(order.begin(), order.end(), 0u);
+    std::sort(order.begin(), order.end(), [pin_ids](uint32_t x, uint32_t y) { return pin_ids[x] < pin_ids[y]; });
+    for (uint32_t i = 1; i < n_pins; ++i)
+        if (pin_ids[order[i - 1]] == pin_ids[order[i]]) return afail(h, ZK_ERR_INVALID_ARG, "a trace id is pinned twice");
+    h->xtimed = false;
+    if (h->segs.empty()) return ZK_OK;  // (a handle that never opened a device answers here)
+    if (min_end == INT64_MIN && n_pins == 0) return ZK_OK;  // every end is >= INT64_MIN
+    h->xpin_ids_host.resize(n_pins);
+    h->xpin_cuts_host.resize(n_pins);
+    for (uint32_t i = 0; i < n_pins; ++i) {
+        h->xpin_ids_host[i] = pin_ids[order[i]];
+        h->xpin_cuts_host[i] = (unsigned long long)pin_min_end[order[i]] ^ kAnSign;
+    }
+    AN_HIP(h, hipSetDevice(h->device));
+    void *table = nullptr, *marks = nullptr;
+    const zk_status st = expire(h, (unsigned long long)min_end ^ kAnSign, removed, &table, &marks);
+    if (table || marks) (void)hipStreamSynchronize(h->stream);
+    if (table) (void)hipFree(table);
+    if (marks) (void)hipFree(marks);
+    return st;
+    ZK_GUARD_END
+}
+
+zk_status zk_an_expire_ms(zk_an* h, double out[3]) {
+    ZK_GUARD_BEGIN
+    if (!h || !out) return ZK_ERR_INVALID_ARG;
+    if (!h->xtimed) return afail(h, ZK_ERR_INVALID_ARG, "no timed expiry has run a pass (zk_an_config.timing)");
+    AN_HIP(h, hipSetDevice(h->device));
+    AN_HIP(h, hipEventSynchronize(h->xev[3]));
+    for (int k = 0; k < 3; ++k) {
+        float ms = 0.f;
+        AN_HIP(h, hipEventElapsedTime(&ms, h->xev[k], h->xev[k + 1]));
+        out[k] = ms;
+    }
+    return ZK_OK;
     ZK_GUARD_END
 }
 

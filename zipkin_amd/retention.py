@@ -10,7 +10,10 @@ three, every (trace_id, ts) the name or annotation index still returns has its t
 index (an entry's ts is at most its trace's end), so sortTraceIds loses none of them.
 
 SpanRetention is the same for the span data (TraceSpanStore): spanTtl, 7 days by default, whole traces by
-their end, and a ttl of its own for a pinned trace (setTimeToLive / getTimeToLive).
+their end, and a ttl of its own for a pinned trace (setTimeToLive / getTimeToLive). Given annotation stores
+(TraceAnnotationStore) as well, it cuts them with the same cutoff and the same pins, after the span stores:
+a trace's end is the same in both (the maximum ts of its annotations is the decoder's last_ts), so stores fed
+from the same decode_annotated batches keep holding the same traces ("Expiry" in include/zkannots.h).
 
 The job drivers are not wired to either: the caller decides when to expire.
 """
@@ -58,13 +61,19 @@ class SpanRetention:
     index returns has its whole trace in the store.
 
     Stated departure: a pin covers the whole trace, fragments observed later included. Cassandra gives
-    later columns spanTtl again and getTimeToLive answers the minimum over the columns."""
+    later columns spanTtl again and getTimeToLive answers the minimum over the columns.
 
-    MAX_PINS = 4096  # ZK_SP_MAX_PINS
+    annotations: None, one TraceAnnotationStore or a list of sharded ones (anything with
+    expire(min_end, pins) -> int). expire(now_us) gives each of them the span stores' cutoff and pins, after
+    the span stores. The pins' bookkeeping (which traces exist, whose pins are dropped) stays with the span
+    stores."""
 
-    def __init__(self, ttl_seconds: int = SPAN_TTL_SECONDS, spans=None):
+    MAX_PINS = 4096  # ZK_SP_MAX_PINS (= ZK_AN_MAX_PINS)
+
+    def __init__(self, ttl_seconds: int = SPAN_TTL_SECONDS, spans=None, annotations=None):
         self.ttl_seconds = _ttl(ttl_seconds)
         self.spans = _handles(spans)
+        self.annotations = _handles(annotations)
         self.pins = {}  # trace id -> ttl in seconds
 
     def _exists(self, trace_id: int) -> bool:
@@ -94,16 +103,22 @@ class SpanRetention:
     def expire(self, now_us: int) -> dict:
         """Apply cutoff(now_us), and now_us - ttl_i for every pin, to every shard: {"cutoff", "spans"}, the
         default cutoff and the entries (fragments) removed, summed over the shards. The pins of traces that
-        no longer exist are dropped afterwards."""
+        no longer exist are dropped afterwards. With annotation stores, every one of them gets the same
+        cutoff and pins after the span stores, and the result gains "annotations", the rows removed, summed
+        over their shards."""
         c = self.cutoff(now_us)
         pins = {t: _cutoff(now_us, ttl) for t, ttl in self.pins.items()}
         removed = sum(int(h.expire(c, pins)) for h in self.spans)
+        rows = sum(int(h.expire(c, pins)) for h in self.annotations)
         ids = list(self.pins)
         alive = set()
         for h in self.spans:
             alive |= set(h.tracesExist(ids)) if ids else set()
         self.pins = {t: ttl for t, ttl in self.pins.items() if t in alive}
-        return {"cutoff": c, "spans": removed}
+        out = {"cutoff": c, "spans": removed}
+        if self.annotations:
+            out["annotations"] = rows
+        return out
 
 
 class IndexRetention:
