@@ -211,6 +211,88 @@ zk_status   zk_an_expire(zk_an* an, int64_t min_end, const uint64_t* pin_ids, co
    without it, or before an expiry that ran a pass. */
 zk_status   zk_an_expire_ms(zk_an* an, double out[3]);
 
+/* ---- time-skew-adjusted trace summaries (the joint call over a zk_an and a zk_sp) ------------------------ */
+
+/* the most annotation rows of a trace that zk_an_adjusted_summaries adjusts on the device; a power of two.
+   How it is chosen: one workgroup holds one trace in the 160 KiB of LDS of a CU. A merged span takes 52 B
+   there and a trace has at most ZK_SP_TRACE_MAX_ROWS = 2048 of them (104 KiB); a row takes 26 B (its span id
+   and ts [8 B], ipv4 and bits [4 B], a 16-bit sort index; value and service_id are read from HBM only to break
+   the ties of the sort). 64 B + 2048 x 52 B + 2048 x 26 B = 159,808 B fits; 4096 rows would not. */
+#define ZK_AN_ADJ_MAX_ROWS 2048u
+/* the plan: a trace of up to this many annotation rows AND merged spans is adjusted by one wave, any other
+   by a workgroup of 256 */
+#define ZK_AN_ADJ_WAVE_ROWS 64u
+/* zk_sp_summary.state of zk_an_adjusted_summaries: the ZK_SP_SUM_* bits, and */
+#define ZK_AN_ADJ_ANNOTATED 8u   /* the trace has rows in the annotation store */
+#define ZK_AN_ADJ_OVERFLOW  16u  /* more than ZK_SP_TRACE_MAX_ROWS fragments, or more than ZK_AN_ADJ_MAX_ROWS
+                                    annotation rows: spans = span_ts = 0 and no entries */
+
+/* getTraceSummariesByIds with Adjust.TimeSkew, on the device: zk_sp_summaries' answer for the traces as the
+   reference's TimeSkewAdjuster leaves them. Only summaries cross to the host. For one asked id, as a function
+   of both stores' multisets alone (DESIGN.md 5l states the rules; zipkin_amd/spanstore.py is their host form):
+     merged spans  the span store's (zk_sp_traces): fragments grouped by span id, the parent of a span from its
+                   first fragment in canonical order with ZK_F_HAS_PARENT, its services ascending.
+     span times    a span that has annotation rows takes first and last from the minimum and maximum ts of its
+                   rows, and is timed even when no fragment of it is; a span without rows keeps its record
+                   times. Rows whose span_id is not a span of the trace are ignored.
+     SPAN ORDER    (first, span_id unsigned), an untimed span as INT64_MAX, computed from THESE times.
+     not annotated a trace without rows in the annotation store is answered exactly as zk_sp_summaries answers
+                   it: nothing is adjusted and nothing pruned.
+     root          the first span in span order without a parent. Without one nothing is shifted and nothing
+                   pruned (the annotation-derived times hold). With one, only the spans whose parent chain
+                   reaches the root stay.
+     the walk      from the root down. A span's list is its rows in CANONICAL ORDER; a shift changes a row's ts
+                   and never the list's order. The children of a span are the spans whose parent is its id,
+                   in the span order from before the walk. At a span, in this order:
+                   1. the skew its parent handed down is taken out of its list;
+                   2. if the list has exactly one cs and one cr, at most one sr and one ss and not both, and
+                      the span has children (a CLIENT-ONLY span): the endpoint is the host of the first cs or
+                      cr in the first child's list (none: no endpoint); every child that has a cs and a cr
+                      (the first of each) gets skew(cs, cr, child cs, child cr) taken out of its list. The
+                      reference also injects sr = cs and ss = cr here; they never move the span's minimum or
+                      maximum and make its own skew 0, so no row is materialised;
+                   3. else, if the list has all of cs, cr, sr, ss (the LAST of each): skew(cs, cr, sr, ss) with
+                      the sr's host as the endpoint is taken out of its list and handed to its children.
+     skew          cd = cr - cs, sd = ss - sr; none when sd > cd or (cs < sr and cr > ss); latency = (cd - sd)
+                   / 2, skew = sr - latency - cs; none when it is 0 or there is no endpoint. The arithmetic is
+                   the JVM's: 64-bit wrap, / 2 truncated toward zero.
+     a shift       of a list by (endpoint, skew): ts -= skew for every row that has a host and whose ipv4 is the
+                   endpoint's, or that is a cs or cr on 127.0.0.1.
+     the answer    the surviving spans, their times taken again from their lists, in span order again.
+   The head and the entries are zk_sp_summaries': start and end are the minimum first and maximum last over
+   the timed spans of the adjusted trace, fragments counts the span store's rows, spans the adjusted trace's
+   spans, span_ts its entries: per timed span, in span order, one (service_id, first, last) per service of
+   the span, ascending. state: ZK_SP_SUM_FOUND, ZK_SP_SUM_TIMED, ZK_AN_ADJ_ANNOTATED, ZK_AN_ADJ_OVERFLOW.
+   An overflowed trace has spans = span_ts = 0 and no entries; fragments, FOUND and ANNOTATED are exact for
+   it, and the caller completes it on the host. An annotated one has start = end = 0 and TIMED clear; one
+   without rows keeps zk_sp_summaries' head (start, end, TIMED, ZK_SP_SUM_OVERFLOW) beside the new bit.
+     an, sp  the two handles, on the same device (else ZK_ERR_INVALID_ARG). Errors go to zk_an_last_error.
+     ids, n, flags   as for zk_sp_summaries; n > ZK_AN_MAX_IDS is ZK_ERR_INVALID_ARG; n == 0 is ZK_OK.
+     heads   n HOST structs in the order asked; a duplicated id is answered as often as asked; an id the span
+             store does not hold gets a head of zeros (whatever the annotation store holds of it).
+     out, cap, n_out   as for zk_sp_summaries: when cap is below the total the call returns ZK_ERR_CAPACITY
+             with *n_out set and the heads written; no entry is written. cap == 0 with NULL columns is the
+             sizing call.
+   NULL handles or arguments are refused before any device is touched. An empty annotation store hands the
+   call to zk_sp_summaries. Otherwise the passes are: zk_sp_traces' on the span store's stream, which leave
+   every asked trace's merged spans and services in its staging and end synchronised; then on THIS handle's
+   stream zk_an_gather's count pass, synchronisation and prefix sum, its write pass into this handle's staging,
+   and k_an_adjust over both stagings on two work lists (a wave or a workgroup per trace, above). In LDS: the
+   span ids sorted once (every span's parent by binary search, and the rank that breaks the span order's
+   ties), the rows sorted by the full canonical key, every span's run of rows by binary search, the span
+   order, the root, the walk LEVEL BY LEVEL (all shifts a span hands to its children happen during its own
+   visit, so the spans of a level are visited at once; a span's level is found as the walk arrives, one
+   round per level), the times again, the span order again, a prefix sum that places the entries. Entries are
+   staged at the trace's row base in the span store's numbering (entries <= fragments). The heads (40 B per
+   id) are copied and the call synchronises; if the entries fit, the staged columns follow in one copy and are
+   packed per trace on the host. zk_an_query_ms covers this handle's passes, zk_sp_query_ms the span store's.
+   A call with n > 0 that ran no k_an_adjust (the annotation store is empty, no asked id is in the span store,
+   or every found trace overflowed) leaves no timed lookup behind: zk_an_query_ms is then an error until the next
+   lookup, never an earlier call's time.
+   Staging is grown on use; a refused allocation is ZK_ERR_CAPACITY. Synchronises. */
+zk_status   zk_an_adjusted_summaries(zk_an* an, zk_sp* sp, const uint64_t* ids, uint32_t n, uint32_t flags,
+                                     zk_sp_summary* heads, zk_sp_span_ts* out, uint64_t cap, uint64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ from .durations import TraceDurationIndex, TraceIdDuration, merge_top  # noqa: F
 from .nameindex import IndexedTraceId, TraceNameIndex, merge_trace_ids  # noqa: F401
 from .annindex import AnnotationItems, DeviceAnnotationItems, TraceAnnotationIndex, get_trace_ids, trace_ids_intersect  # noqa: F401
 from .retention import IndexRetention, SpanRetention  # noqa: F401
-from .annotstore import Annotation, AnnotationRows, DeviceAnnotationRows, Endpoint, TraceAnnotationStore  # noqa: F401
+from .annotstore import ADJ_ANNOTATED, ADJ_OVERFLOW, ADJUSTED_HEAD, Annotation, AnnotationRows, DeviceAnnotationRows, Endpoint, TraceAnnotationStore  # noqa: F401
 from .spanstore import (SUMMARY_HEAD, TRACE_HEAD, TRACE_SPAN, AnnotatedSpan, Span, SpanTimestamp, TimelineAnnotation,  # noqa: F401
                         Timespan, TimeSkewAdjuster, Trace, TraceCombo, TraceSpanStore, TraceSummary, TraceTimeline)
 from .windows import WindowedAggregateJob, WindowPartition  # noqa: F401
@@ -54,6 +54,9 @@ __all__ = [
     "TRACE_SPAN",
     "TraceCombo",
     "TraceAnnotationStore",
+    "ADJUSTED_HEAD",
+    "ADJ_ANNOTATED",
+    "ADJ_OVERFLOW",
     "AnnotationRows",
     "DeviceAnnotationRows",
     "Annotation",

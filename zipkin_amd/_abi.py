@@ -450,6 +450,10 @@ ZK_AN_KIND_MASK = 7
 ZK_AN_KIND_OTHER, ZK_AN_KIND_CS, ZK_AN_KIND_CR, ZK_AN_KIND_SR, ZK_AN_KIND_SS = 0, 1, 2, 3, 4
 ZK_AN_HAS_HOST = 8
 ZK_AN_PORT_SHIFT = 16
+ZK_AN_ADJ_MAX_ROWS = 2048
+ZK_AN_ADJ_WAVE_ROWS = 64
+ZK_AN_ADJ_ANNOTATED = 8
+ZK_AN_ADJ_OVERFLOW = 16
 
 
 class zk_an_config(C.Structure):
@@ -770,6 +774,7 @@ _SIGNATURES = [
     ("zk_an_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_an_expire", C.c_int, [_P, C.c_int64, _P, _P, C.c_uint32, _U64P]),
     ("zk_an_expire_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zk_an_adjusted_summaries", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, C.POINTER(zk_sp_span_ts), C.c_uint64, _U64P]),
 ]
 
 SYMBOLS = [s[0] for s in _SIGNATURES]

@@ -15,6 +15,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi
+from .columns import ENTRY_COLUMNS, SUMMARY_HEAD
 
 _M64 = 2 ** 64 - 1
 
@@ -22,6 +23,10 @@ AnnotationRow = Tuple[int, int, int, int, int, int, int]
 
 ROW_COLUMNS = (("trace_id", np.uint64), ("span_id", np.uint64), ("ts", np.int64), ("value", np.uint64),
                ("ipv4", np.uint32), ("service_id", np.uint32), ("bits", np.uint32))
+
+# zk_an_adjusted_summaries' answer: zk_sp_summary heads with two more state bits, and zk_sp_span_ts entries
+ADJUSTED_HEAD, ADJUSTED_ENTRY_COLUMNS = SUMMARY_HEAD, ENTRY_COLUMNS
+ADJ_ANNOTATED, ADJ_OVERFLOW = _abi.ZK_AN_ADJ_ANNOTATED, _abi.ZK_AN_ADJ_OVERFLOW
 
 KIND_OTHER, KIND_CS, KIND_CR, KIND_SR, KIND_SS = 0, 1, 2, 3, 4
 KIND_NAMES = ("", "cs", "cr", "sr", "ss")
@@ -266,6 +271,26 @@ class TraceAnnotationStore:
                 at += c
         return out
 
+    def adjusted_summaries(self, spans, ids):
+        """(heads, entries) for at most ZK_AN_MAX_IDS ids (zk_an_adjusted_summaries): the trace summaries after
+        the time-skew adjuster, joined on the device from this store's rows and `spans`, a TraceSpanStore on
+        the same device. heads: an ADJUSTED_HEAD array in the order asked (state: ZK_SP_SUM_FOUND / _TIMED,
+        ADJ_ANNOTATED, ADJ_OVERFLOW); entries: the (service_id, first, last) of all asked traces one after
+        another (a dict of three numpy columns of exactly the total). The sizing call, then the call that
+        fills."""
+        keep, ptr, n, flags = self._ask(ids)
+        heads = np.zeros(n, ADJUSTED_HEAD)
+        total = C.c_uint64()
+        st = self._L.zk_an_adjusted_summaries(self._h, spans._h, ptr, n, flags, heads.ctypes.data, None, 0, C.byref(total))
+        if st not in (_abi.ZK_OK, _abi.ZK_ERR_CAPACITY):
+            self._check(st)
+        cols = {k: np.zeros(total.value, dt) for k, dt in ADJUSTED_ENTRY_COLUMNS}
+        if st == _abi.ZK_ERR_CAPACITY:
+            out = _abi.zk_sp_span_ts(*[cols[k].ctypes.data for k, _ in ADJUSTED_ENTRY_COLUMNS])
+            self._check(self._L.zk_an_adjusted_summaries(self._h, spans._h, ptr, n, flags, heads.ctypes.data, C.byref(out),
+                                                         total.value, C.byref(total)))
+        return heads, cols
+
     # ---- timing ----------------------------------------------------------------------------------------
     def observe_ms(self) -> dict:
         """Device time (ms) of the passes of the last observe (zk_an_observe_ms; timing=True)."""
@@ -280,7 +305,8 @@ class TraceAnnotationStore:
         return dict(zip(self.EXPIRE_PHASES, out))
 
     def query_ms(self) -> float:
-        """Time (ms) on the handle's stream of the last gather (zk_an_query_ms; timing=True)."""
+        """Time (ms) on the handle's stream of the last gather or adjusted_summaries (zk_an_query_ms;
+        timing=True)."""
         ms = C.c_double()
         self._check(self._L.zk_an_query_ms(self._h, C.byref(ms)))
         return float(ms.value)

@@ -23,6 +23,12 @@ COLUMNS = (
 )
 BYTES_PER_RECORD = 48
 
+# zk_sp_summary, the 40-byte head of one asked id (zk_sp_summaries, zk_an_adjusted_summaries), and the columns of
+# zk_sp_span_ts, their entries
+SUMMARY_HEAD = np.dtype([("trace_id", np.uint64), ("start", np.int64), ("end", np.int64), ("fragments", np.uint32),
+                         ("spans", np.uint32), ("span_ts", np.uint32), ("state", np.uint32)])
+ENTRY_COLUMNS = (("service_id", np.uint32), ("first", np.int64), ("last", np.int64))
+
 
 @dataclass
 class SpanColumns:

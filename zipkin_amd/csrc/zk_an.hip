@@ -42,6 +42,7 @@
 #include "zk_guard.h"
 #include "zk_hist.h"
 #include "zk_launch.h"
+#include "zk_sp_staged.h"
 #include "zk_tracegen.h"
 #include "zkannots.h"
 
@@ -536,7 +537,11 @@ struct zk_an {
     void* mplan = nullptr;   // a merge's bases, per old segment
     void* q = nullptr;       // the lookups' block (kQBytes)
     void* rows = nullptr;    // the write pass's rows, seven columns
-    size_t stage_bytes = 0, mplan_bytes = 0, rows_bytes = 0;
+    void* adj = nullptr;     // the adjusted summaries' block: the heads, then the work lists (kAdjBytes)
+    void* adj_ents = nullptr;  // their entries at the span store's row bases: first, last [8 B], service [4 B]
+    size_t stage_bytes = 0, mplan_bytes = 0, rows_bytes = 0, adj_ents_bytes = 0;
+    std::vector<uint8_t> adj_traces_host, adj_heads_host, adj_ents_host;
+    std::vector<uint32_t> adj_counts_host, adj_list_host;
     std::vector<uint32_t> counts_host, cursor_host, off_host;  // (queued copies read the last two: they change only behind a synchronisation)
     std::vector<uint32_t> mplan_host, moff_host;
     std::vector<uint64_t> ids_host, base_host;
@@ -915,7 +920,7 @@ zk_status zk_an_destroy(zk_an* h) {
         (void)hipSetDevice(h->device);
         if (h->stream) (void)hipStreamSynchronize(h->stream);
         free_segments(h);
-        for (void* p : {h->obs, h->stage, h->mplan, h->q, h->rows, h->xplan})
+        for (void* p : {h->obs, h->stage, h->mplan, h->q, h->rows, h->xplan, h->adj, h->adj_ents})
             if (p) (void)hipFree(p);
         for (hipEvent_t e : h->oev)
             if (e) (void)hipEventDestroy(e);
@@ -1206,3 +1211,606 @@ zk_status zk_an_query_ms(zk_an* h, double* ms) {
 }
 
 }  // extern "C"
+
+// ---- time-skew-adjusted summaries (zk_an_adjusted_summaries) ----------------------------------------------
+//   k_an_adjust   one asked trace per wave (up to 64 rows and 64 spans) or per workgroup of 256, over BOTH
+//                 stagings: the merged spans and services zk_sp_traces left in the span store's, and the rows
+//                 this handle's write pass staged. 52 B of LDS per span and 26 B per row. The span ids are
+//                 sorted once (in the rows' area, before the rows come in) for every span's parent and for the
+//                 rank that breaks the ties of the span order; the rows are sorted by the full canonical key
+//                 (value and service_id, read only on a tie of span, ts and kind, stay in HBM); every span
+//                 finds its run of rows by binary search and takes its times from it; the spans are sorted
+//                 into span order; the root is the first without a parent; the walk goes level by level, a
+//                 thread per span of the level, and finds a span's level as it arrives (a span whose parent
+//                 was visited in the round before is visited in this one), so no depths are computed ahead;
+//                 then the times again, the span order again over the survivors, a prefix sum that places the
+//                 entries. Every store is bounded: a trace that does not fit the launch's caps or whose
+//                 stagings end before it is left alone (its head stays zero), and an entry at or past the
+//                 trace's (span, service) pairs or the staging's end is dropped.
+namespace zk {
+namespace {
+
+constexpr int kAdjWave = ZK_AN_ADJ_WAVE_ROWS;
+constexpr uint32_t kAdjMaxRows = ZK_AN_ADJ_MAX_ROWS;
+constexpr uint32_t kAdjMaxSpans = ZK_SP_TRACE_MAX_ROWS;
+constexpr uint32_t kAdjNone16 = 0xFFFFu, kAdjNone = 0xFFFFFFFFu;
+constexpr uint32_t kAdjLoopback = 0x7F000001u;
+constexpr uint32_t kAdjHasParent = 1u, kAdjTimed = 2u, kAdjGiveOwn = 4u, kAdjGiveClient = 8u, kAdjGiveEp = 16u;  // a span's bits in LDS
+constexpr size_t kAdjLdsHead = 64;      // the counters [8 x 4 B], start, end [8 B], 16 B unused
+constexpr size_t kAdjLdsPerSpan = 52;   // first, last, give [8 B], gip, bits, fc [4 B], par, run, len, ord, rank, pos, depth, svo [2 B]
+constexpr size_t kAdjLdsPerRow = 26;    // span, ts [8 B], ip, bits [4 B], ord [2 B]
+// the block: the heads, then the work list
+constexpr size_t kAdjListAt = (size_t)ZK_AN_MAX_IDS * sizeof(zk_sp_summary);
+constexpr size_t kAdjBytes = kAdjListAt + (size_t)ZK_AN_MAX_IDS * 4;
+
+static_assert(kAdjWave == 64, "a wave holds one row or span per lane");
+static_assert(kAdjMaxRows >= 1024 && (kAdjMaxRows & (kAdjMaxRows - 1)) == 0 && kAdjMaxRows < kAdjNone16, "16-bit row numbers over a power of two");
+static_assert(kAdjMaxSpans < kAdjNone16 && (kAdjMaxSpans & (kAdjMaxSpans - 1)) == 0, "16-bit span numbers and levels");
+static_assert(ZK_AN_MAX_IDS == ZK_SP_MAX_IDS, "one ask goes to both stores");
+static_assert((ZK_AN_ADJ_ANNOTATED & (ZK_SP_SUM_FOUND | ZK_SP_SUM_TIMED | ZK_SP_SUM_OVERFLOW)) == 0 &&
+                  (ZK_AN_ADJ_OVERFLOW & (ZK_SP_SUM_FOUND | ZK_SP_SUM_TIMED | ZK_SP_SUM_OVERFLOW | ZK_AN_ADJ_ANNOTATED)) == 0,
+              "the new state bits lie beside the ZK_SP_SUM_* ones");
+
+// LDS of one k_an_adjust workgroup whose launch admits `spans` spans and `rows` rows (powers of two >= 64):
+// the rows' area first holds the span ids of the id sort
+constexpr size_t adj_lds(uint32_t spans, uint32_t rows) {
+    return kAdjLdsHead + kAdjLdsPerSpan * spans + (kAdjLdsPerRow * rows > 8 * (size_t)spans ? kAdjLdsPerRow * rows : 8 * (size_t)spans);
+}
+static_assert(adj_lds(kAdjMaxSpans, kAdjMaxRows) <= kLdsPerCU, "a trace at both bounds fits the 160 KiB of a CU");
+
+struct AdjIn {
+    AnCols rows;                            // this handle's staged rows
+    const uint32_t* list;                   // the work list: asked indices
+    const unsigned long long* ids;
+    const uint32_t* counts;                 // the rows per asked id
+    const unsigned long long* base;         // their bases in `rows`
+    const zk_sp_trace* t_heads;             // the span store's staging (zk_sp_staged.h)
+    const zk_sp_span* t_spans;
+    const uint32_t* t_svc;
+    const unsigned long long* t_base;
+    unsigned long long t_total;             // its rows: the bound of t_spans, t_svc and of the entries written
+    uint32_t cap_spans, cap_rows;           // what the launch's LDS admits
+    zk_sp_summary* heads;
+    uint32_t* o_svc;
+    long long* o_first;
+    long long* o_last;
+};
+
+// a bitonic sort of ord[0, P) (P a power of two >= 2, the same for the whole workgroup). Ends behind a barrier.
+template <int T, class Less>
+__device__ inline void adj_sort(uint16_t* ord, uint32_t P, const Less& less) {
+    for (uint32_t k = 2; k <= P; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t w = threadIdx.x; w < P / 2; w += T) {
+                const uint32_t i = ((w & ~(j - 1u)) << 1) | (w & (j - 1u)), x = i | j;
+                const uint16_t a = ord[i], b = ord[x];
+                if ((i & k) == 0 ? less(b, a) : less(a, b)) {
+                    ord[i] = b;
+                    ord[x] = a;
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// the exclusive prefix of `sum` over the workgroup's threads and the total; s_wave: T / 64 words. Every thread calls.
+template <int T>
+__device__ inline uint32_t adj_scan(uint32_t sum, uint32_t* s_wave, uint32_t* total) {
+    uint32_t inc = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(inc, d);
+        if ((int)lane_id() >= d) inc += o;
+    }
+    __syncthreads();
+    if (lane_id() == 63) s_wave[threadIdx.x >> 6] = inc;
+    __syncthreads();
+    uint32_t before = inc - sum, all = 0u;
+    for (uint32_t w = 0; w < (uint32_t)(T / 64); ++w) {
+        if (w < (threadIdx.x >> 6)) before += s_wave[w];
+        all += s_wave[w];
+    }
+    *total = all;
+    return before;
+}
+
+// TimeSkewAdjuster's skew, the JVM's arithmetic (64-bit wrap, / 2 toward zero); false: none
+__device__ inline bool adj_skew(long long cs, long long cr, long long sr, long long ss, unsigned long long* out) {
+    const long long cd = (long long)((unsigned long long)cr - (unsigned long long)cs);
+    const long long sd = (long long)((unsigned long long)ss - (unsigned long long)sr);
+    if (sd > cd || (cs < sr && cr > ss)) return false;
+    const long long lat = (long long)((unsigned long long)cd - (unsigned long long)sd) / 2;
+    const unsigned long long sk = (unsigned long long)sr - (unsigned long long)lat - (unsigned long long)cs;
+    if (sk == 0ull) return false;
+    *out = sk;
+    return true;
+}
+
+template <int T>
+__global__ __launch_bounds__(T) void k_an_adjust(AdjIn in) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_adj[];
+    uint32_t* s_cnt = (uint32_t*)s_adj;  // [0] the root's position, [1] a level's visits, [2] timed, [3] the survivors, [4..7] the scan's waves
+    unsigned long long* s_lo = (unsigned long long*)(s_adj + 32);
+    unsigned long long* s_hi = s_lo + 1;
+    const uint32_t q = in.list[blockIdx.x];
+    const zk_sp_trace th = in.t_heads[q];
+    const uint32_t S = th.spans, A = in.counts[q];
+    const uint32_t cs = in.cap_spans, cr = in.cap_rows;
+    const unsigned long long sb0 = in.t_base[q], ab0 = in.base[q];
+    // (the host lists only traces that fit; anything else is left alone, before any barrier)
+    if (S == 0 || S > cs || S > kAdjMaxSpans || A > cr || A > kAdjMaxRows || sb0 + S > in.t_total ||
+        sb0 + th.services > in.t_total || ab0 + A > in.rows.n)
+        return;
+    unsigned long long* f_first = (unsigned long long*)(s_adj + kAdjLdsHead);
+    unsigned long long* f_last = f_first + cs;
+    unsigned long long* f_give = f_last + cs;   // OWN: the skew; CLIENT: the sorted positions of its cs and cr
+    uint32_t* f_gip = (uint32_t*)(f_give + cs);  // the ipv4 of what it hands down
+    uint32_t* f_bits = f_gip + cs;
+    uint32_t* f_fc = f_bits + cs;                // the first child's position in span order (kAdjNone: no child)
+    uint16_t* f_par = (uint16_t*)(f_fc + cs);
+    uint16_t* f_run = f_par + cs;
+    uint16_t* f_len = f_run + cs;
+    uint16_t* f_ord = f_len + cs;
+    uint16_t* f_rank = f_ord + cs;
+    uint16_t* f_pos = f_rank + cs;
+    uint16_t* f_depth = f_pos + cs;
+    uint16_t* f_svo = f_depth + cs;
+    unsigned char* area = (unsigned char*)(f_svo + cs);
+    unsigned long long* tmp_id = (unsigned long long*)area;
+    unsigned long long* r_span = (unsigned long long*)area;
+    unsigned long long* r_ts = r_span + cr;
+    uint32_t* r_ip = (uint32_t*)(r_ts + cr);
+    uint32_t* r_bits = r_ip + cr;
+    uint16_t* r_ord = (uint16_t*)(r_bits + cr);
+    const zk_sp_span* spans = in.t_spans + sb0;
+    const bool annotated = A > 0u;
+    uint32_t PS = 2, PA = 2;
+    while (PS < S) PS <<= 1;
+    while (PA < A) PA <<= 1;
+    if (threadIdx.x == 0) {
+        s_cnt[0] = kAdjNone;
+        s_cnt[1] = s_cnt[2] = s_cnt[3] = 0u;
+        *s_lo = kAnNone;
+        *s_hi = 0ull;
+    }
+    // 1. the spans: record times, bits; the ids sorted for the parents and the ranks
+    for (uint32_t i = threadIdx.x; i < PS; i += T) f_ord[i] = (uint16_t)i;
+    for (uint32_t i = threadIdx.x; i < S; i += T) {
+        const zk_sp_span sp = spans[i];
+        const bool timed = sp.bits & ZK_SP_SPAN_TIMED;
+        tmp_id[i] = sp.span_id;
+        f_first[i] = timed ? (unsigned long long)sp.first ^ kAnSign : kAnNone;
+        f_last[i] = timed ? (unsigned long long)sp.last ^ kAnSign : 0ull;
+        f_bits[i] = ((sp.bits & ZK_SP_SPAN_HAS_PARENT) ? kAdjHasParent : 0u) | (timed ? kAdjTimed : 0u);
+        f_fc[i] = kAdjNone;
+        f_par[i] = (uint16_t)kAdjNone16;
+        f_run[i] = f_len[i] = f_depth[i] = 0;
+    }
+    __syncthreads();
+    if (annotated) {
+        adj_sort<T>(f_ord, PS, [&](uint32_t a, uint32_t b) {
+            if (b >= S) return a < S;
+            if (a >= S) return false;
+            return tmp_id[a] < tmp_id[b];
+        });
+        for (uint32_t p = threadIdx.x; p < S; p += T) f_rank[f_ord[p]] = (uint16_t)p;
+        for (uint32_t i = threadIdx.x; i < S; i += T) {
+            const zk_sp_span sp = spans[i];
+            if ((sp.bits & ZK_SP_SPAN_HAS_PARENT) && (sp.bits & ZK_SP_SPAN_PARENT_FOUND)) {
+                uint32_t a = 0, z = S;
+                while (a < z) {
+                    const uint32_t mid = (a + z) >> 1;
+                    if (tmp_id[f_ord[mid]] < sp.parent_id) a = mid + 1; else z = mid;
+                }
+                if (a < S && tmp_id[f_ord[a]] == sp.parent_id) f_par[i] = f_ord[a];
+            }
+        }
+    }
+    // every span's place in the services column: the prefix sum of the spans' service counts
+    {
+        const uint32_t C = (S + T - 1) / T, p0 = threadIdx.x * C;
+        uint32_t sum = 0u, all;
+        for (uint32_t p = p0; p < p0 + C && p < S; ++p) sum += spans[p].services;
+        uint32_t before = adj_scan<T>(sum, s_cnt + 4, &all);
+        for (uint32_t p = p0; p < p0 + C && p < S; ++p) {
+            f_svo[p] = (uint16_t)(before < kAdjNone16 ? before : kAdjNone16);
+            before += spans[p].services;
+        }
+    }
+    __syncthreads();  // (tmp_id is read no more: the rows take its place)
+    bool has_root = false;
+    if (annotated) {
+        // 2. the rows, in canonical order
+        for (uint32_t i = threadIdx.x; i < PA; i += T) r_ord[i] = (uint16_t)i;
+        for (uint32_t i = threadIdx.x; i < A; i += T) {
+            r_span[i] = in.rows.span[ab0 + i];
+            r_ts[i] = (unsigned long long)in.rows.ts[ab0 + i] ^ kAnSign;
+            r_ip[i] = in.rows.ip[ab0 + i];
+            r_bits[i] = in.rows.bits[ab0 + i];
+        }
+        __syncthreads();
+        adj_sort<T>(r_ord, PA, [&](uint32_t a, uint32_t b) {
+            if (b >= A) return a < A;
+            if (a >= A) return false;
+            if (r_span[a] != r_span[b]) return r_span[a] < r_span[b];
+            if (r_ts[a] != r_ts[b]) return r_ts[a] < r_ts[b];
+            const uint32_t ba = r_bits[a], bb = r_bits[b];
+            if ((ba & ZK_AN_KIND_MASK) != (bb & ZK_AN_KIND_MASK)) return (ba & ZK_AN_KIND_MASK) < (bb & ZK_AN_KIND_MASK);
+            const unsigned long long va = in.rows.val[ab0 + a], vb = in.rows.val[ab0 + b];
+            if (va != vb) return va < vb;
+            if (r_ip[a] != r_ip[b]) return r_ip[a] < r_ip[b];
+            if ((ba >> ZK_AN_PORT_SHIFT) != (bb >> ZK_AN_PORT_SHIFT)) return (ba >> ZK_AN_PORT_SHIFT) < (bb >> ZK_AN_PORT_SHIFT);
+            const uint32_t sa = in.rows.svc[ab0 + a], sb = in.rows.svc[ab0 + b];
+            if (sa != sb) return sa < sb;
+            if ((ba & ZK_AN_HAS_HOST) != (bb & ZK_AN_HAS_HOST)) return (ba & ZK_AN_HAS_HOST) < (bb & ZK_AN_HAS_HOST);
+            return ba < bb;
+        });
+        // 3. every span's run of rows, and its times from it
+        for (uint32_t i = threadIdx.x; i < S; i += T) {
+            const unsigned long long id = spans[i].span_id;
+            uint32_t a = 0, z = A;
+            while (a < z) {
+                const uint32_t mid = (a + z) >> 1;
+                if (r_span[r_ord[mid]] < id) a = mid + 1; else z = mid;
+            }
+            uint32_t e = a;
+            z = A;
+            while (e < z) {
+                const uint32_t mid = (e + z) >> 1;
+                if (r_span[r_ord[mid]] <= id) e = mid + 1; else z = mid;
+            }
+            f_run[i] = (uint16_t)a;
+            f_len[i] = (uint16_t)(e - a);
+            if (e > a) {
+                f_first[i] = r_ts[r_ord[a]];
+                f_last[i] = r_ts[r_ord[e - 1]];
+                f_bits[i] |= kAdjTimed;
+            }
+        }
+        __syncthreads();
+        // 4. span order from these times; the root; every span's first child
+        adj_sort<T>(f_ord, PS, [&](uint32_t a, uint32_t b) {
+            if (b >= S) return a < S;
+            if (a >= S) return false;
+            if (f_first[a] != f_first[b]) return f_first[a] < f_first[b];
+            return f_rank[a] < f_rank[b];
+        });
+        for (uint32_t p = threadIdx.x; p < S; p += T) {
+            const uint32_t i = f_ord[p];
+            f_pos[i] = (uint16_t)p;
+            if (!(f_bits[i] & kAdjHasParent)) atomicMin(&s_cnt[0], p);
+        }
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < S; i += T)
+            if (f_par[i] != kAdjNone16) atomicMin(&f_fc[f_par[i]], (uint32_t)f_pos[i]);
+        __syncthreads();
+        has_root = s_cnt[0] < S;
+    }
+    if (has_root) {
+        // 5. the walk, a level per round: the root, then every span whose parent was visited the round before
+        const uint32_t root = f_ord[s_cnt[0]];
+        for (uint32_t level = 1; level <= S; ++level) {
+            bool did = false;
+            for (uint32_t i = threadIdx.x; i < S; i += T) {
+                const uint32_t par = f_par[i];
+                if (level == 1 ? i != root : (f_depth[i] != 0 || par == kAdjNone16 || par == i || f_depth[par] != level - 1)) continue;
+                f_depth[i] = (uint16_t)level;
+                did = true;
+                const uint32_t r0 = f_run[i], len = f_len[i];
+                // what the parent hands down: its own skew, or (a client-only parent) this child's own
+                bool shift = false;
+                uint32_t ip = 0u;
+                unsigned long long sk = 0ull;
+                uint32_t n1 = 0, n2 = 0, n3 = 0, n4 = 0, f1 = 0, f2 = 0, l1 = 0, l2 = 0, l3 = 0, l4 = 0;
+                for (uint32_t k = 0; k < len; ++k) {
+                    const uint32_t p = r0 + k, kind = r_bits[r_ord[p]] & ZK_AN_KIND_MASK;
+                    if (kind == ZK_AN_KIND_CS) { if (!n1++) f1 = p; l1 = p; }
+                    else if (kind == ZK_AN_KIND_CR) { if (!n2++) f2 = p; l2 = p; }
+                    else if (kind == ZK_AN_KIND_SR) { ++n3; l3 = p; }
+                    else if (kind == ZK_AN_KIND_SS) { ++n4; l4 = p; }
+                }
+                if (level > 1) {
+                    const uint32_t pb = f_bits[par];
+                    if (pb & kAdjGiveOwn) {
+                        shift = true;
+                        ip = f_gip[par];
+                        sk = f_give[par];
+                    } else if ((pb & kAdjGiveClient) && (pb & kAdjGiveEp) && n1 && n2) {
+                        const uint32_t pcs = (uint32_t)(f_give[par] & 0xFFFFu), pcr = (uint32_t)(f_give[par] >> 16) & 0xFFFFu;
+                        shift = adj_skew((long long)(r_ts[r_ord[pcs]] ^ kAnSign), (long long)(r_ts[r_ord[pcr]] ^ kAnSign),
+                                         (long long)(r_ts[r_ord[f1]] ^ kAnSign), (long long)(r_ts[r_ord[f2]] ^ kAnSign), &sk);
+                        ip = f_gip[par];
+                    }
+                }
+                for (int pass = 0; pass < 2; ++pass) {
+                    if (shift)
+                        for (uint32_t k = 0; k < len; ++k) {
+                            const uint32_t r = r_ord[r0 + k], b = r_bits[r], kind = b & ZK_AN_KIND_MASK;
+                            if ((b & ZK_AN_HAS_HOST) && (r_ip[r] == ip || ((kind == ZK_AN_KIND_CS || kind == ZK_AN_KIND_CR) && r_ip[r] == kAdjLoopback)))
+                                r_ts[r] -= sk;  // (held ^ sign: the difference is the same)
+                        }
+                    if (pass == 1) break;
+                    shift = false;
+                    if (n1 == 1 && n2 == 1 && n3 <= 1 && n4 <= 1 && !(n3 && n4) && f_fc[i] != kAdjNone) {
+                        // client-only: the endpoint is the host of the first cs or cr of the first child's list
+                        const uint32_t kid = f_ord[f_fc[i]];
+                        uint32_t bits = kAdjGiveClient;
+                        for (uint32_t k = 0; k < f_len[kid]; ++k) {
+                            const uint32_t r = r_ord[(uint32_t)f_run[kid] + k], b = r_bits[r], kind = b & ZK_AN_KIND_MASK;
+                            if (kind == ZK_AN_KIND_CS || kind == ZK_AN_KIND_CR) {
+                                if (b & ZK_AN_HAS_HOST) {
+                                    bits |= kAdjGiveEp;
+                                    f_gip[i] = r_ip[r];
+                                }
+                                break;
+                            }
+                        }
+                        f_give[i] = (unsigned long long)f1 | ((unsigned long long)f2 << 16);
+                        f_bits[i] |= bits;
+                    } else if (n1 && n2 && n3 && n4) {
+                        // its own skew, from the last of each kind; the endpoint is the sr's host
+                        const uint32_t rs = r_ord[l3];
+                        if ((r_bits[rs] & ZK_AN_HAS_HOST) &&
+                            adj_skew((long long)(r_ts[r_ord[l1]] ^ kAnSign), (long long)(r_ts[r_ord[l2]] ^ kAnSign),
+                                     (long long)(r_ts[rs] ^ kAnSign), (long long)(r_ts[r_ord[l4]] ^ kAnSign), &sk)) {
+                            shift = true;
+                            ip = r_ip[rs];
+                            f_gip[i] = ip;
+                            f_give[i] = sk;
+                            f_bits[i] |= kAdjGiveOwn;
+                        }
+                    }
+                }
+            }
+            if (did) s_cnt[1] = 1u;
+            __syncthreads();
+            const bool any = s_cnt[1] != 0u;
+            __syncthreads();
+            if (!any) break;  // (the same for the whole workgroup)
+            if (threadIdx.x == 0) s_cnt[1] = 0u;
+            __syncthreads();
+        }
+        // 6. the survivors' times from their lists again
+        for (uint32_t i = threadIdx.x; i < S; i += T) {
+            if (f_depth[i] == 0 || f_len[i] == 0) continue;
+            unsigned long long lo = kAnNone, hi = 0ull;
+            for (uint32_t k = 0; k < f_len[i]; ++k) {
+                const unsigned long long t = r_ts[r_ord[(uint32_t)f_run[i] + k]];
+                lo = t < lo ? t : lo;
+                hi = t > hi ? t : hi;
+            }
+            f_first[i] = lo;
+            f_last[i] = hi;
+        }
+        __syncthreads();
+        // 7. span order again: the survivors, then the pruned spans, then the padding (the first S positions
+        // stay the trace's spans)
+        adj_sort<T>(f_ord, PS, [&](uint32_t a, uint32_t b) {
+            const uint32_t ca = a >= S ? 2u : f_depth[a] == 0 ? 1u : 0u, cb = b >= S ? 2u : f_depth[b] == 0 ? 1u : 0u;
+            if (ca != cb) return ca < cb;
+            if (ca != 0u) return false;
+            if (f_first[a] != f_first[b]) return f_first[a] < f_first[b];
+            return f_rank[a] < f_rank[b];
+        });
+    }
+    // (not annotated: f_ord is still the spans' own order, which zk_sp_traces made)
+    // 8. the head's reductions and the entries' places over the sorted positions, consecutive ones per thread
+    const uint32_t C = (S + T - 1) / T, p0 = threadIdx.x * C;
+    uint32_t sum = 0u, kept = 0u, total = 0u;
+    unsigned long long lo = kAnNone, hi = 0ull;
+    bool timed_any = false;
+    for (uint32_t p = p0; p < p0 + C && p < S; ++p) {
+        const uint32_t i = f_ord[p];
+        if (has_root && f_depth[i] == 0) continue;
+        ++kept;
+        if (f_bits[i] & kAdjTimed) {
+            sum += spans[i].services;
+            lo = f_first[i] < lo ? f_first[i] : lo;
+            hi = f_last[i] > hi ? f_last[i] : hi;
+            timed_any = true;
+        }
+    }
+    if (kept) atomicAdd(&s_cnt[3], kept);
+    if (timed_any) {
+        atomicMin(s_lo, lo);
+        atomicMax(s_hi, hi);
+        atomicOr(&s_cnt[2], 1u);
+    }
+    uint32_t before = adj_scan<T>(sum, s_cnt + 4, &total);
+    for (uint32_t p = p0; p < p0 + C && p < S; ++p) {
+        const uint32_t i = f_ord[p];
+        if ((has_root && f_depth[i] == 0) || !(f_bits[i] & kAdjTimed)) continue;
+        const uint32_t k_n = spans[i].services, at = f_svo[i];
+        for (uint32_t k = 0; k < k_n; ++k) {
+            const unsigned long long e = sb0 + before + k;
+            if (before + k < th.services && at + k < th.services && e < in.t_total) {
+                in.o_svc[e] = in.t_svc[sb0 + at + k];
+                in.o_first[e] = (long long)(f_first[i] ^ kAnSign);
+                in.o_last[e] = (long long)(f_last[i] ^ kAnSign);
+            }
+        }
+        before += k_n;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        zk_sp_summary hd;
+        const bool timed = s_cnt[2] != 0u;
+        hd.trace_id = in.ids[q];
+        hd.start = timed ? (long long)(*s_lo ^ kAnSign) : 0;
+        hd.end = timed ? (long long)(*s_hi ^ kAnSign) : 0;
+        hd.fragments = th.fragments;
+        hd.spans = s_cnt[3];
+        hd.span_ts = total <= th.services ? total : th.services;
+        hd.state = ZK_SP_SUM_FOUND | (timed ? ZK_SP_SUM_TIMED : 0u) | (annotated ? ZK_AN_ADJ_ANNOTATED : 0u);
+        in.heads[q] = hd;
+    }
+}
+
+}  // namespace
+}  // namespace zk
+
+extern "C" zk_status zk_an_adjusted_summaries(zk_an* h, zk_sp* sp, const uint64_t* ids, uint32_t n, uint32_t flags,
+                                              zk_sp_summary* heads, zk_sp_span_ts* out, uint64_t cap, uint64_t* n_out) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (!sp || !n_out) return afail(h, ZK_ERR_INVALID_ARG, "null argument");
+    if (flags & ~ZK_BATCH_DEVICE_PTRS) return afail(h, ZK_ERR_INVALID_ARG, "unknown flag");
+    if (n > ZK_AN_MAX_IDS) return afail(h, ZK_ERR_INVALID_ARG, "more than ZK_AN_MAX_IDS ids");
+    if (n && (!ids || !heads)) return afail(h, ZK_ERR_INVALID_ARG, "null argument");
+    if (cap && (!out || !out->service_id || !out->first || !out->last)) return afail(h, ZK_ERR_INVALID_ARG, "null output column");
+    if (sp_device(sp) != h->device) return afail(h, ZK_ERR_INVALID_ARG, "the two handles are on different devices");
+    *n_out = 0;
+    if (n == 0) return ZK_OK;
+    memset(heads, 0, (size_t)n * sizeof(zk_sp_summary));
+    h->qtimed = false;  // (zk_an_query_ms answers for this call only once k_an_adjust has run)
+    zk_status st;
+    if (h->segs.empty()) {
+        // no trace is annotated: every answer is zk_sp_summaries' own
+        st = zk_sp_summaries(sp, ids, n, flags, heads, out, cap, n_out);
+        if (st != ZK_OK) afail(h, st, zk_sp_last_error(sp));
+        if (st == ZK_OK || st == ZK_ERR_CAPACITY)
+            for (uint32_t i = 0; i < n; ++i)
+                if (heads[i].state & ZK_SP_SUM_OVERFLOW) heads[i].state |= ZK_AN_ADJ_OVERFLOW;
+        return st;
+    }
+    // the span store's part: zk_sp_traces' passes, its sizing call; the merged spans stay in its staging
+    h->adj_traces_host.resize((size_t)n * sizeof(zk_sp_trace));
+    zk_sp_trace* th = (zk_sp_trace*)h->adj_traces_host.data();
+    uint64_t t_out[2] = {0, 0};
+    st = zk_sp_traces(sp, ids, n, flags, th, nullptr, 0, nullptr, 0, t_out);
+    if (st != ZK_OK && st != ZK_ERR_CAPACITY) return afail(h, st, zk_sp_last_error(sp));
+    bool any = false;
+    for (uint32_t i = 0; i < n; ++i) any = any || (th[i].state & ZK_SP_TR_FOUND);
+    if (!any) return ZK_OK;
+    SpStagedTraces sv;
+    sp_staged_traces(sp, &sv);
+    if (!sv.heads || sv.total == 0) return afail(h, ZK_ERR_HIP, "the span store's staging is not there");
+    AN_HIP(h, hipSetDevice(h->device));
+    // this handle's part: the rows of the asked traces into its staging
+    uint32_t parts = 1;
+    h->adj_counts_host.resize(n);
+    uint32_t* counts = h->adj_counts_host.data();
+    if ((st = find_count(h, ids, n, flags, counts, &parts)) != ZK_OK) return st;
+    h->base_host.resize(n);
+    uint64_t rows_total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        h->base_host[i] = rows_total;
+        rows_total += counts[i];
+    }
+    // the overflowed traces are answered here; the others go on the two work lists
+    h->adj_list_host.clear();
+    uint32_t big_spans = kAdjWave, big_rows = kAdjWave;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (uint32_t i = 0; i < n; ++i) {
+            if (!(th[i].state & ZK_SP_TR_FOUND)) continue;
+            const bool over = (th[i].state & ZK_SP_TR_OVERFLOW) || th[i].spans > kAdjMaxSpans || counts[i] > kAdjMaxRows;
+            if (over) {
+                if (pass) continue;
+                zk_sp_summary& hd = heads[i];
+                hd.trace_id = th[i].trace_id;
+                hd.fragments = th[i].fragments;
+                hd.state = ZK_SP_SUM_FOUND | ZK_AN_ADJ_OVERFLOW;
+                if (counts[i]) {
+                    hd.state |= ZK_AN_ADJ_ANNOTATED;
+                } else {  // not annotated: zk_sp_summaries' head of a trace above its bound
+                    hd.start = th[i].start;
+                    hd.end = th[i].end;
+                    hd.state |= ZK_SP_SUM_OVERFLOW | (th[i].state & ZK_SP_TR_TIMED ? ZK_SP_SUM_TIMED : 0u);
+                }
+                continue;
+            }
+            const bool small = counts[i] <= (uint32_t)kAdjWave && th[i].spans <= (uint32_t)kAdjWave;
+            if (small != (pass == 0)) continue;
+            h->adj_list_host.push_back(i);
+            if (!small) {
+                while (big_spans < th[i].spans) big_spans <<= 1;
+                while (big_rows < counts[i]) big_rows <<= 1;
+            }
+        }
+    }
+    uint32_t n_wave = 0;
+    for (uint32_t i : h->adj_list_host)
+        if (counts[i] <= (uint32_t)kAdjWave && th[i].spans <= (uint32_t)kAdjWave) ++n_wave;
+    const uint32_t n_group = (uint32_t)h->adj_list_host.size() - n_wave;
+    if (h->adj_list_host.empty()) return ZK_OK;
+    if (!h->adj && (st = alloc(h, &h->adj, kAdjBytes, "the adjusted summaries' heads and work lists")) != ZK_OK) return st;
+    if ((st = grow(h, &h->rows, &h->rows_bytes, Block::cols_bytes(rows_total), "the gathered rows (44 B each)")) != ZK_OK) return st;
+    const size_t e8 = Block::col8(sv.total);
+    if ((st = grow(h, &h->adj_ents, &h->adj_ents_bytes, 2 * e8 + Block::col4(sv.total), "the adjusted summaries' entries (20 B per fragment)")) != ZK_OK)
+        return st;
+    uint8_t* qb = (uint8_t*)h->q;
+    uint8_t* ab = (uint8_t*)h->adj;
+    const AnCols dev = Block::view(h->rows, rows_total, false);
+    if (rows_total) {
+        AN_HIP(h, hipMemcpyAsync(qb + kQBaseAt, h->base_host.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+        AN_HIP(h, hipMemsetAsync(qb + kQCursorAt, 0, (size_t)n * 4, h->stream));
+        AN_HIP(h, launch_checked("k_an_find_write", k_an_find_write, dim3(n, (uint32_t)h->segs.size(), parts), dim3(kAnWG), 0, h->stream,
+                                 (const AnCols*)(qb + kQSegsAt), (const unsigned long long*)(qb + kQIdsAt),
+                                 (const uint32_t*)(qb + kQCountsAt), (uint32_t*)(qb + kQCursorAt),
+                                 (const unsigned long long*)(qb + kQBaseAt), dev));
+    } else {
+        AN_HIP(h, hipMemcpyAsync(qb + kQBaseAt, h->base_host.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    AN_HIP(h, hipMemcpyAsync(ab + kAdjListAt, h->adj_list_host.data(), h->adj_list_host.size() * 4, hipMemcpyHostToDevice, h->stream));
+    AN_HIP(h, hipMemsetAsync(ab, 0, (size_t)n * sizeof(zk_sp_summary), h->stream));
+    AdjIn in;
+    in.rows = dev;
+    in.list = (const uint32_t*)(ab + kAdjListAt);
+    in.ids = (const unsigned long long*)(qb + kQIdsAt);
+    in.counts = (const uint32_t*)(qb + kQCountsAt);
+    in.base = (const unsigned long long*)(qb + kQBaseAt);
+    in.t_heads = sv.heads;
+    in.t_spans = sv.spans;
+    in.t_svc = sv.services;
+    in.t_base = sv.base;
+    in.t_total = sv.total;
+    in.cap_spans = in.cap_rows = (uint32_t)kAdjWave;
+    in.heads = (zk_sp_summary*)ab;
+    in.o_first = (long long*)h->adj_ents;
+    in.o_last = (long long*)((uint8_t*)h->adj_ents + e8);
+    in.o_svc = (uint32_t*)((uint8_t*)h->adj_ents + 2 * e8);
+    AN_HIP(h, launch_checked("k_an_adjust (a wave per trace)", k_an_adjust<kAdjWave>, dim3(n_wave), dim3(kAdjWave),
+                             adj_lds(kAdjWave, kAdjWave), h->stream, in));
+    in.list += n_wave;
+    in.cap_spans = big_spans;
+    in.cap_rows = big_rows;
+    AN_HIP(h, launch_checked("k_an_adjust (a workgroup per trace)", k_an_adjust<kAnWG>, dim3(n_group), dim3(kAnWG),
+                             adj_lds(big_spans, big_rows), h->stream, in));
+    // only the heads cross before the entries' total is known
+    h->adj_heads_host.resize((size_t)n * sizeof(zk_sp_summary));
+    const zk_sp_summary* got = (const zk_sp_summary*)h->adj_heads_host.data();
+    AN_HIP(h, hipMemcpyAsync(h->adj_heads_host.data(), ab, (size_t)n * sizeof(zk_sp_summary), hipMemcpyDeviceToHost, h->stream));
+    if (h->timing) AN_HIP(h, hipEventRecord(h->qev[1], h->stream));
+    AN_HIP(h, hipStreamSynchronize(h->stream));
+    h->qtimed = h->timing;
+    uint64_t need = 0;
+    for (uint32_t i : h->adj_list_host) {
+        if (!(got[i].state & ZK_SP_SUM_FOUND)) return afail(h, ZK_ERR_HIP, "a listed trace was not adjusted");
+        if (got[i].span_ts > th[i].fragments) return afail(h, ZK_ERR_HIP, "an adjusted summary has more entries than its trace has fragments");
+        heads[i] = got[i];
+        need += got[i].span_ts;
+    }
+    *n_out = need;
+    if (need > cap) return afail(h, ZK_ERR_CAPACITY, "the output columns hold fewer entries than the asked traces have");
+    if (need == 0) return ZK_OK;
+    // the staged entry columns in one copy, then each trace's entries packed behind the ones before it
+    const size_t bytes = 2 * e8 + (size_t)sv.total * 4;
+    h->adj_ents_host.resize(bytes);
+    AN_HIP(h, hipMemcpyAsync(h->adj_ents_host.data(), h->adj_ents, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (h->timing) AN_HIP(h, hipEventRecord(h->qev[1], h->stream));
+    AN_HIP(h, hipStreamSynchronize(h->stream));
+    const int64_t* s_first = (const int64_t*)h->adj_ents_host.data();
+    const int64_t* s_last = (const int64_t*)(h->adj_ents_host.data() + e8);
+    const uint32_t* s_svc = (const uint32_t*)(h->adj_ents_host.data() + 2 * e8);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t c = heads[i].span_ts, from = sv.base_host[i];
+        if (!c) continue;
+        memcpy(out->service_id + at, s_svc + from, c * 4);
+        memcpy(out->first + at, s_first + from, c * 8);
+        memcpy(out->last + at, s_last + from, c * 8);
+        at += c;
+    }
+    return ZK_OK;
+    ZK_GUARD_END
+}

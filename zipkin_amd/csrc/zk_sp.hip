@@ -56,6 +56,7 @@
 #include "zk_guard.h"
 #include "zk_hist.h"
 #include "zk_launch.h"
+#include "zk_sp_staged.h"
 #include "zk_tracegen.h"
 #include "zkspans.h"
 
@@ -2073,3 +2074,26 @@ zk_status zk_sp_query_ms(zk_sp* h, double* ms) {
 }
 
 }  // extern "C"
+
+// ---- the staging, for the joint kernels (zk_sp_staged.h) -------------------------------------------------
+namespace zk {
+
+int sp_device(const zk_sp* h) { return h->device; }
+
+// zk_sp_traces' staging as it stands: the layout is that call's (the spans, then the services 256-B aligned
+// behind them, both at the traces' row bases).
+void sp_staged_traces(const zk_sp* h, SpStagedTraces* out) {
+    *out = SpStagedTraces();
+    out->device = h->device;
+    if (!h->q || !h->tr_heads || !h->tr_out || h->base_host.empty() || h->base_host.size() != h->sum_counts_host.size()) return;
+    const uint64_t total = h->base_host.back() + h->sum_counts_host.back();
+    if (total == 0 || al256((size_t)total * sizeof(zk_sp_span)) + Block::col4(total) > h->tr_bytes) return;
+    out->heads = (const zk_sp_trace*)h->tr_heads;
+    out->spans = (const zk_sp_span*)h->tr_out;
+    out->services = (const uint32_t*)((const uint8_t*)h->tr_out + al256((size_t)total * sizeof(zk_sp_span)));
+    out->base = (const unsigned long long*)((const uint8_t*)h->q + kQBaseAt);
+    out->base_host = h->base_host.data();
+    out->total = total;
+}
+
+}  // namespace zk

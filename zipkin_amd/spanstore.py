@@ -26,17 +26,13 @@ import numpy as np
 from . import _abi
 from .annotstore import (KIND_CR, KIND_CS, KIND_NAMES, KIND_SR, KIND_SS, LOOPBACK_IPV4, Annotation, AnnotationRow, Endpoint,
                          annotation_key)
-from .columns import COLUMNS, DeviceColumns
+from .columns import COLUMNS, ENTRY_COLUMNS, SUMMARY_HEAD, DeviceColumns  # noqa: F401  (zk_sp_summary's head and entries)
 
 INT64_MIN, INT64_MAX = -(2 ** 63), 2 ** 63 - 1
 _M64 = 2 ** 64 - 1
 
 Row = Tuple[int, int, int, int, int, int, int]
 
-# zk_sp_summary, the 40-byte head of one asked id
-SUMMARY_HEAD = np.dtype([("trace_id", np.uint64), ("start", np.int64), ("end", np.int64), ("fragments", np.uint32),
-                         ("spans", np.uint32), ("span_ts", np.uint32), ("state", np.uint32)])
-ENTRY_COLUMNS = (("service_id", np.uint32), ("first", np.int64), ("last", np.int64))
 # zk_sp_trace, the 48-byte head of one asked id, and zk_sp_span, one merged span (48 bytes)
 TRACE_HEAD = np.dtype([("trace_id", np.uint64), ("start", np.int64), ("end", np.int64), ("root_most", np.uint64),
                        ("fragments", np.uint32), ("spans", np.uint32), ("services", np.uint32), ("state", np.uint32)])
@@ -816,12 +812,55 @@ class TraceSpanStore:
             return [TraceCombo.of(t) for t in traces]
         return [TraceCombo.of(t, TraceTimeline.of(t, None, self.services)) for t in traces]
 
-    def getTraceSummariesByIds(self, ids, on_device: bool = False, adjust: Sequence[str] = (), annotations=None) -> List[TraceSummary]:
+    def _summaries_adjusted_on_device(self, ids, annotations) -> List[TraceSummary]:
+        """getTraceSummariesByIds(adjust=("TIME_SKEW",), annotations=) from annotations.adjusted_summaries():
+        _summaries_on_device's loop over zk_an_adjusted_summaries' answer; a trace above the device's bounds
+        goes the host's way. The cyclic collector is paused while the tuples are built, as in _combos_on_device."""
+        out: List[TraceSummary] = []
+        paused = gc.isenabled()
+        gc.disable()
+        try:
+            for a in range(0, len(ids), _abi.ZK_AN_MAX_IDS):
+                self._adjusted_of(out, annotations, *annotations.adjusted_summaries(self, ids[a:a + _abi.ZK_AN_MAX_IDS]))
+        finally:
+            if paused:
+                gc.enable()
+        return out
+
+    def _adjusted_of(self, out: List[TraceSummary], annotations, heads, cols) -> None:
+        """The TraceSummaries of one adjusted_summaries() answer, appended to out."""
+        low = None if self.services is None else [s.lower() for s in self.services]
+        svc, first, last = (cols[k].tolist() for k, _ in ENTRY_COLUMNS)
+        if low is not None:
+            if svc and max(svc) >= len(low):
+                raise ValueError("a service id beyond the services dictionary")
+            svc = [low[i] for i in svc]
+        entries = list(map(SpanTimestamp, svc, first, last))
+        at = 0
+        for tid, start, end, _, _, c, state in heads.tolist():
+            if state & _abi.ZK_AN_ADJ_OVERFLOW:
+                out += self.getTraceSummariesByIds([tid], adjust=("TIME_SKEW",), annotations=annotations)
+            elif state & _abi.ZK_SP_SUM_TIMED:
+                out.append(TraceSummary(tid, start, end, _to_int(_wrap64(end - start)), entries[at:at + c], []))
+            at += c
+
+    def getTraceSummariesByIds(self, ids, on_device: bool = False, adjust: Sequence[str] = (), annotations=None,
+                               adjust_on_device: bool = False) -> List[TraceSummary]:
         """QueryService.getTraceSummariesByIds: the summaries in the order asked; ids that are not found
         and traces without a timed fragment (TraceSummary.apply yields None) are left out. on_device:
         the summaries are merged on the device (zk_sp_summaries) and only they cross to the host; the
         answer is the same. adjust, annotations: as for getTracesByIds; with an annotation store the host
-        path is used."""
+        path is used, unless adjust_on_device: then the adjuster runs on the device too
+        (zk_an_adjusted_summaries) and only the adjusted summaries cross; the answer is the same. It needs
+        annotations= and "TIME_SKEW" as the only adjuster besides "NOTHING", once; anything else is a
+        ValueError."""
+        if adjust_on_device:
+            adjust = self._adjusters(adjust, annotations)
+            if on_device:
+                raise ValueError("adjust_on_device=True replaces on_device=True: give one of them")
+            if [name for name in adjust if name != "NOTHING"] != ["TIME_SKEW"] or annotations is None:
+                raise ValueError('adjust_on_device=True needs annotations= and adjust=("TIME_SKEW",), applied once')
+            return self._summaries_adjusted_on_device(np.ascontiguousarray(np.asarray(ids, dtype=np.uint64)), annotations)
         if not self._host_only(on_device, adjust, annotations):
             return self._summaries_on_device(ids)
         return [s for s in (TraceSummary.of(t) for t in self.getTracesByIds(ids, adjust, annotations)) if s is not None]
