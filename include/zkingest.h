@@ -66,6 +66,8 @@ extern "C" {
                                       ids are NOT the host decoder's: see zk_ingest_dev_create_names. */
 #define ZK_INGEST_NO_CLIENT_RULE 8u /* zk_ingest_spans_indexed: emit the entries of a client-side span of the
                                       service called "client" too (shouldIndex off) */
+#define ZK_INGEST_NO_ROW_STRINGS 16u /* zk_ingest_dev_spans_annotated: do not capture the rows' value strings
+                                      (the rows are the same; zk_ingest_dev_string is untouched by them) */
 /* Both decoders (host zk_ingest_spans, device zk_ingest_dev_spans) reject a Snappy fragment whose
  * header announces more than ZK_INGEST_MAX_FRAGMENT bytes, or more than the format can expand its
  * payload to (a 3-byte copy emits at most 64 bytes: < ZK_SNAPPY_MAX_EXPANSION x), before any
@@ -130,8 +132,9 @@ typedef struct zk_ingest_index_items {
 zk_status zk_ingest_spans_indexed(zk_ingest* ing, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
                                   uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
                                   zk_ingest_index_items* ix);
-/* caller buffers for the rows of the annotation store (zkannots.h): seven parallel HOST columns, laid out
- * as zk_an_cols, then their capacity and count */
+/* caller buffers for the rows of the annotation store (zkannots.h): seven parallel columns (HOST memory for
+ * zk_ingest_spans_annotated, DEVICE memory for zk_ingest_dev_spans_annotated), laid out as zk_an_cols, then
+ * their capacity and count */
 typedef struct zk_ingest_annotation_rows {
     uint64_t* trace_id;
     uint64_t* span_id;
@@ -162,7 +165,7 @@ typedef struct zk_ingest_annotation_rows {
  *     their outputs are what they were.)
  *   - an->cap too small: ZK_ERR_CAPACITY; the records and the first cap rows are written and an->n = cap.
  *   - an and its seven columns must not be NULL (ZK_ERR_INVALID_ARG).
- * The device decoder does not emit these rows. */
+ * The device decoder emits the same rows into device columns: zk_ingest_dev_spans_annotated. */
 zk_status zk_ingest_spans_annotated(zk_ingest* ing, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
                                     uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
                                     zk_ingest_items* items, zk_ingest_annotation_rows* an);
@@ -269,7 +272,55 @@ zk_status   zk_ingest_dev_spans_multi_indexed(zk_ingest_dev* ing, uint32_t nb, c
 /* the last index pass of this decoder: the device time between its first and last launch (ms), and the
    slices it ran in (0 / 0 before the first indexed call) */
 zk_status   zk_ingest_dev_index_stats(const zk_ingest_dev* ing, double* pass_ms, uint64_t* slices);
-/* the string behind a key / value hash an items batch of this decoder has seen (two-phase) */
+/* zk_ingest_dev_spans(_items) / zk_ingest_dev_spans_multi that also write the annotation store's rows
+ * (zkannots.h) to the seven DEVICE columns of `an` (laid out as zk_an_cols): zk_ingest_spans_annotated on
+ * the device, so stored bytes reach zk_an_observe (ZK_BATCH_DEVICE_PTRS) without leaving HBM and without a
+ * copy. Records, rejection, dictionaries, `items` (may be NULL: none) and ZK_INGEST_SPAN_NAMES behave exactly
+ * as in those calls for the same arguments. an, or any of its seven columns, NULL: ZK_ERR_INVALID_ARG before
+ * any device is touched. an->n = 0 on entry.
+ *   - Rows: one per time annotation of every ACCEPTED span, none for binary annotations; all field-6 lists
+ *     appended. value = zk_hash_string(value), an annotation without a value field hashing as ""; the kind
+ *     from cs / cr / sr / ss; ipv4 from Endpoint field 1 (the i32's bits), the port from field 2 (the
+ *     i16's bits, in bits 16..31); ZK_AN_HAS_HOST when the annotation carries a host struct (field 3), as
+ *     the host decoder sets it; a row without a host has service_id = ipv4 = 0, no HAS_HOST bit and port 0;
+ *     trace_id and span_id are the record's.
+ *   - Endpoint wire forms: the host decoder's, word for word ("Wire forms" above and the extension in
+ *     zk_ingest_spans_annotated's comment): within an endpoint the last occurrence wins; a known id with
+ *     another wire type is skipped by its type; within one annotation a later host struct keeps the earlier
+ *     ipv4, port and name unless it carries its own; an absent or empty name is "Unknown service name".
+ *   - Order: the host decoder's. Record order and, within a record, the annotation list's order. The output
+ *     is reproducible, so ZK_ERR_CAPACITY leaves a defined prefix:
+ *   - an->cap too small: ZK_ERR_CAPACITY; the records and the first cap rows are written, an->n = cap.
+ *   - `service_id` is THIS decoder's id of the row's host (ids in slot order: compare through names). A row's
+ *     host enters the service dictionary as an entry's host does in the indexed call. More names than
+ *     max_services: ZK_ERR_SERVICE_RANGE; two names with one hash: ZK_ERR_INVALID_SPAN; a strict-mode failure
+ *     or a span-name overflow returns before any row is written. In all these cases an->n = 0.
+ *   - Strings: after the call zk_ingest_dev_string(hash) answers for the value of every row the call wrote,
+ *     as zk_ingest_string does on the host (a timeline needs the text). New values go through the captured-
+ *     string set of the items path, which the pass sizes and regrows itself (with items == NULL too); the
+ *     four core values are answered from the host side without a probe. ZK_INGEST_NO_ROW_STRINGS switches
+ *     the capture off: the rows are identical and zk_ingest_dev_string is untouched by them (the time-skew
+ *     adjuster and the summaries need no text).
+ *   - Bounded stores: a row at or past cap is dropped, never written elsewhere.
+ * The rows come from a pass of their own after the batch's decode, shaped like the index pass (count -> scan
+ * -> write over slices of fragments whose decompressed Spans fit the Snappy scratch, honouring
+ * zk_ingest_dev_set_scratch), but ONE linear walk of a fragment's field-6 lists per kernel: no grouping by
+ * value and no field-8 walk. The decode kernels are those of the calls above. No call runs the index pass
+ * and the rows pass together. */
+zk_status   zk_ingest_dev_spans_annotated(zk_ingest_dev* ing, const uint8_t* buf, const uint64_t* offsets, uint64_t n,
+                                          uint32_t codec, uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
+                                          uint64_t* n_rejected, zk_ingest_items* items /* may be NULL */,
+                                          zk_ingest_annotation_rows* an);
+zk_status   zk_ingest_dev_spans_multi_annotated(zk_ingest_dev* ing, uint32_t nb, const uint8_t* const* bufs,
+                                                const uint64_t* const* offsets, const uint64_t* ns, uint32_t codec,
+                                                uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
+                                                uint64_t* n_rejected, zk_ingest_items* items,
+                                                zk_ingest_annotation_rows* an);
+/* the last rows pass of this decoder: the device time between its first and last launch (ms), and the
+   slices it ran in (0 / 0 before the first annotated call) */
+zk_status   zk_ingest_dev_rows_stats(const zk_ingest_dev* ing, double* pass_ms, uint64_t* slices);
+/* the string behind a key / value hash an items batch of this decoder has seen, or behind the value of a
+   row an annotated call wrote without ZK_INGEST_NO_ROW_STRINGS (two-phase) */
 zk_status   zk_ingest_dev_string(const zk_ingest_dev* ing, uint64_t hash, char* buf, uint64_t cap, uint64_t* len);
 zk_status   zk_ingest_dev_num_services(const zk_ingest_dev* ing, uint32_t* n);
 /* Snappy scratch (deferred fragments' Spans, names not yet in the dictionary): bump-allocated per

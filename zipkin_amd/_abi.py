@@ -484,6 +484,7 @@ ZK_INGEST_STRICT = 1
 ZK_INGEST_ONE_THREAD = 2
 ZK_INGEST_SPAN_NAMES = 4
 ZK_INGEST_NO_CLIENT_RULE = 8
+ZK_INGEST_NO_ROW_STRINGS = 16
 
 
 class zk_moments(C.Structure):
@@ -652,6 +653,12 @@ _SIGNATURES = [
                                                     _U64P, C.POINTER(zk_ingest_items),
                                                     C.POINTER(zk_ingest_index_items)]),
     ("zk_ingest_dev_index_stats", C.c_int, [_P, C.POINTER(C.c_double), _U64P]),
+    ("zk_ingest_dev_spans_annotated", C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _U64P, _U64P,
+                                                C.POINTER(zk_ingest_items), C.POINTER(zk_ingest_annotation_rows)]),
+    ("zk_ingest_dev_spans_multi_annotated", C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _U64P,
+                                                      _U64P, C.POINTER(zk_ingest_items),
+                                                      C.POINTER(zk_ingest_annotation_rows)]),
+    ("zk_ingest_dev_rows_stats", C.c_int, [_P, C.POINTER(C.c_double), _U64P]),
     ("zk_ingest_dev_string", C.c_int, [_P, C.c_uint64, C.c_char_p, C.c_uint64, _U64P]),
     ("zk_ingest_dev_num_services", C.c_int, [_P, C.POINTER(C.c_uint32)]),
     ("zk_ingest_dev_set_scratch", C.c_int, [_P, C.c_uint64]),

@@ -154,6 +154,7 @@ class TraceAnnotationStore:
             raise _abi.ZkError(st, _abi.status_str(st))
         self._h = h
         self.device = device
+        self._held = None  # device row columns a queued observe may still read (observe_stored)
 
     def _check(self, st: int) -> None:
         if st != _abi.ZK_OK:
@@ -193,6 +194,32 @@ class TraceAnnotationStore:
         if sync:
             self.info()
 
+    def observe_stored(self, decoder, buf, offsets, n: int, *, snappy: bool = True, strict: bool = True, spans=None,
+                       row_strings: bool = True):
+        """Decode one batch of STORED fragments already in HBM (buf uint8, offsets int64[n + 1]: torch tensors
+        on the device) with `decoder` (an ingest.DeviceSpanDecoder) and observe its annotation rows in one
+        step: the twin of TraceAnnotationIndex.observe_stored. No row column is copied to the host. With
+        spans= (a spanstore.TraceSpanStore on the same device) the same call's record columns are observed
+        there too, so both stores are fed the same batch (zkannots.h "Expiry", the invariant). Returns
+        (cols, rejected, rows_observed). The row tensors are kept until this handle's next synchronising call
+        (info, gather, compact, expire, observe_stored; observe(sync=True) ends in info), the record columns
+        until the span store's next info() or the next observe_stored(spans=) on it: longer than the
+        device-pointer rule of zk_an_observe / zk_sp_observe requires, never shorter. row_strings=False leaves the
+        values' strings uncaptured (the adjuster and the summaries need no text; a timeline does)."""
+        import torch
+
+        torch.cuda.current_stream(self.device).synchronize()  # (the caller's tensors may still be in flight)
+        cols, rejected, rows = decoder.decode_device(buf, offsets, n, snappy=snappy, strict=strict, annotated=True,
+                                                     row_strings=row_strings)
+        if len(rows):
+            self.observe(rows, sync=False)
+        self._held = rows
+        if spans is not None:
+            if cols.n:
+                spans.observe(cols, sync=False)
+            spans._held = cols
+        return cols, rejected, len(rows)
+
     def reset(self) -> None:
         """Empty the store (zk_an_reset)."""
         self._check(self._L.zk_an_reset(self._h))
@@ -200,6 +227,7 @@ class TraceAnnotationStore:
     def compact(self) -> None:
         """Merge all segments into one (zk_an_compact)."""
         self._check(self._L.zk_an_compact(self._h))
+        self._held = None  # (synchronised)
 
     def expire(self, min_end: int, pins: Optional[Dict[int, int]] = None) -> int:
         """Remove every trace whose end (the maximum ts of its rows) is below its cutoff, whole
@@ -214,12 +242,14 @@ class TraceAnnotationStore:
         removed = C.c_uint64()
         self._check(self._L.zk_an_expire(self._h, int(min_end), ids.ctypes.data if len(ids) else None,
                                          cuts.ctypes.data if len(ids) else None, len(ids), C.byref(removed)))
+        self._held = None  # (synchronised)
         return int(removed.value)
 
     def info(self) -> dict:
         """{"entries", "segments", "bytes"} (zk_an_info); synchronises."""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self._L.zk_an_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        self._held = None  # (synchronised: the columns of a queued observe are consumed)
         return {"entries": int(a.value), "segments": int(b.value), "bytes": int(c.value)}
 
     # ---- reading ---------------------------------------------------------------------------------------
@@ -250,6 +280,7 @@ class TraceAnnotationStore:
         if st == _abi.ZK_ERR_CAPACITY:
             ab = rows.abi()
             self._check(self._L.zk_an_gather(self._h, ptr, n, flags, cp, C.byref(ab), total.value, C.byref(total)))
+        self._held = None  # (synchronised)
         return counts, rows
 
     def _chunks(self, ids):

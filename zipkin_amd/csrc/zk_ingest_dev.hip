@@ -29,6 +29,8 @@
 // The annotation index's entries (zk_ingest_dev_spans_indexed) come from a pass of its own after D5,
 // k_ing_index_raw / _slices / _count / _write at the end of the kernels: count -> scan -> write over
 // slices of fragments whose Spans fit the scratch. The kernels above it are the same with and without it.
+// The annotation store's rows (zk_ingest_dev_spans_annotated) come from a second such pass,
+// k_ing_rows_count / _write behind them: the same slices, one linear walk of the annotations per kernel.
 //
 // Every byte read is bounds-checked: corrupt input marks the fragment undecodable, never faults.
 #include <string.h>
@@ -42,6 +44,7 @@
 
 #include "zk_guard.h"
 #include "zk_launch.h"
+#include "zkannots.h"
 #include "zkingest.h"
 
 namespace zk {
@@ -2738,6 +2741,165 @@ __global__ __launch_bounds__(kIngWG) void k_ing_index_write(IngArgs a, IxArgs x)
     ix_walk<true>(a, x, src, len, at, x.r_last[p], x.r_tid[p]);
 }
 
+// ---- the annotation store's rows (zk_ingest_dev_spans_annotated) ---------------------------------
+// A pass of its own after the batch's decode, laid out as the index pass above (k_ing_index_raw, the
+// scan and k_ing_index_slices are shared; IxArgs carries the slice, the per-fragment arrays, ctl and the
+// capacity), but a fragment's rows come from ONE linear walk of its field-6 lists: a row per annotation,
+// in the list's order (zk_ingest.cpp "the annotation store's rows"). No grouping, no field-8 walk.
+//   k_ing_rows_count  per slice: decompress, count the fragment's rows; a row host the dictionary does
+//                     not hold goes to the extra-name list, a value the captured-string set does not
+//                     hold goes into it and onto the new-string list (the host copies both out before
+//                     the slice's scratch is reused). ctl[4]: the core values seen (bit kind - 1).
+//   k_ing_rows_write  per slice, over the same scratch bytes: row j of fragment i at base + eoff[i] + j,
+//                     the service by dictionary lookup, trace and span id from the record columns
+struct RwArgs {
+    const uint64_t* r_sid;  // the records' span ids at their final index (IxArgs::r_tid: the trace ids)
+    uint64_t* o_tid;        // the caller's seven row columns
+    uint64_t* o_sid;
+    int64_t* o_ts;
+    uint64_t* o_val;
+    uint32_t* o_ipv4;
+    uint32_t* o_svc;
+    uint32_t* o_bits;
+    uint32_t strings;       // capture the value strings (no ZK_INGEST_NO_ROW_STRINGS)
+};
+
+// read_endpoint with the two fields the rows keep: field 1 (i32 -> ipv4) and field 2 (i16 -> port), by
+// the same rules (the last occurrence wins, another wire type is skipped by its type, and a second host
+// struct of the annotation keeps what the first gave unless it carries its own: the caller resets
+// all four per annotation)
+template <class P>
+__device__ __forceinline__ void read_endpoint_row(DRdT<P>& r, P* name, uint32_t* nlen, uint32_t* ipv4, uint32_t* port) {
+    for (;;) {
+        uint8_t t;
+        int16_t id;
+        if (!r.field(&t, &id)) return;
+        if (id == 3 && t == T_STRING)
+            r.str(name, nlen);
+        else if (id == 1 && t == T_I32)
+            *ipv4 = (uint32_t)r.i32();
+        else if (id == 2 && t == T_I16)
+            *port = (uint32_t)(uint16_t)r.i16();
+        else
+            skip_flat(r, t);
+    }
+}
+
+// The rows of one Span at [src, src + len) (bytes the decoder accepted); returns their number.
+// Count: lists unknown hosts and captures value strings (the bytes are global memory that lives until
+// the host has copied them: the slice's scratch or the input buffer); *core: the core kinds seen.
+// Write: row k at `at + k` when that is below the capacity.
+template <bool kWrite>
+__device__ uint32_t rows_walk(const IngArgs& a, const IxArgs& x, const RwArgs& w, const uint8_t* src, uint64_t len,
+                              uint64_t at, uint64_t tid, uint64_t sid, uint32_t* core) {
+    typedef const uint8_t* P;
+    GItemIter<P> it{DRdT<P>{src, src + len, true}, 0, 6};
+    uint32_t m = 0;
+    // the lane's last value hash found in the set: a repeated value skips the probe. (d_hash never gives 0,
+    // which is also the set's empty key: it maps 0 to 1, as zk_hash_string does.)
+    uint64_t known = 0;
+    while (it.next_elem()) {
+        int64_t ts = 0;
+        P v = nullptr, hn = nullptr;
+        uint32_t vl = 0, hl = 0, ip = 0, port = 0;
+        bool host = false;
+        for (;;) {
+            uint8_t t;
+            int16_t id;
+            if (!it.r.field(&t, &id)) break;
+            if (id == 1 && t == T_I64)
+                ts = it.r.i64();
+            else if (id == 2 && t == T_STRING)
+                it.r.str(&v, &vl);
+            else if (id == 3 && t == T_STRUCT) {
+                host = true;
+                read_endpoint_row(it.r, &hn, &hl, &ip, &port);
+            } else
+                skip_flat(it.r, t);
+        }
+        if (!it.r.ok) break;  // (the decoder read these bytes: never taken)
+        int c = 0;
+        const bool is_c = is_core(v, vl, &c);
+        uint32_t id = 0;
+        if (host) {
+            if (!hn || hl == 0) {
+                hn = a.unknown;
+                hl = kUnknownLen;
+            }
+            uint64_t h;
+            id = kNoId;
+            const bool found = resolve16_id(a, hn, hl, &h, &id);
+            if constexpr (kWrite) {
+                if (!found) atomicAdd(&x.ctl[3], 1ull);
+            } else if (!found) {
+                const unsigned long long q = atomicAdd(&a.icnt[3], 1ull);
+                if (q < a.x_cap) {  // (past it the host sees the count, grows the list and counts the slice again)
+                    a.x_hash[q] = h;
+                    a.x_ptr[q] = (uint64_t)(uintptr_t)hn;
+                    a.x_len[q] = hl;
+                    a.x_keep[q] = 1u;
+                    a.x_status[q] = kStOk;
+                    a.x_list[q] = (uint32_t)q;
+                }
+            }
+        }
+        if constexpr (kWrite) {
+            const uint64_t q = at + m;
+            if (q < x.cap) {
+                w.o_tid[q] = tid;
+                w.o_sid[q] = sid;
+                w.o_ts[q] = ts;
+                w.o_val[q] = d_hash(v, v ? vl : 0u);
+                w.o_ipv4[q] = host ? ip : 0u;
+                w.o_svc[q] = host ? id : 0u;
+                w.o_bits[q] = (is_c ? (uint32_t)c + 1u : 0u) | (host ? (ZK_AN_HAS_HOST | (port << ZK_AN_PORT_SHIFT)) : 0u);
+            }
+        } else if (is_c) {
+            *core |= 1u << c;
+        } else if (w.strings) {
+            const bool vv = v != nullptr && vl > 0;
+            const uint64_t h = d_hash(v, vv ? vl : 0u);
+            // (a full set fails the probe and counts in icnt[4]: the host grows it and counts the slice again)
+            if (h != known && capture_string(a, h, vv ? v : a.unknown, vv ? vl : 0u, vv ? v : a.unknown)) known = h;
+        }
+        ++m;
+    }
+    return m;
+}
+
+__global__ __launch_bounds__(kIngWG) void k_ing_rows_count(IngArgs a, IxArgs x, RwArgs w) {
+    const uint64_t i = x.lo + (uint64_t)blockIdx.x * kIngWG + threadIdx.x;
+    uint64_t p, len, n = 0;
+    uint32_t core = 0;
+    if (i < x.hi && ix_live(a, x, i, &p)) {
+        const uint8_t* src = ix_span(a, x, i, &len);
+        bool ok = true;
+        if (a.snappy) {
+            const uint64_t so = x.raw_off[i] - x.raw_off[x.lo];
+            ok = len > 0 && so + len <= a.scratch_cap &&
+                 snappy_block(a.buf + a.offsets[i], a.ends[i] - a.offsets[i], a.scratch + so, len);
+            if (!ok) atomicAdd(&x.ctl[3], 1ull);  // (the decoder read these bytes: never taken)
+        }
+        if (ok) n = rows_walk<false>(a, x, w, src, len, 0, 0, 0, &core);
+    }
+    if (i < x.hi) x.cnt[i] = n;
+    // the core kinds of the wave, one atomic per wave, and only while the word lacks one of them
+    for (int d = 32; d > 0; d >>= 1) core |= (uint32_t)__shfl_xor((int)core, d);
+    if (__lane_id() == 0 && core && (x.ctl[4] & core) != core) atomicOr(&x.ctl[4], (unsigned long long)core);
+}
+
+__global__ __launch_bounds__(kIngWG) void k_ing_rows_write(IngArgs a, IxArgs x, RwArgs w) {
+    const uint64_t i = x.lo + (uint64_t)blockIdx.x * kIngWG + threadIdx.x;
+    if (i >= x.hi) return;
+    const uint64_t base = x.ctl[1 + x.parity], n = x.cnt[i], at = base + x.eoff[i];
+    if (i == x.hi - 1) x.ctl[1 + (x.parity ^ 1u)] = at + n;  // the rows before the next slice
+    if (n == 0) return;
+    uint64_t p, len;
+    if (!ix_live(a, x, i, &p)) return;
+    const uint8_t* src = ix_span(a, x, i, &len);
+    rows_walk<true>(a, x, w, src, len, at, x.r_tid[p], w.r_sid[p], nullptr);
+}
+
 }  // namespace
 }  // namespace zk
 
@@ -2797,6 +2959,10 @@ struct zk_ingest_dev : zk_ing_dict {  // (the base: the service dictionary)
     hipEvent_t ix_ev[2] = {nullptr, nullptr};  // around the last pass
     bool ix_timed = false;
     uint64_t ix_slices = 0;                // slices of the last pass
+    // the rows pass (zk_ingest_dev_spans_annotated; it runs on ix_ctl: no call runs both passes)
+    hipEvent_t rw_ev[2] = {nullptr, nullptr};  // around the last pass
+    bool rw_timed = false;
+    uint64_t rw_slices = 0;                // slices of the last pass
     std::string err;
 };
 
@@ -2925,6 +3091,8 @@ zk_status zk_ingest_dev_destroy(zk_ingest_dev* g) {
     hipFree(g->ix_ctl);
     for (hipEvent_t e : g->ix_ev)
         if (e) hipEventDestroy(e);
+    for (hipEvent_t e : g->rw_ev)
+        if (e) hipEventDestroy(e);
     if (g->own_stream && g->stream) hipStreamDestroy(g->stream);
     delete g;
     return ZK_OK;
@@ -3052,6 +3220,39 @@ void bind_items(zk_ingest_dev* g, IngArgs& a, IngArgs& x) {
     x.status = a.x_status;
     x.pub = a.x_list;
     x.pub_n = a.icnt + 3;
+}
+
+// The first `count` strings of the new-string list (a.ns_*: captured since the list's counter was last
+// cleared) -> the host map. Their bytes are gathered on the device (one kernel, one copy), so this runs
+// while they are still alive: before the scratch they may lie in is reused. gt joins `retired`.
+zk_status harvest_strings(zk_ingest_dev* g, const IngArgs& a, uint64_t count, hipStream_t s, std::vector<uint8_t*>& retired) {
+    const uint64_t m = std::min<uint64_t>(count, g->ns_cap);
+    std::vector<uint64_t> hh(m), pp(m), off(m);
+    std::vector<uint32_t> ll(m);
+    ING_HIP(g, hipMemcpyAsync(hh.data(), a.ns_hash, m * 8, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipMemcpyAsync(pp.data(), a.ns_ptr, m * 8, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipMemcpyAsync(ll.data(), a.ns_len, m * 4, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipStreamSynchronize(s));
+    uint64_t total = 0;
+    for (uint64_t k = 0; k < m; ++k) {
+        off[k] = total;
+        total += ll[k];
+    }
+    std::string bytes(total, '\0');
+    if (total) {
+        uint8_t* gt = nullptr;  // destination offsets, then the gathered bytes
+        ING_HIP(g, hipMalloc(&gt, m * 8 + total));
+        retired.push_back(gt);
+        ING_HIP(g, hipMemcpyAsync(gt, off.data(), m * 8, hipMemcpyHostToDevice, s));
+        ING_HIP(g, launch_checked("k_ing_gather_names", k_ing_gather_names, dim3((unsigned)((m + 255) / 256)), dim3(256),
+                                  0, s, (const uint64_t*)a.ns_ptr, (const uint64_t*)gt, (const uint32_t*)a.ns_len,
+                                  (uint32_t)m, gt + m * 8));
+        ING_HIP(g, hipMemcpyAsync(&bytes[0], gt + m * 8, total, hipMemcpyDeviceToHost, s));
+        ING_HIP(g, hipStreamSynchronize(s));
+    }
+    for (uint64_t k = 0; k < m; ++k) g->strings.emplace(hh[k], bytes.substr(off[k], ll[k]));
+    g->s_count += m;
+    return ZK_OK;
 }
 
 // After D3: ids for the slots a batch claimed in dictionary d, in slot order; their names gathered
@@ -3423,32 +3624,8 @@ zk_status ingest_batch(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* off
     if (items && icf[2]) {
         // the strings captured in this batch -> the host map (before any error return: their hashes
         // are in the device set from now on)
-        const uint64_t m = std::min<uint64_t>(icf[2], g->ns_cap);
-        std::vector<uint64_t> hh(m), pp(m), off(m);
-        std::vector<uint32_t> ll(m);
-        ING_HIP(g, hipMemcpyAsync(hh.data(), a.ns_hash, m * 8, hipMemcpyDeviceToHost, s));
-        ING_HIP(g, hipMemcpyAsync(pp.data(), a.ns_ptr, m * 8, hipMemcpyDeviceToHost, s));
-        ING_HIP(g, hipMemcpyAsync(ll.data(), a.ns_len, m * 4, hipMemcpyDeviceToHost, s));
-        ING_HIP(g, hipStreamSynchronize(s));
-        uint64_t total = 0;
-        for (uint64_t k = 0; k < m; ++k) {
-            off[k] = total;
-            total += ll[k];
-        }
-        std::string bytes(total, '\0');
-        if (total) {
-            uint8_t* gt = nullptr;  // destination offsets, then the gathered bytes
-            ING_HIP(g, hipMalloc(&gt, m * 8 + total));
-            retired.push_back(gt);
-            ING_HIP(g, hipMemcpyAsync(gt, off.data(), m * 8, hipMemcpyHostToDevice, s));
-            ING_HIP(g, launch_checked("k_ing_gather_names", k_ing_gather_names, dim3((unsigned)((m + 255) / 256)), dim3(256),
-                                      0, s, (const uint64_t*)a.ns_ptr, (const uint64_t*)gt, (const uint32_t*)a.ns_len,
-                                      (uint32_t)m, gt + m * 8));
-            ING_HIP(g, hipMemcpyAsync(&bytes[0], gt + m * 8, total, hipMemcpyDeviceToHost, s));
-            ING_HIP(g, hipStreamSynchronize(s));
-        }
-        for (uint64_t k = 0; k < m; ++k) g->strings.emplace(hh[k], bytes.substr(off[k], ll[k]));
-        g->s_count += m;
+        const zk_status st = harvest_strings(g, a, icf[2], s, retired);
+        if (st != ZK_OK) return st;
     }
     for (uint8_t* r : retired) hipFree(r);
     uint64_t dropped = 0;  // every fragment whose status is not ok is not a record
@@ -3627,13 +3804,100 @@ hipError_t size_ix_ctl(zk_ingest_dev* g, uint64_t slices) {
     return e;
 }
 
+// The start of a pass over a decoded batch (the index pass, the rows pass): ctl and the extra-name counters
+// cleared, the fragments' decompressed lengths and their scan, and the slices in *bounds: everything at
+// once when the batch's Spans fit the scratch (always, for the thrift codec); the scratch grows only for a
+// fragment larger than all of it. a.scratch / a.scratch_cap and x.ctl are set for the pass; *need: the
+// scan's temporary bytes (g->cub holds them).
+zk_status lay_out_slices(zk_ingest_dev* g, IngArgs& a, IxArgs& x, hipStream_t s, const char* what,
+                         std::vector<uint64_t>* bounds_out, size_t* need_out) {
+    const uint64_t n = a.n, n1 = n + 1;
+    const dim3 blk(kIngWG);
+    ING_HIP(g, hipMemsetAsync(x.ctl, 0, 8 * 8, s));
+    ING_HIP(g, hipMemsetAsync(a.icnt + 3, 0, 4 * 8, s));
+    ING_HIP(g, hipMemsetAsync(x.raw + n, 0, 8, s));
+    ING_HIP(g, launch_checked("k_ing_index_raw", k_ing_index_raw, dim3((unsigned)((n + kIngWG - 1) / kIngWG)), blk, 0, s, a, x));
+    size_t need = 0;
+    ING_HIP(g, hipcub::DeviceScan::ExclusiveSum(nullptr, need, x.raw, x.raw_off, (int)n1, s));
+    if (need > g->cub_cap) {
+        hipFree(g->cub);
+        g->cub = nullptr;
+        g->cub_cap = 0;
+        ING_HIP(g, hipMalloc(&g->cub, need));
+        g->cub_cap = need;
+    }
+    ING_HIP(g, hipcub::DeviceScan::ExclusiveSum(g->cub, need, x.raw, x.raw_off, (int)n1, s));
+    unsigned long long* const hc = g->h_counts;
+    ING_HIP(g, hipMemcpyAsync(hc, x.raw_off + n, 8, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipMemcpyAsync(hc + 1, x.ctl, 8, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipStreamSynchronize(s));
+    const uint64_t total_raw = hc[0], max_raw = hc[1];
+    std::vector<uint64_t> bounds{0, n};
+    if (a.snappy && total_raw) {
+        if (max_raw > g->scratch_cap) {
+            hipFree(g->scratch);
+            g->scratch = nullptr;
+            g->scratch_cap = 0;
+            ING_HIP(g, hipMalloc(&g->scratch, max_raw));
+            g->scratch_cap = max_raw;
+        }
+        // the bytes alive at once: the scratch as it is, or the size zk_ingest_dev_set_scratch asked for
+        // when the decode has grown it past that (at least the largest fragment either way)
+        uint64_t budget = g->scratch_cap;
+        if (g->scratch_min) budget = std::min(budget, std::max(g->scratch_min, max_raw));
+        a.scratch = g->scratch;
+        a.scratch_cap = budget;
+        if (total_raw > budget) {
+            // two greedy slices in a row hold more than one budget: at most 2 total / budget + 1 of them
+            const uint64_t ms = 2 * (total_raw / budget) + 2;
+            ING_HIP(g, size_ix_ctl(g, ms));
+            x.ctl = g->ix_ctl;
+            ING_HIP(g, hipMemsetAsync(x.ctl, 0, 8 * 8, s));
+            uint64_t* const db = (uint64_t*)(g->ix_ctl + 8);
+            uint32_t* const dn = (uint32_t*)(db + ms + 1);
+            ING_HIP(g, launch_checked("k_ing_index_slices", k_ing_index_slices, dim3(1), dim3(64), 0, s,
+                                      (const uint64_t*)x.raw_off, n, budget, db, (uint32_t)std::min<uint64_t>(ms, 0xFFFFFFFFull), dn));
+            ING_HIP(g, hipMemcpyAsync(hc, dn, 4, hipMemcpyDeviceToHost, s));
+            ING_HIP(g, hipStreamSynchronize(s));
+            const uint32_t k = *(const uint32_t*)hc;
+            if (!k) return dfail(g, ZK_ERR_HIP, std::string(what) + ": the slices of the batch could not be laid out");
+            bounds.resize((size_t)k + 1);
+            ING_HIP(g, hipMemcpyAsync(bounds.data(), db, ((size_t)k + 1) * 8, hipMemcpyDeviceToHost, s));
+            ING_HIP(g, hipStreamSynchronize(s));
+        }
+    }
+    *bounds_out = std::move(bounds);
+    *need_out = need;
+    return ZK_OK;
+}
+
+// The hosts a slice's count kernel listed as new names (ax: the extra list as "fragments", bind_items):
+// D3, ids in slot order, D4 (exact bytes, range), before the next slice takes the scratch their bytes may
+// lie in. whose: "an entry's host" / "a row's host", for the collision's message.
+zk_status publish_extra_names(zk_ingest_dev* g, IngArgs& a, const IngArgs& ax, hipStream_t s, std::vector<uint8_t*>& retired,
+                              const char* whose) {
+    const dim3 xgrid(64), blk(kIngWG);
+    unsigned long long* const hc = g->h_counts;
+    ING_HIP(g, launch_checked("k_ing_dict_insert_x", k_ing_dict_insert_x, xgrid, blk, 0, s, ax));
+    const zk_status st = dict_assign_ids(g, g, s, retired, 0, nullptr);
+    if (st != ZK_OK) return st;
+    a.unknown = g->arena;
+    ING_HIP(g, launch_checked("k_ing_lookup_x", k_ing_lookup_x, xgrid, blk, 0, s, ax));
+    ING_HIP(g, hipMemsetAsync(a.icnt + 5, 0, 2 * 8, s));
+    ING_HIP(g, launch_checked("k_ing_count_extra", k_ing_count_extra, xgrid, blk, 0, s, ax));
+    ING_HIP(g, hipMemcpyAsync(hc, a.icnt + 5, 2 * 8, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipStreamSynchronize(s));
+    if (hc[0]) return dfail(g, ZK_ERR_INVALID_SPAN, std::string("two service names (") + whose + ") share a 64-bit hash");
+    if (hc[1]) return dfail(g, ZK_ERR_SERVICE_RANGE, "more distinct service names than max_services");
+    return ZK_OK;
+}
+
 // The index pass over a decoded batch (the kernels' comment above IxArgs): the entries of the
 // accepted fragments into the device columns of ix, in the host decoder's order. The stream is idle
 // when this starts (the decode waits for its results) and when it returns.
 zk_status index_pass(zk_ingest_dev* g, const IngBatchState& bs, uint32_t flags, const zk_span_cols* out,
                      zk_ingest_index_items* ix) {
     IngArgs a = bs.a;
-    const uint64_t n = a.n, n1 = n + 1;
     hipStream_t s = g->stream;
     ING_HIP(g, hipSetDevice(g->device));
     for (hipEvent_t& e : g->ix_ev)
@@ -3664,67 +3928,18 @@ zk_status index_pass(zk_ingest_dev* g, const IngBatchState& bs, uint32_t flags, 
     a.unknown = g->arena;
     const dim3 blk(kIngWG);
     ING_HIP(g, hipEventRecord(g->ix_ev[0], s));
-    ING_HIP(g, hipMemsetAsync(x.ctl, 0, 8 * 8, s));
-    ING_HIP(g, hipMemsetAsync(a.icnt + 3, 0, 4 * 8, s));
-    ING_HIP(g, hipMemsetAsync(x.raw + n, 0, 8, s));
-    ING_HIP(g, launch_checked("k_ing_index_raw", k_ing_index_raw, dim3((unsigned)((n + kIngWG - 1) / kIngWG)), blk, 0, s, a, x));
+    std::vector<uint64_t> bounds;
     size_t need = 0;
-    ING_HIP(g, hipcub::DeviceScan::ExclusiveSum(nullptr, need, x.raw, x.raw_off, (int)n1, s));
-    if (need > g->cub_cap) {
-        hipFree(g->cub);
-        g->cub = nullptr;
-        g->cub_cap = 0;
-        ING_HIP(g, hipMalloc(&g->cub, need));
-        g->cub_cap = need;
+    {
+        const zk_status st = lay_out_slices(g, a, x, s, "index pass", &bounds, &need);
+        if (st != ZK_OK) return st;
     }
-    ING_HIP(g, hipcub::DeviceScan::ExclusiveSum(g->cub, need, x.raw, x.raw_off, (int)n1, s));
     unsigned long long* const hc = g->h_counts;
-    ING_HIP(g, hipMemcpyAsync(hc, x.raw_off + n, 8, hipMemcpyDeviceToHost, s));
-    ING_HIP(g, hipMemcpyAsync(hc + 1, x.ctl, 8, hipMemcpyDeviceToHost, s));
-    ING_HIP(g, hipStreamSynchronize(s));
-    const uint64_t total_raw = hc[0], max_raw = hc[1];
-    // the slices: everything at once when the batch's Spans fit the scratch (always, for the thrift
-    // codec); the scratch grows only for a fragment larger than all of it
-    std::vector<uint64_t> bounds{0, n};
-    if (a.snappy && total_raw) {
-        if (max_raw > g->scratch_cap) {
-            hipFree(g->scratch);
-            g->scratch = nullptr;
-            g->scratch_cap = 0;
-            ING_HIP(g, hipMalloc(&g->scratch, max_raw));
-            g->scratch_cap = max_raw;
-        }
-        // the bytes alive at once: the scratch as it is, or the size zk_ingest_dev_set_scratch asked for
-        // when the decode has grown it past that (at least the largest fragment either way)
-        uint64_t budget = g->scratch_cap;
-        if (g->scratch_min) budget = std::min(budget, std::max(g->scratch_min, max_raw));
-        a.scratch = g->scratch;
-        a.scratch_cap = budget;
-        if (total_raw > budget) {
-            // two greedy slices in a row hold more than one budget: at most 2 total / budget + 1 of them
-            const uint64_t ms = 2 * (total_raw / budget) + 2;
-            ING_HIP(g, size_ix_ctl(g, ms));
-            x.ctl = g->ix_ctl;
-            ING_HIP(g, hipMemsetAsync(x.ctl, 0, 8 * 8, s));
-            uint64_t* const db = (uint64_t*)(g->ix_ctl + 8);
-            uint32_t* const dn = (uint32_t*)(db + ms + 1);
-            ING_HIP(g, launch_checked("k_ing_index_slices", k_ing_index_slices, dim3(1), dim3(64), 0, s,
-                                      (const uint64_t*)x.raw_off, n, budget, db, (uint32_t)std::min<uint64_t>(ms, 0xFFFFFFFFull), dn));
-            ING_HIP(g, hipMemcpyAsync(hc, dn, 4, hipMemcpyDeviceToHost, s));
-            ING_HIP(g, hipStreamSynchronize(s));
-            const uint32_t k = *(const uint32_t*)hc;
-            if (!k) return dfail(g, ZK_ERR_HIP, "index pass: the slices of the batch could not be laid out");
-            bounds.resize((size_t)k + 1);
-            ING_HIP(g, hipMemcpyAsync(bounds.data(), db, ((size_t)k + 1) * 8, hipMemcpyDeviceToHost, s));
-            ING_HIP(g, hipStreamSynchronize(s));
-        }
-    }
     std::vector<uint8_t*> retired;  // old arenas stay valid until the pass is done
     auto leave = [&](zk_status st, const std::string& m) {
         for (uint8_t* r : retired) hipFree(r);
         return dfail(g, st, m);
     };
-    const dim3 xgrid(64);
     IngArgs ax{};
     uint32_t parity = 0;
     for (size_t k = 0; k + 1 < bounds.size();) {
@@ -3744,19 +3959,8 @@ zk_status index_pass(zk_ingest_dev* g, const IngBatchState& bs, uint32_t flags, 
             continue;
         }
         if (extra) {
-            // the entry hosts that are new names: D3, ids in slot order, D4 (exact bytes, range), before
-            // the next slice takes the scratch their bytes may lie in
-            ING_HIP(g, launch_checked("k_ing_dict_insert_x", k_ing_dict_insert_x, xgrid, blk, 0, s, ax));
-            const zk_status st = dict_assign_ids(g, g, s, retired, 0, nullptr);
+            const zk_status st = publish_extra_names(g, a, ax, s, retired, "an entry's host");
             if (st != ZK_OK) return leave(st, g->err);
-            a.unknown = g->arena;
-            ING_HIP(g, launch_checked("k_ing_lookup_x", k_ing_lookup_x, xgrid, blk, 0, s, ax));
-            ING_HIP(g, hipMemsetAsync(a.icnt + 5, 0, 2 * 8, s));
-            ING_HIP(g, launch_checked("k_ing_count_extra", k_ing_count_extra, xgrid, blk, 0, s, ax));
-            ING_HIP(g, hipMemcpyAsync(hc, a.icnt + 5, 2 * 8, hipMemcpyDeviceToHost, s));
-            ING_HIP(g, hipStreamSynchronize(s));
-            if (hc[0]) return leave(ZK_ERR_INVALID_SPAN, "two service names (an entry's host) share a 64-bit hash");
-            if (hc[1]) return leave(ZK_ERR_SERVICE_RANGE, "more distinct service names than max_services");
         }
         ING_HIP(g, hipcub::DeviceScan::ExclusiveSum(g->cub, need, x.cnt + x.lo, x.eoff + x.lo, (int)m, s));
         ING_HIP(g, launch_checked("k_ing_index_write", k_ing_index_write, grid, blk, 0, s, a, x));
@@ -3790,6 +3994,136 @@ zk_status finish_indexed(zk_ingest_dev* g, zk_status st, const IngBatchState& bs
     const std::string item_err = g->err;
     const zk_status si = index_pass(g, bs, flags, out, ix);
     if (si != ZK_OK) return si;
+    if (st != ZK_OK) g->err = item_err;
+    return st;
+}
+
+// The rows pass over a decoded batch (the kernels' comment above RwArgs): the annotation rows of the
+// accepted fragments into the seven device columns of an, in the host decoder's order. The stream is idle
+// when this starts and when it returns. Per slice: count (which also lists new hosts and captures new
+// value strings), the new strings to the host map, the new hosts through D3 / D4, scan, write.
+zk_status rows_pass(zk_ingest_dev* g, const IngBatchState& bs, uint32_t flags, const zk_span_cols* out,
+                    zk_ingest_annotation_rows* an) {
+    IngArgs a = bs.a;
+    hipStream_t s = g->stream;
+    ING_HIP(g, hipSetDevice(g->device));
+    for (hipEvent_t& e : g->rw_ev)
+        if (!e) ING_HIP(g, hipEventCreate(&e));
+    g->rw_timed = false;
+    g->rw_slices = 0;
+    ING_HIP(g, size_ix_ctl(g, 1));
+    if (!g->xs) ING_HIP(g, size_extra(g, 4096, 0));  // (the items path sizes these only when it runs)
+    const bool strings = (flags & ZK_INGEST_NO_ROW_STRINGS) == 0;
+    if (strings && !g->s_key) ING_HIP(g, grow_string_set(g, 1u << 16));
+    IxArgs x{};
+    x.raw = bs.w[0];
+    x.raw_off = bs.w[1];
+    x.cnt = bs.w[2];
+    x.eoff = bs.w[3];
+    x.ctl = g->ix_ctl;
+    x.dropped = bs.dropped ? 1u : 0u;
+    x.r_tid = (const uint64_t*)out->trace_id;
+    x.r_flags = (const uint32_t*)out->flags;
+    x.cap = an->cap;
+    RwArgs w{};
+    w.r_sid = (const uint64_t*)out->span_id;
+    w.o_tid = an->trace_id;
+    w.o_sid = an->span_id;
+    w.o_ts = an->ts;
+    w.o_val = an->value;
+    w.o_ipv4 = an->ipv4;
+    w.o_svc = an->service_id;
+    w.o_bits = an->bits;
+    w.strings = strings ? 1u : 0u;
+    a.scratch = g->scratch;
+    a.scratch_cap = g->scratch_cap;
+    a.unknown = g->arena;
+    const dim3 blk(kIngWG);
+    ING_HIP(g, hipEventRecord(g->rw_ev[0], s));
+    std::vector<uint64_t> bounds;
+    size_t need = 0;
+    {
+        const zk_status st = lay_out_slices(g, a, x, s, "rows pass", &bounds, &need);
+        if (st != ZK_OK) return st;
+    }
+    unsigned long long* const hc = g->h_counts;
+    std::vector<uint8_t*> retired;  // old arenas and gather tables stay valid until the pass is done
+    auto leave = [&](zk_status st, const std::string& m) {
+        for (uint8_t* r : retired) hipFree(r);
+        return dfail(g, st, m);
+    };
+    IngArgs ax{};
+    uint32_t parity = 0;
+    for (size_t k = 0; k + 1 < bounds.size();) {
+        x.lo = bounds[k];
+        x.hi = bounds[k + 1];
+        x.parity = parity;
+        const uint64_t m = x.hi - x.lo;
+        const dim3 grid((unsigned)((m + kIngWG - 1) / kIngWG));
+        if (strings) {  // the set at most half full before a slice, the list as long as the set
+            while (g->s_count * 2 > g->s_cap) ING_HIP(g, grow_string_set(g, g->s_cap * 2));
+            ING_HIP(g, size_new_strings(g, 0));
+        }
+        bind_items(g, a, ax);
+        ING_HIP(g, hipMemsetAsync(a.icnt + 2, 0, 3 * 8, s));  // captured strings, extra names, a full set
+        ING_HIP(g, launch_checked("k_ing_rows_count", k_ing_rows_count, grid, blk, 0, s, a, x, w));
+        ING_HIP(g, hipMemcpyAsync(hc, a.icnt + 2, 3 * 8, hipMemcpyDeviceToHost, s));
+        ING_HIP(g, hipStreamSynchronize(s));
+        const uint64_t fresh = hc[0], extra = hc[1], set_full = hc[2];
+        if (fresh) {
+            // this attempt's new strings -> the host map, whether or not the slice is counted again: their
+            // hashes are in the device set from now on, and their bytes may lie in the slice's scratch
+            const zk_status st = harvest_strings(g, a, fresh, s, retired);
+            if (st != ZK_OK) return leave(st, g->err);
+        }
+        if (set_full) {  // a probe ran past kSetProbes: a larger set, and the slice again
+            ING_HIP(g, grow_string_set(g, g->s_cap * 2));
+            continue;
+        }
+        if (extra > g->x_cap) {  // the extra-name list is too short for this slice: a longer one, and again
+            ING_HIP(g, size_extra(g, std::max<uint64_t>(2 * g->x_cap, 2 * extra), 0));
+            continue;
+        }
+        if (extra) {
+            const zk_status st = publish_extra_names(g, a, ax, s, retired, "a row's host");
+            if (st != ZK_OK) return leave(st, g->err);
+        }
+        ING_HIP(g, hipcub::DeviceScan::ExclusiveSum(g->cub, need, x.cnt + x.lo, x.eoff + x.lo, (int)m, s));
+        ING_HIP(g, launch_checked("k_ing_rows_write", k_ing_rows_write, grid, blk, 0, s, a, x, w));
+        parity ^= 1u;
+        ++k;
+    }
+    ING_HIP(g, hipEventRecord(g->rw_ev[1], s));
+    ING_HIP(g, hipMemcpyAsync(hc, x.ctl + 1 + parity, 8, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipMemcpyAsync(hc + 1, x.ctl + 3, 2 * 8, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipStreamSynchronize(s));
+    g->rw_timed = true;
+    g->rw_slices = bounds.size() - 1;
+    const uint64_t total = hc[0];
+    if (hc[1]) return leave(ZK_ERR_HIP, "rows pass: " + std::to_string(hc[1]) + " fragments or hosts could not be read again");
+    for (uint8_t* r : retired) hipFree(r);
+    if (strings) {  // the core values the rows carry, from a table (the count kernel does not probe for them)
+        static const char* const kCore[4] = {"cs", "cr", "sr", "ss"};
+        for (int c = 0; c < 4; ++c)
+            if (hc[2] >> c & 1ull) g->strings.emplace(zk_hash_string(kCore[c], 2), kCore[c]);
+    }
+    an->n = std::min<uint64_t>(total, an->cap);
+    if (total > an->cap)
+        return dfail(g, ZK_ERR_CAPACITY, "annotation row buffers too small: " + std::to_string(total) + " rows");
+    return ZK_OK;
+}
+
+bool an_valid(const zk_ingest_annotation_rows* an) {
+    return an && an->trace_id && an->span_id && an->ts && an->value && an->ipv4 && an->service_id && an->bits;
+}
+
+// after the decode of an annotated call: as finish_indexed, with the rows pass
+zk_status finish_annotated(zk_ingest_dev* g, zk_status st, const IngBatchState& bs, uint32_t flags, const zk_span_cols* out,
+                           zk_ingest_annotation_rows* an) {
+    if (!bs.done || (st != ZK_OK && st != ZK_ERR_CAPACITY)) return st;
+    const std::string item_err = g->err;
+    const zk_status sr = rows_pass(g, bs, flags, out, an);
+    if (sr != ZK_OK) return sr;
     if (st != ZK_OK) g->err = item_err;
     return st;
 }
@@ -3857,6 +4191,45 @@ zk_status zk_ingest_dev_index_stats(const zk_ingest_dev* g, double* pass_ms, uin
     if (g->ix_timed) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, g->ix_ev[0], g->ix_ev[1]) != hipSuccess) return ZK_ERR_HIP;
+        *pass_ms = ms;
+    }
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+zk_status zk_ingest_dev_spans_annotated(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* offsets, uint64_t n,
+                                        uint32_t codec, uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
+                                        uint64_t* n_rejected, zk_ingest_items* items, zk_ingest_annotation_rows* an) {
+    ZK_GUARD_BEGIN
+    if (!g || !an_valid(an)) return ZK_ERR_INVALID_ARG;  // (before any device is touched)
+    an->n = 0;
+    IngBatchState bs;
+    const zk_status st = ingest_batch(g, buf, offsets, n, codec, flags, out, n_out, n_rejected, items, nullptr, &bs);
+    return finish_annotated(g, st, bs, flags, out, an);
+    ZK_GUARD_END
+}
+
+zk_status zk_ingest_dev_spans_multi_annotated(zk_ingest_dev* g, uint32_t nb, const uint8_t* const* bufs,
+                                              const uint64_t* const* offsets, const uint64_t* ns, uint32_t codec,
+                                              uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
+                                              uint64_t* n_rejected, zk_ingest_items* items, zk_ingest_annotation_rows* an) {
+    ZK_GUARD_BEGIN
+    if (!g || !an_valid(an)) return ZK_ERR_INVALID_ARG;
+    an->n = 0;
+    IngBatchState bs;
+    const zk_status st = ingest_multi(g, nb, bufs, offsets, ns, codec, flags, out, n_out, n_rejected, items, &bs);
+    return finish_annotated(g, st, bs, flags, out, an);
+    ZK_GUARD_END
+}
+
+zk_status zk_ingest_dev_rows_stats(const zk_ingest_dev* g, double* pass_ms, uint64_t* slices) {
+    ZK_GUARD_BEGIN
+    if (!g || !pass_ms || !slices) return ZK_ERR_INVALID_ARG;
+    *pass_ms = 0.0;
+    *slices = g->rw_slices;
+    if (g->rw_timed) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, g->rw_ev[0], g->rw_ev[1]) != hipSuccess) return ZK_ERR_HIP;
         *pass_ms = ms;
     }
     return ZK_OK;

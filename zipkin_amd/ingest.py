@@ -226,6 +226,11 @@ def snappy_uncompress(data: bytes) -> bytes:
     return out[: n.value].tobytes()
 
 
+def _one_pass(indexed: bool, annotated: bool) -> None:
+    if indexed and annotated:
+        raise ValueError("annotated=True with indexed=True: no call runs the index pass and the rows pass together")
+
+
 class DeviceSpanDecoder:
     """zk_ingest_dev: stored fragments already in HBM -> device columns (one lane per fragment).
 
@@ -274,7 +279,8 @@ class DeviceSpanDecoder:
 
     def decode_device(self, buf, offsets, n: int, *, snappy: bool = True, strict: bool = True, out=None,
                       items: bool = False, item_cap: int | None = None, span_names: bool = False,
-                      indexed: bool = False, client_rule: bool = True, index_cap: int | None = None):
+                      indexed: bool = False, client_rule: bool = True, index_cap: int | None = None,
+                      annotated: bool = False, row_cap: int | None = None, row_strings: bool = True):
         """-> (DeviceColumns with .n = records written, rejected), or with items=True
         (cols, rejected, (kv_service, kv_key), (ann_service, ann_value)): the span indexer's items as
         device tensors (int32 service ids of this decoder, int64 hashes = uint64 bit patterns), in no
@@ -286,11 +292,22 @@ class DeviceSpanDecoder:
         entries), or after the two item pairs with items=True. client_rule=False emits the entries of
         a client-side span of the service "client" too (ZK_INGEST_NO_CLIENT_RULE). index_cap: the
         entries to allow for (default 8 per fragment, at least 16; a batch with more is decoded again
-        with 4x the room)."""
+        with 4x the room).
+        annotated=True (zk_ingest_dev_spans_annotated) appends the annotation store's rows, an
+        annotstore.DeviceAnnotationRows in the host decoder's order, to the result: (cols, rejected,
+        rows), or after the two item pairs with items=True. row_cap: the rows to allow for (default 8
+        per fragment, at least 16; a batch with more is decoded again with 4x the room).
+        row_strings=False (ZK_INGEST_NO_ROW_STRINGS) leaves the rows' value strings uncaptured: the
+        rows are the same, string() does not learn them. annotated and indexed together are a
+        ValueError: no C call runs both passes."""
+        _one_pass(indexed, annotated)
         L, h = self._L, self._h
         bp, op = buf.data_ptr(), offsets.data_ptr()
 
-        def call(codec, flags, ab, nout, nrej, it, ix=None):
+        def call(codec, flags, ab, nout, nrej, it, ix=None, an=None):
+            if an is not None:
+                return L.zk_ingest_dev_spans_annotated(h, bp, op, n, codec, flags, C.byref(ab), C.byref(nout), C.byref(nrej),
+                                                       None if it is None else C.byref(it), C.byref(an))
             if ix is not None:
                 return L.zk_ingest_dev_spans_indexed(h, bp, op, n, codec, flags, C.byref(ab), C.byref(nout), C.byref(nrej),
                                                      None if it is None else C.byref(it), C.byref(ix))
@@ -299,15 +316,18 @@ class DeviceSpanDecoder:
             return L.zk_ingest_dev_spans_items(h, bp, op, n, codec, flags, C.byref(ab), C.byref(nout), C.byref(nrej),
                                                C.byref(it))
 
-        return self._run(call, n, snappy, strict, out, items, item_cap, span_names, indexed, client_rule, index_cap)
+        return self._run(call, n, snappy, strict, out, items, item_cap, span_names, indexed, client_rule, index_cap,
+                         annotated, row_cap, row_strings)
 
     def decode_device_many(self, batches, *, snappy: bool = True, strict: bool = True, out=None,
                            items: bool = False, item_cap: int | None = None, span_names: bool = False,
-                           indexed: bool = False, client_rule: bool = True, index_cap: int | None = None):
+                           indexed: bool = False, client_rule: bool = True, index_cap: int | None = None,
+                           annotated: bool = False, row_cap: int | None = None, row_strings: bool = True):
         """Several HBM-resident batches [(buf, offsets, n), ...] in ONE decode
-        (zk_ingest_dev_spans_multi, or zk_ingest_dev_spans_multi_indexed with indexed=True): the
-        results of decode_device over the batches joined in order, for one set of launches and one
-        host round trip."""
+        (zk_ingest_dev_spans_multi, zk_ingest_dev_spans_multi_indexed with indexed=True, or
+        zk_ingest_dev_spans_multi_annotated with annotated=True): the results of decode_device over
+        the batches joined in order, for one set of launches and one host round trip."""
+        _one_pass(indexed, annotated)
         L, h = self._L, self._h
         nb = len(batches)
         n = sum(int(b[2]) for b in batches)
@@ -315,17 +335,21 @@ class DeviceSpanDecoder:
         offs = (C.c_void_p * max(1, nb))(*[b[1].data_ptr() if int(b[2]) else None for b in batches])
         ns = (C.c_uint64 * max(1, nb))(*[int(b[2]) for b in batches])
 
-        def call(codec, flags, ab, nout, nrej, it, ix=None):
+        def call(codec, flags, ab, nout, nrej, it, ix=None, an=None):
+            if an is not None:
+                return L.zk_ingest_dev_spans_multi_annotated(h, nb, bufs, offs, ns, codec, flags, C.byref(ab), C.byref(nout),
+                                                             C.byref(nrej), None if it is None else C.byref(it), C.byref(an))
             if ix is not None:
                 return L.zk_ingest_dev_spans_multi_indexed(h, nb, bufs, offs, ns, codec, flags, C.byref(ab), C.byref(nout),
                                                            C.byref(nrej), None if it is None else C.byref(it), C.byref(ix))
             return L.zk_ingest_dev_spans_multi(h, nb, bufs, offs, ns, codec, flags, C.byref(ab), C.byref(nout),
                                                C.byref(nrej), None if it is None else C.byref(it))
 
-        return self._run(call, n, snappy, strict, out, items, item_cap, span_names, indexed, client_rule, index_cap)
+        return self._run(call, n, snappy, strict, out, items, item_cap, span_names, indexed, client_rule, index_cap,
+                         annotated, row_cap, row_strings)
 
     def _run(self, call, n, snappy, strict, out, items, item_cap, span_names=False, indexed=False, client_rule=True,
-             index_cap=None):
+             index_cap=None, annotated=False, row_cap=None, row_strings=True):
         import torch
 
         from .columns import DeviceColumns
@@ -338,13 +362,16 @@ class DeviceSpanDecoder:
         flags = (_abi.ZK_INGEST_STRICT if strict else 0) | (_abi.ZK_INGEST_SPAN_NAMES if span_names else 0)
         if indexed and not client_rule:
             flags |= _abi.ZK_INGEST_NO_CLIENT_RULE
-        if not items and not indexed:
+        if annotated and not row_strings:
+            flags |= _abi.ZK_INGEST_NO_ROW_STRINGS
+        if not items and not indexed and not annotated:
             self._check(call(codec, flags, ab, nout, nrej, None))
             cols.n = int(nout.value)
             return cols, int(nrej.value)
         cap = item_cap if item_cap is not None else 2 * n + 16
         icap = int(index_cap) if index_cap is not None else max(16, 8 * n)
-        it = ix = None
+        rcap = int(row_cap) if row_cap is not None else max(16, 8 * n)
+        it = ix = an = None
         while True:
             if items:
                 ks = torch.empty(cap, dtype=torch.int32, device=dev)
@@ -357,14 +384,21 @@ class DeviceSpanDecoder:
                 ent = [torch.empty(max(1, icap), dtype=torch.int32 if k == 0 else torch.int64, device=dev) for k in range(5)]
                 ix = _abi.zk_ingest_index_items(*[t.data_ptr() for t in ent], icap, 0)
                 st = call(codec, flags, ab, nout, nrej, it, ix)
+            elif annotated:
+                # (fresh tensors per decode: a store that observed the last ones may still read them)
+                row = [torch.empty(max(1, rcap), dtype=torch.int64 if k < 4 else torch.int32, device=dev) for k in range(7)]
+                an = _abi.zk_ingest_annotation_rows(*[t.data_ptr() for t in row], rcap, 0)
+                st = call(codec, flags, ab, nout, nrej, it, None, an)
             else:
                 st = call(codec, flags, ab, nout, nrej, it)
             if st == _abi.ZK_ERR_CAPACITY:
                 grow_items = items and (it.kv_n == cap or it.ann_n == cap)
                 grow_index = indexed and ix.n == icap
-                if grow_items or grow_index:  # more items / entries than guessed: the batch again
+                grow_rows = annotated and an.n == rcap
+                if grow_items or grow_index or grow_rows:  # more items / entries / rows than guessed: the batch again
                     cap = cap * 4 if grow_items else cap
                     icap = max(16, icap * 4) if grow_index else icap
+                    rcap = max(16, rcap * 4) if grow_rows else rcap
                     continue
             self._check(st)
             break
@@ -376,6 +410,10 @@ class DeviceSpanDecoder:
             from .annindex import DeviceAnnotationItems
 
             res += (DeviceAnnotationItems(*[t[: ix.n] for t in ent]),)
+        if annotated:
+            from .annotstore import DeviceAnnotationRows
+
+            res += (DeviceAnnotationRows(*[t[: an.n] for t in row]),)
         return res
 
     def index_stats(self) -> dict:
@@ -384,8 +422,15 @@ class DeviceSpanDecoder:
         self._check(self._L.zk_ingest_dev_index_stats(self._h, C.byref(ms), C.byref(sl)))
         return {"pass_ms": float(ms.value), "slices": int(sl.value)}
 
+    def rows_stats(self) -> dict:
+        """{"pass_ms", "slices"} of the last annotated decode's rows pass (zk_ingest_dev_rows_stats)."""
+        ms, sl = C.c_double(), C.c_uint64()
+        self._check(self._L.zk_ingest_dev_rows_stats(self._h, C.byref(ms), C.byref(sl)))
+        return {"pass_ms": float(ms.value), "slices": int(sl.value)}
+
     def string(self, h: int) -> str:
-        """The key / value string behind a hash an items batch has seen (zk_ingest_dev_string);
+        """The key / value string behind a hash an items batch has seen, or behind the value of a row
+        an annotated decode wrote with row_strings=True (zk_ingest_dev_string);
         memoised (a hash keeps the string first captured for it)."""
         h = int(h) & 0xFFFFFFFFFFFFFFFF
         memo = self.__dict__.setdefault("_strings", {})
@@ -401,7 +446,9 @@ class DeviceSpanDecoder:
 
     def decode(self, blobs: Sequence[bytes], *, snappy: bool = True, strict: bool = True, items: bool = False,
                span_names: bool = False, indexed: bool = False, client_rule: bool = True,
-               index_cap: int | None = None):
+               index_cap: int | None = None, annotated: bool = False, row_cap: int | None = None,
+               row_strings: bool = True):
+        _one_pass(indexed, annotated)
         import torch
 
         dev = f"cuda:{self.device}"
@@ -412,7 +459,8 @@ class DeviceSpanDecoder:
         buf = torch.from_numpy(raw.copy()).to(dev)
         off = torch.from_numpy(offsets).to(dev)
         return self.decode_device(buf, off, len(blobs), snappy=snappy, strict=strict, items=items,
-                                  span_names=span_names, indexed=indexed, client_rule=client_rule, index_cap=index_cap)
+                                  span_names=span_names, indexed=indexed, client_rule=client_rule, index_cap=index_cap,
+                                  annotated=annotated, row_cap=row_cap, row_strings=row_strings)
 
     @property
     def num_services(self) -> int:

@@ -503,6 +503,7 @@ class TraceSpanStore:
         self.device = device
         self.services = None if services is None else list(services)
         self.span_names = None if span_names is None else list(span_names)
+        self._held = None  # device record columns a queued observe may still read (TraceAnnotationStore.observe_stored)
 
     def _check(self, st: int) -> None:
         if st != _abi.ZK_OK:
@@ -569,6 +570,7 @@ class TraceSpanStore:
         """{"entries", "segments", "bytes"} (zk_sp_info); synchronises."""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self._L.zk_sp_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        self._held = None  # (synchronised: the columns of a queued observe are consumed)
         return {"entries": int(a.value), "segments": int(b.value), "bytes": int(c.value)}
 
     # ---- reading ---------------------------------------------------------------------------------------
