@@ -293,6 +293,94 @@ zk_status   zk_an_expire_ms(zk_an* an, double out[3]);
 zk_status   zk_an_adjusted_summaries(zk_an* an, zk_sp* sp, const uint64_t* ids, uint32_t n, uint32_t flags,
                                      zk_sp_summary* heads, zk_sp_span_ts* out, uint64_t cap, uint64_t* n_out);
 
+/* ---- time-skew-adjusted traces (the second joint call) --------------------------------------------------- */
+
+/* zk_an_adjusted_traces' head of one asked id, 56 bytes: zk_sp_trace's fields with the same meaning, over the
+   ADJUSTED trace, and the trace's entries in the row columns */
+typedef struct zk_an_trace {
+    uint64_t trace_id;   /* the asked id; 0 when the span store lacks it (the whole head is zeros then) */
+    int64_t  start;      /* the minimum first and the maximum last over the timed spans of the adjusted trace */
+    int64_t  end;
+    uint64_t root_most;  /* the span id of getRootMostSpan over the adjusted trace; 0 when spans == 0 */
+    uint32_t fragments;  /* the span store's rows of the trace */
+    uint32_t spans;      /* its entries in the span column */
+    uint32_t services;   /* its entries in the services column */
+    uint32_t state;      /* ZK_SP_TR_FOUND, ZK_SP_TR_TIMED, ZK_SP_TR_OVERFLOW, ZK_AN_ADJ_ANNOTATED, ZK_AN_ADJ_OVERFLOW */
+    uint32_t rows;       /* its entries in the row columns, injected ones included */
+    uint32_t reserved;   /* 0 */
+} zk_an_trace;
+
+/* one span of an adjusted trace, 56 bytes: zk_sp_span's fields under the same names, then */
+typedef struct zk_an_span {
+    uint64_t span_id;
+    uint64_t parent_id;
+    int64_t  first;      /* 0 when untimed */
+    int64_t  last;
+    uint32_t name;
+    uint32_t depth;
+    uint32_t services;
+    uint32_t bits;       /* ZK_SP_SPAN_* */
+    uint32_t rows;       /* the span's entries in the row columns, injected ones included */
+    uint32_t injected;   /* 0, or 2: the sr and ss of a client-only span, its last two rows */
+} zk_an_span;
+
+/* getTraceCombosByIds / getTraceTimelinesByIds / getTracesByIds with Adjust.TimeSkew, on the device: the asked
+   traces as the reference's TimeSkewAdjuster leaves them, with every span's annotations. The adjuster's rules
+   are zk_an_adjusted_summaries' above (merged spans, span times, SPAN ORDER, root, the walk, skew, a shift);
+   this call emits what that one drops. Per asked id, as a function of both stores' multisets alone:
+     spans     the surviving spans in the adjusted span order. first and last from their lists again (a span
+               without rows keeps its record times; 0 when untimed); name and services are zk_sp_traces';
+               ZK_SP_SPAN_TIMED when the span has rows or a timed fragment; ZK_SP_SPAN_HAS_PARENT unchanged;
+               ZK_SP_SPAN_PARENT_FOUND when the parent is a span of the ADJUSTED trace. The services column
+               holds the survivors' service ids in the same order, ascending per span.
+     rows      per span in that order its rows in CANONICAL ORDER (a shift never reorders a list): ts is the
+               adjusted value, every other column as stored. Rows of pruned spans, and rows whose span_id is no
+               span of the trace, are not emitted.
+     injected  a CLIENT-ONLY span (the walk, 2.) gets the reference's two injected annotations behind its own
+               rows, sr then ss: ts = the span's first cs (sr) / first cr (ss) after the handed-down shift,
+               value = zk_hash_string("sr") / ("ss"), the kind SR / SS, and the host the whole endpoint of the
+               first cs or cr in the first child's list (ipv4, port, service_id, ZK_AN_HAS_HOST); without such
+               a host ipv4 = service_id = 0 and bits = the kind alone. They never move the span's first or last.
+     annotated, with a root      root_most is the root, depth the walk's level (the root 1), and the root
+               carries ZK_SP_SPAN_ROOT_MOST.
+     annotated, every span with a parent   nothing is shifted, pruned or injected: all spans in the
+               annotation-derived span order with all rows of known spans. root_most and depth are zk_sp_traces'
+               rules (root-most, depth) over THAT order: from the first span up through the parents the trace
+               holds, ending where the chain would repeat; then level by level down the children, a span
+               reached twice keeping its first depth.
+     not annotated   zk_sp_traces' answer span for span, rows = 0; ZK_SP_TR_OVERFLOW stays beside
+               ZK_AN_ADJ_OVERFLOW if it was set.
+     overflow  more than ZK_SP_TRACE_MAX_ROWS fragments or more than ZK_AN_ADJ_MAX_ROWS rows: ZK_AN_ADJ_OVERFLOW,
+               spans = services = rows = 0 and nothing emitted; fragments, FOUND and ANNOTATED are exact (an
+               annotated one has start = end = 0 and TIMED clear, as above).
+   Arguments:
+     an, sp, ids, n, flags   as for zk_an_adjusted_summaries.
+     heads     n HOST structs in the order asked; a duplicated id is answered as often as asked; an id the span
+               store lacks gets a head of zeros.
+     spans, services, rows   HOST outputs of cap_spans, cap_services, cap_rows entries: the traces one after
+               another in the order asked. All seven row columns are written (trace_id is the asked id). Each
+               may be NULL (rows: or any of its columns) only with its cap at 0.
+     totals    the totals of spans, services and rows.
+   When any capacity is short the call returns ZK_ERR_CAPACITY with totals set and the heads written; no span,
+   service or row is written. All caps 0 with NULL outputs is the sizing call. NULL handles or arguments and
+   n > ZK_AN_MAX_IDS are refused before any device is touched; n == 0 is ZK_OK. An empty annotation store hands
+   the call to zk_sp_traces (rows = 0 in every head).
+   The passes are zk_an_adjusted_summaries', with k_an_adjust's emitting instantiation: behind the second span
+   order a prefix sum over the sorted positions of (rows + injected) and of services places every survivor's
+   rows and pairs; the spans are written a thread per position; the rows are written with all threads of the
+   workgroup striding over the OUTPUT rows, each finding its span by binary search over the spans' row
+   offsets (kept in LDS fields that are dead behind the walk: the budget stays 159,808 B at both bounds);
+   value and service_id come from the staged rows in HBM. A trace emits at most A + 2 S rows (A its rows, S
+   its spans): the row staging holds the sum of that over the asked traces, and a trace's rows lie at its row
+   base plus twice its span base; spans and pairs lie at its base in the span store's numbering. The heads
+   (56 B per id) are copied and the call synchronises; if all three outputs fit, one copy per output follows
+   and each is packed per trace on the host. zk_an_query_ms / zk_sp_query_ms as for the summaries call.
+   Staging is grown on use; a refused allocation is ZK_ERR_CAPACITY. Synchronises. */
+zk_status   zk_an_adjusted_traces(zk_an* an, zk_sp* sp, const uint64_t* ids, uint32_t n, uint32_t flags,
+                                  zk_an_trace* heads, zk_an_span* spans, uint64_t cap_spans,
+                                  uint32_t* services, uint64_t cap_services, zk_an_cols* rows, uint64_t cap_rows,
+                                  uint64_t totals[3] /* spans, services, rows */);
+
 #ifdef __cplusplus
 }
 #endif

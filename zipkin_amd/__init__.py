@@ -4,7 +4,8 @@ The compute lives in libzkagg.so (HIP, gfx950) behind the C ABI of include/zkagg
 binds it (ctypes) and mirrors the reference's Aggregates store surface for the host side.
 """
 from ._abi import ZkError, ZkLibraryError  # noqa: F401
-from .columns import BYTES_PER_RECORD, DeviceColumns, SpanColumns, tracegen_host, tracegen_params  # noqa: F401
+from .columns import (ADJUSTED_TRACE_HEAD, ADJUSTED_TRACE_SPAN, BYTES_PER_RECORD, DeviceColumns, SpanColumns,  # noqa: F401
+                      tracegen_host, tracegen_params)
 from .context import DepsContext, LinkTable  # noqa: F401
 from .realtime import LinkHistogram, LinkHistogramSnapshot  # noqa: F401
 from .durations import TraceDurationIndex, TraceIdDuration, merge_top  # noqa: F401
@@ -55,6 +56,8 @@ __all__ = [
     "TraceCombo",
     "TraceAnnotationStore",
     "ADJUSTED_HEAD",
+    "ADJUSTED_TRACE_HEAD",
+    "ADJUSTED_TRACE_SPAN",
     "ADJ_ANNOTATED",
     "ADJ_OVERFLOW",
     "AnnotationRows",

@@ -478,6 +478,36 @@ class zk_an_cols(C.Structure):
     ]
 
 
+class zk_an_trace(C.Structure):
+    _fields_ = [
+        ("trace_id", C.c_uint64),
+        ("start", C.c_int64),
+        ("end", C.c_int64),
+        ("root_most", C.c_uint64),
+        ("fragments", C.c_uint32),
+        ("spans", C.c_uint32),
+        ("services", C.c_uint32),
+        ("state", C.c_uint32),
+        ("rows", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class zk_an_span(C.Structure):
+    _fields_ = [
+        ("span_id", C.c_uint64),
+        ("parent_id", C.c_uint64),
+        ("first", C.c_int64),
+        ("last", C.c_int64),
+        ("name", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("services", C.c_uint32),
+        ("bits", C.c_uint32),
+        ("rows", C.c_uint32),
+        ("injected", C.c_uint32),
+    ]
+
+
 ZK_CODEC_THRIFT = 0
 ZK_CODEC_SNAPPY_THRIFT = 1
 ZK_INGEST_STRICT = 1
@@ -782,6 +812,8 @@ _SIGNATURES = [
     ("zk_an_expire", C.c_int, [_P, C.c_int64, _P, _P, C.c_uint32, _U64P]),
     ("zk_an_expire_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_an_adjusted_summaries", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, C.POINTER(zk_sp_span_ts), C.c_uint64, _U64P]),
+    ("zk_an_adjusted_traces", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint64, _P, C.c_uint64,
+                                        C.POINTER(zk_an_cols), C.c_uint64, _U64P]),
 ]
 
 SYMBOLS = [s[0] for s in _SIGNATURES]

@@ -15,7 +15,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi
-from .columns import ENTRY_COLUMNS, SUMMARY_HEAD
+from .columns import ADJUSTED_TRACE_HEAD, ADJUSTED_TRACE_SPAN, ENTRY_COLUMNS, SUMMARY_HEAD
 
 _M64 = 2 ** 64 - 1
 
@@ -322,6 +322,28 @@ class TraceAnnotationStore:
                                                          total.value, C.byref(total)))
         return heads, cols
 
+    def adjusted_traces(self, spans, ids):
+        """(heads, spans, services, rows) for at most ZK_AN_MAX_IDS ids (zk_an_adjusted_traces): the asked traces
+        after the time-skew adjuster, with every span's annotations, joined on the device from this store's rows
+        and `spans`, a TraceSpanStore on the same device. heads: an ADJUSTED_TRACE_HEAD array in the order
+        asked; spans: an ADJUSTED_TRACE_SPAN array, the traces one after another, each in its adjusted span
+        order; services: the spans' service ids, a uint32 column; rows: AnnotationRows, per span in that order
+        its annotations in list order, the injected sr / ss of a client-only span behind its own. The sizing
+        call, then the call that fills."""
+        keep, ptr, n, flags = self._ask(ids)
+        heads = np.zeros(n, ADJUSTED_TRACE_HEAD)
+        totals = (C.c_uint64 * 3)()
+        st = self._L.zk_an_adjusted_traces(self._h, spans._h, ptr, n, flags, heads.ctypes.data, None, 0, None, 0, None, 0, totals)
+        if st not in (_abi.ZK_OK, _abi.ZK_ERR_CAPACITY):
+            self._check(st)
+        out_spans, services = np.zeros(totals[0], ADJUSTED_TRACE_SPAN), np.zeros(totals[1], np.uint32)
+        rows = AnnotationRows.empty(totals[2])
+        if st == _abi.ZK_ERR_CAPACITY:
+            ab = rows.abi()
+            self._check(self._L.zk_an_adjusted_traces(self._h, spans._h, ptr, n, flags, heads.ctypes.data, out_spans.ctypes.data,
+                                                      len(out_spans), services.ctypes.data, len(services), C.byref(ab), len(rows), totals))
+        return heads, out_spans, services, rows
+
     # ---- timing ----------------------------------------------------------------------------------------
     def observe_ms(self) -> dict:
         """Device time (ms) of the passes of the last observe (zk_an_observe_ms; timing=True)."""
@@ -336,7 +358,7 @@ class TraceAnnotationStore:
         return dict(zip(self.EXPIRE_PHASES, out))
 
     def query_ms(self) -> float:
-        """Time (ms) on the handle's stream of the last gather or adjusted_summaries (zk_an_query_ms;
+        """Time (ms) on the handle's stream of the last gather, adjusted_summaries or adjusted_traces (zk_an_query_ms;
         timing=True)."""
         ms = C.c_double()
         self._check(self._L.zk_an_query_ms(self._h, C.byref(ms)))

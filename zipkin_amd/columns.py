@@ -29,6 +29,15 @@ SUMMARY_HEAD = np.dtype([("trace_id", np.uint64), ("start", np.int64), ("end", n
                          ("spans", np.uint32), ("span_ts", np.uint32), ("state", np.uint32)])
 ENTRY_COLUMNS = (("service_id", np.uint32), ("first", np.int64), ("last", np.int64))
 
+# zk_an_trace, the 56-byte head of one asked id (zk_an_adjusted_traces), and zk_an_span, one span of an adjusted
+# trace (56 bytes): zk_sp_trace's and zk_sp_span's fields under the same names, then the row counts
+ADJUSTED_TRACE_HEAD = np.dtype([("trace_id", np.uint64), ("start", np.int64), ("end", np.int64), ("root_most", np.uint64),
+                                ("fragments", np.uint32), ("spans", np.uint32), ("services", np.uint32), ("state", np.uint32),
+                                ("rows", np.uint32), ("reserved", np.uint32)])
+ADJUSTED_TRACE_SPAN = np.dtype([("span_id", np.uint64), ("parent_id", np.uint64), ("first", np.int64), ("last", np.int64),
+                                ("name", np.uint32), ("depth", np.uint32), ("services", np.uint32), ("bits", np.uint32),
+                                ("rows", np.uint32), ("injected", np.uint32)])
+
 
 @dataclass
 class SpanColumns:

@@ -45,6 +45,7 @@
 #include "zk_sp_staged.h"
 #include "zk_tracegen.h"
 #include "zkannots.h"
+#include "zkingest.h"
 
 namespace zk {
 namespace {
@@ -539,8 +540,14 @@ struct zk_an {
     void* rows = nullptr;    // the write pass's rows, seven columns
     void* adj = nullptr;     // the adjusted summaries' block: the heads, then the work lists (kAdjBytes)
     void* adj_ents = nullptr;  // their entries at the span store's row bases: first, last [8 B], service [4 B]
+    void* adjt = nullptr;      // the adjusted traces' block: the heads (56 B), then the work lists (kAdjtBytes)
+    void* adjt_spans = nullptr;  // their spans (56 B) at the span store's row bases
+    void* adjt_svc = nullptr;    // their (span, service) pairs at the same bases
+    void* adjt_rows = nullptr;   // their rows, six columns (the trace id is the asked one): a trace at its row base + 2 x its span base
     size_t stage_bytes = 0, mplan_bytes = 0, rows_bytes = 0, adj_ents_bytes = 0;
+    size_t adjt_spans_bytes = 0, adjt_svc_bytes = 0, adjt_rows_bytes = 0;
     std::vector<uint8_t> adj_traces_host, adj_heads_host, adj_ents_host;
+    std::vector<uint8_t> adjt_heads_host, adjt_spans_host, adjt_svc_host, adjt_rows_host;
     std::vector<uint32_t> adj_counts_host, adj_list_host;
     std::vector<uint32_t> counts_host, cursor_host, off_host;  // (queued copies read the last two: they change only behind a synchronisation)
     std::vector<uint32_t> mplan_host, moff_host;
@@ -920,7 +927,8 @@ zk_status zk_an_destroy(zk_an* h) {
         (void)hipSetDevice(h->device);
         if (h->stream) (void)hipStreamSynchronize(h->stream);
         free_segments(h);
-        for (void* p : {h->obs, h->stage, h->mplan, h->q, h->rows, h->xplan, h->adj, h->adj_ents})
+        for (void* p : {h->obs, h->stage, h->mplan, h->q, h->rows, h->xplan, h->adj, h->adj_ents, h->adjt, h->adjt_spans,
+                        h->adjt_svc, h->adjt_rows})
             if (p) (void)hipFree(p);
         for (hipEvent_t e : h->oev)
             if (e) (void)hipEventDestroy(e);
@@ -1227,6 +1235,14 @@ zk_status zk_an_query_ms(zk_an* h, double* ms) {
 //                 entries. Every store is bounded: a trace that does not fit the launch's caps or whose
 //                 stagings end before it is left alone (its head stays zero), and an entry at or past the
 //                 trace's (span, service) pairs or the staging's end is dropped.
+//                 The EMITTING instantiation (In = AdjEmitIn, zk_an_adjusted_traces) shares steps 1 to 7 and then
+//                 writes the adjusted trace itself: for a trace without a parentless span the root-most span (one
+//                 lane up the parents) and the depths (the walk's rounds without a shift); prefix sums over the
+//                 sorted positions of every survivor's rows (its own and the two injected ones of a client-only
+//                 span) and services; the spans and pairs a thread per position; the rows with all threads
+//                 striding over the OUTPUT rows, each finding its span by binary search over the row offsets,
+//                 which lie in LDS fields the walk has left dead. The summaries instantiation compiles to what
+//                 it was before the template parameter.
 namespace zk {
 namespace {
 
@@ -1274,6 +1290,24 @@ struct AdjIn {
     uint32_t* o_svc;
     long long* o_first;
     long long* o_last;
+    static constexpr bool kEmit = false;
+};
+
+// k_an_adjust's emitting instantiation (zk_an_adjusted_traces): the same inputs, and the adjusted trace's spans,
+// pairs and rows. heads, o_svc, o_first and o_last of the base are not used.
+struct AdjEmitIn : AdjIn {
+    zk_an_trace* e_heads;
+    zk_an_span* e_spans;                    // [t_total]: a trace's spans at its base in the span store's numbering
+    uint32_t* e_svc;                        // [t_total]: its pairs at the same base
+    unsigned long long* e_span;             // the rows, six columns of e_n entries: a trace's at base[q] + 2 * t_base[q]
+    long long* e_ts;
+    unsigned long long* e_val;
+    uint32_t* e_ip;
+    uint32_t* e_rsvc;
+    uint32_t* e_bits;
+    unsigned long long e_n;
+    unsigned long long h_sr, h_ss;          // zk_hash_string("sr"), ("ss"): the injected rows' values
+    static constexpr bool kEmit = true;
 };
 
 // a bitonic sort of ord[0, P) (P a power of two >= 2, the same for the whole workgroup). Ends behind a barrier.
@@ -1326,8 +1360,9 @@ __device__ inline bool adj_skew(long long cs, long long cr, long long sr, long l
     return true;
 }
 
-template <int T>
-__global__ __launch_bounds__(T) void k_an_adjust(AdjIn in) {
+template <int T, class In>
+__global__ __launch_bounds__(T) void k_an_adjust(In in) {
+    constexpr bool EMIT = In::kEmit;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_adj[];
     uint32_t* s_cnt = (uint32_t*)s_adj;  // [0] the root's position, [1] a level's visits, [2] timed, [3] the survivors, [4..7] the scan's waves
     unsigned long long* s_lo = (unsigned long long*)(s_adj + 32);
@@ -1535,12 +1570,14 @@ __global__ __launch_bounds__(T) void k_an_adjust(AdjIn in) {
                         // client-only: the endpoint is the host of the first cs or cr of the first child's list
                         const uint32_t kid = f_ord[f_fc[i]];
                         uint32_t bits = kAdjGiveClient;
+                        if constexpr (EMIT) f_pos[i] = (uint16_t)kAdjNone16;  // (dead behind step 4: the row that gives the injected rows' host)
                         for (uint32_t k = 0; k < f_len[kid]; ++k) {
                             const uint32_t r = r_ord[(uint32_t)f_run[kid] + k], b = r_bits[r], kind = b & ZK_AN_KIND_MASK;
                             if (kind == ZK_AN_KIND_CS || kind == ZK_AN_KIND_CR) {
                                 if (b & ZK_AN_HAS_HOST) {
                                     bits |= kAdjGiveEp;
                                     f_gip[i] = r_ip[r];
+                                    if constexpr (EMIT) f_pos[i] = (uint16_t)r;
                                 }
                                 break;
                             }
@@ -1592,6 +1629,170 @@ __global__ __launch_bounds__(T) void k_an_adjust(AdjIn in) {
             if (f_first[a] != f_first[b]) return f_first[a] < f_first[b];
             return f_rank[a] < f_rank[b];
         });
+    }
+    if constexpr (EMIT) {
+        // 8e. the emitting instantiation: the adjusted trace itself instead of its summary
+        uint32_t rm = kAdjNone;  // the root-most span of an annotated trace
+        if (has_root) {
+            // the root: the one span the walk visited at level 1 (behind step 7 it need not be the first)
+            __syncthreads();
+            for (uint32_t i = threadIdx.x; i < S; i += T)
+                if (f_depth[i] == 1) s_cnt[0] = i;
+            __syncthreads();
+            rm = s_cnt[0];
+        } else if (annotated) {
+            // every span has a parent: getRootMostSpan and toSpanDepths over the annotation-derived span order.
+            // One lane walks up from the first span through the parents the trace holds, to where the chain
+            // would repeat (f_depth marks the spans met); then the levels go down as in step 5, with no shift.
+            __syncthreads();  // (every thread has read s_cnt[0] for has_root)
+            if (threadIdx.x == 0) {
+                uint32_t s = f_ord[0];
+                for (uint32_t step = 0; step < S; ++step) {
+                    const uint32_t par = f_par[s];
+                    if (par == kAdjNone16 || f_depth[s] != 0) break;
+                    f_depth[s] = 1;
+                    s = par;
+                }
+                s_cnt[0] = s;
+            }
+            __syncthreads();
+            rm = s_cnt[0];
+            for (uint32_t i = threadIdx.x; i < S; i += T) f_depth[i] = 0;
+            __syncthreads();
+            for (uint32_t level = 1; level <= S; ++level) {
+                bool did = false;
+                for (uint32_t i = threadIdx.x; i < S; i += T) {
+                    const uint32_t par = f_par[i];
+                    if (level == 1 ? i != rm : (f_depth[i] != 0 || par == kAdjNone16 || par == i || f_depth[par] != level - 1)) continue;
+                    f_depth[i] = (uint16_t)level;
+                    did = true;
+                }
+                if (did) s_cnt[1] = 1u;
+                __syncthreads();
+                const bool any = s_cnt[1] != 0u;
+                __syncthreads();
+                if (!any) break;  // (the same for the whole workgroup)
+                if (threadIdx.x == 0) s_cnt[1] = 0u;
+                __syncthreads();
+            }
+        }
+        // the head's reductions, and every survivor's place in the rows and in the pairs: prefix sums over the
+        // sorted positions, consecutive ones per thread (the survivors are the first positions)
+        const uint32_t C = (S + T - 1) / T, p0 = threadIdx.x * C;
+        uint32_t n_rows = 0u, n_svc = 0u, kept = 0u, rows_all = 0u, svc_all = 0u;
+        unsigned long long lo = kAnNone, hi = 0ull;
+        bool timed_any = false;
+        for (uint32_t p = p0; p < p0 + C && p < S; ++p) {
+            const uint32_t i = f_ord[p];
+            if (has_root && f_depth[i] == 0) continue;
+            ++kept;
+            n_rows += (uint32_t)f_len[i] + ((f_bits[i] & kAdjGiveClient) ? 2u : 0u);
+            n_svc += spans[i].services;
+            if (f_bits[i] & kAdjTimed) {
+                lo = f_first[i] < lo ? f_first[i] : lo;
+                hi = f_last[i] > hi ? f_last[i] : hi;
+                timed_any = true;
+            }
+        }
+        if (kept) atomicAdd(&s_cnt[3], kept);
+        if (timed_any) {
+            atomicMin(s_lo, lo);
+            atomicMax(s_hi, hi);
+            atomicOr(&s_cnt[2], 1u);
+        }
+        uint32_t r_at = adj_scan<T>(n_rows, s_cnt + 4, &rows_all);
+        uint32_t v_at = adj_scan<T>(n_svc, s_cnt + 4, &svc_all);
+        // (f_fc and f_gip are dead behind the walk: by POSITION now, the span's first output row and first pair)
+        for (uint32_t p = p0; p < p0 + C && p < S; ++p) {
+            const uint32_t i = f_ord[p];
+            if (has_root && f_depth[i] == 0) continue;
+            f_fc[p] = r_at;
+            f_gip[p] = v_at;
+            r_at += (uint32_t)f_len[i] + ((f_bits[i] & kAdjGiveClient) ? 2u : 0u);
+            v_at += spans[i].services;
+        }
+        __syncthreads();
+        const uint32_t K = s_cnt[3] <= S ? s_cnt[3] : S;
+        const uint32_t R = rows_all <= A + 2u * S ? rows_all : A + 2u * S;  // (a trace's share of the row staging)
+        const uint32_t V = svc_all <= th.services ? svc_all : th.services;
+        // the spans and their pairs, a thread per position
+        for (uint32_t p = threadIdx.x; p < K; p += T) {
+            const uint32_t i = f_ord[p];
+            const zk_sp_span sp = spans[i];
+            const bool timed = f_bits[i] & kAdjTimed;
+            const uint32_t inj = (f_bits[i] & kAdjGiveClient) ? 2u : 0u;
+            zk_an_span o;
+            o.span_id = sp.span_id;
+            o.parent_id = sp.parent_id;
+            o.first = timed ? (long long)(f_first[i] ^ kAnSign) : 0;
+            o.last = timed ? (long long)(f_last[i] ^ kAnSign) : 0;
+            o.name = sp.name;
+            o.services = sp.services;
+            if (annotated) {
+                o.depth = f_depth[i];
+                o.bits = (sp.bits & ZK_SP_SPAN_HAS_PARENT) | (timed ? ZK_SP_SPAN_TIMED : 0u) |
+                         (f_par[i] != kAdjNone16 ? ZK_SP_SPAN_PARENT_FOUND : 0u) | (i == rm ? ZK_SP_SPAN_ROOT_MOST : 0u);
+            } else {  // zk_sp_traces' span as it is
+                o.depth = sp.depth;
+                o.bits = sp.bits;
+            }
+            o.rows = (uint32_t)f_len[i] + inj;
+            o.injected = inj;
+            if (sb0 + p < in.t_total) in.e_spans[sb0 + p] = o;
+            const uint32_t to = f_gip[p], from = f_svo[i];
+            for (uint32_t k = 0; k < sp.services; ++k)
+                if (to + k < V && from + k < th.services && sb0 + to + k < in.t_total) in.e_svc[sb0 + to + k] = in.t_svc[sb0 + from + k];
+        }
+        // the rows: all threads stride over the OUTPUT rows; a row finds its span by binary search over the offsets
+        const unsigned long long rb0 = ab0 + 2ull * sb0;
+        for (uint32_t o = threadIdx.x; o < R; o += T) {
+            uint32_t a = 0, z = K;
+            while (a < z) {
+                const uint32_t mid = (a + z) >> 1;
+                if (f_fc[mid] <= o) a = mid + 1; else z = mid;
+            }
+            const unsigned long long e = rb0 + o;
+            if (a == 0 || e >= in.e_n) continue;
+            const uint32_t p = a - 1, i = f_ord[p], k = o - f_fc[p], len = f_len[i];
+            if (k < len) {
+                const uint32_t r = r_ord[(uint32_t)f_run[i] + k];
+                in.e_span[e] = r_span[r];
+                in.e_ts[e] = (long long)(r_ts[r] ^ kAnSign);
+                in.e_val[e] = in.rows.val[ab0 + r];
+                in.e_ip[e] = r_ip[r];
+                in.e_rsvc[e] = in.rows.svc[ab0 + r];
+                in.e_bits[e] = r_bits[r];
+            } else if (k < len + 2u && (f_bits[i] & kAdjGiveClient)) {
+                // an injected row: sr at the span's first cs, ss at its first cr, on the lead's endpoint
+                const unsigned long long g = f_give[i];
+                const bool sr = k == len;
+                const uint32_t at = sr ? (uint32_t)(g & 0xFFFFu) : (uint32_t)(g >> 16) & 0xFFFFu, lead = f_pos[i];
+                const uint32_t kind = sr ? ZK_AN_KIND_SR : ZK_AN_KIND_SS;
+                const bool hosted = lead < A;
+                in.e_span[e] = spans[i].span_id;
+                in.e_ts[e] = (long long)(r_ts[r_ord[at < A ? at : 0u]] ^ kAnSign);
+                in.e_val[e] = sr ? in.h_sr : in.h_ss;
+                in.e_ip[e] = hosted ? r_ip[lead] : 0u;
+                in.e_rsvc[e] = hosted ? in.rows.svc[ab0 + lead] : 0u;
+                in.e_bits[e] = hosted ? (kind | ZK_AN_HAS_HOST | (r_bits[lead] & (0xFFFFu << ZK_AN_PORT_SHIFT))) : kind;
+            }
+        }
+        if (threadIdx.x == 0) {
+            zk_an_trace hd;
+            const bool timed = s_cnt[2] != 0u;
+            hd.trace_id = in.ids[q];
+            hd.start = timed ? (long long)(*s_lo ^ kAnSign) : 0;
+            hd.end = timed ? (long long)(*s_hi ^ kAnSign) : 0;
+            hd.root_most = !annotated ? th.root_most : rm < S ? spans[rm].span_id : 0ull;
+            hd.fragments = th.fragments;
+            hd.spans = K;
+            hd.services = V;
+            hd.state = ZK_SP_TR_FOUND | (timed ? ZK_SP_TR_TIMED : 0u) | (annotated ? ZK_AN_ADJ_ANNOTATED : 0u);
+            hd.rows = R;
+            hd.reserved = 0u;
+            in.e_heads[q] = hd;
+        }
+        return;
     }
     // (not annotated: f_ord is still the spans' own order, which zk_sp_traces made)
     // 8. the head's reductions and the entries' places over the sorted positions, consecutive ones per thread
@@ -1769,12 +1970,12 @@ extern "C" zk_status zk_an_adjusted_summaries(zk_an* h, zk_sp* sp, const uint64_
     in.o_first = (long long*)h->adj_ents;
     in.o_last = (long long*)((uint8_t*)h->adj_ents + e8);
     in.o_svc = (uint32_t*)((uint8_t*)h->adj_ents + 2 * e8);
-    AN_HIP(h, launch_checked("k_an_adjust (a wave per trace)", k_an_adjust<kAdjWave>, dim3(n_wave), dim3(kAdjWave),
+    AN_HIP(h, launch_checked("k_an_adjust (a wave per trace)", k_an_adjust<kAdjWave, AdjIn>, dim3(n_wave), dim3(kAdjWave),
                              adj_lds(kAdjWave, kAdjWave), h->stream, in));
     in.list += n_wave;
     in.cap_spans = big_spans;
     in.cap_rows = big_rows;
-    AN_HIP(h, launch_checked("k_an_adjust (a workgroup per trace)", k_an_adjust<kAnWG>, dim3(n_group), dim3(kAnWG),
+    AN_HIP(h, launch_checked("k_an_adjust (a workgroup per trace)", k_an_adjust<kAnWG, AdjIn>, dim3(n_group), dim3(kAnWG),
                              adj_lds(big_spans, big_rows), h->stream, in));
     // only the heads cross before the entries' total is known
     h->adj_heads_host.resize((size_t)n * sizeof(zk_sp_summary));
@@ -1810,6 +2011,252 @@ extern "C" zk_status zk_an_adjusted_summaries(zk_an* h, zk_sp* sp, const uint64_
         memcpy(out->first + at, s_first + from, c * 8);
         memcpy(out->last + at, s_last + from, c * 8);
         at += c;
+    }
+    return ZK_OK;
+    ZK_GUARD_END
+}
+
+// ---- time-skew-adjusted traces (zk_an_adjusted_traces) ------------------------------------------------------
+namespace zk {
+namespace {
+
+// the block: the heads (56 B), then the work list
+constexpr size_t kAdjtListAt = (size_t)ZK_AN_MAX_IDS * sizeof(zk_an_trace);
+constexpr size_t kAdjtBytes = kAdjtListAt + (size_t)ZK_AN_MAX_IDS * 4;
+
+static_assert(sizeof(zk_an_trace) == 56 && sizeof(zk_an_span) == 56, "the ABI's layouts");
+static_assert(offsetof(zk_an_trace, rows) == sizeof(zk_sp_trace) && offsetof(zk_an_span, rows) == sizeof(zk_sp_span),
+              "zk_sp_trace and zk_sp_span are the first 48 bytes");
+static_assert(ZK_SP_TR_FOUND == ZK_SP_SUM_FOUND && ZK_SP_TR_TIMED == ZK_SP_SUM_TIMED && ZK_SP_TR_OVERFLOW == ZK_SP_SUM_OVERFLOW &&
+                  (ZK_AN_ADJ_ANNOTATED & (ZK_SP_TR_FOUND | ZK_SP_TR_TIMED | ZK_SP_TR_OVERFLOW)) == 0 &&
+                  (ZK_AN_ADJ_OVERFLOW & (ZK_SP_TR_FOUND | ZK_SP_TR_TIMED | ZK_SP_TR_OVERFLOW | ZK_AN_ADJ_ANNOTATED)) == 0,
+              "the ZK_AN_ADJ_* bits lie beside the ZK_SP_TR_* ones");
+
+// the head of a trace that zk_sp_traces answered alone: its 48 bytes, no rows
+zk_an_trace adjt_head_of(const zk_sp_trace& t) {
+    zk_an_trace hd;
+    memset(&hd, 0, sizeof hd);
+    memcpy(&hd, &t, sizeof t);
+    if (hd.state & ZK_SP_TR_OVERFLOW) hd.state |= ZK_AN_ADJ_OVERFLOW;
+    return hd;
+}
+
+// An empty annotation store: every answer is zk_sp_traces' own, span for span.
+zk_status adjt_plain(zk_an* h, zk_sp* sp, const uint64_t* ids, uint32_t n, uint32_t flags, zk_an_trace* heads, zk_an_span* spans,
+                     uint64_t cap_spans, uint32_t* services, uint64_t cap_services, uint64_t totals[3]) {
+    h->adj_traces_host.resize((size_t)n * sizeof(zk_sp_trace));
+    zk_sp_trace* th = (zk_sp_trace*)h->adj_traces_host.data();
+    uint64_t t_out[2] = {0, 0};
+    zk_status st = zk_sp_traces(sp, ids, n, flags, th, nullptr, 0, nullptr, 0, t_out);
+    if (st != ZK_OK && st != ZK_ERR_CAPACITY) return afail(h, st, zk_sp_last_error(sp));
+    for (uint32_t i = 0; i < n; ++i) heads[i] = adjt_head_of(th[i]);
+    totals[0] = t_out[0];
+    totals[1] = t_out[1];
+    if (t_out[0] > cap_spans || t_out[1] > cap_services)
+        return afail(h, ZK_ERR_CAPACITY, "an output holds fewer entries than the asked traces have");
+    if (st == ZK_OK) return ZK_OK;  // (nothing to emit)
+    h->adjt_spans_host.resize((size_t)t_out[0] * sizeof(zk_sp_span));
+    h->adjt_svc_host.resize((size_t)t_out[1] * 4 + 4);
+    zk_sp_span* ts = (zk_sp_span*)h->adjt_spans_host.data();
+    st = zk_sp_traces(sp, ids, n, flags, th, ts, t_out[0], (uint32_t*)h->adjt_svc_host.data(), t_out[1], t_out);
+    if (st != ZK_OK) return afail(h, st, zk_sp_last_error(sp));
+    for (uint64_t k = 0; k < t_out[0]; ++k) {
+        zk_an_span o;
+        memset(&o, 0, sizeof o);
+        memcpy(&o, &ts[k], sizeof ts[k]);
+        spans[k] = o;
+    }
+    if (t_out[1]) memcpy(services, h->adjt_svc_host.data(), (size_t)t_out[1] * 4);
+    return ZK_OK;
+}
+
+}  // namespace
+}  // namespace zk
+
+extern "C" zk_status zk_an_adjusted_traces(zk_an* h, zk_sp* sp, const uint64_t* ids, uint32_t n, uint32_t flags, zk_an_trace* heads,
+                                           zk_an_span* spans, uint64_t cap_spans, uint32_t* services, uint64_t cap_services,
+                                           zk_an_cols* rows, uint64_t cap_rows, uint64_t totals[3]) {
+    ZK_GUARD_BEGIN
+    if (!h) return ZK_ERR_INVALID_ARG;
+    if (!sp || !totals) return afail(h, ZK_ERR_INVALID_ARG, "null argument");
+    if (flags & ~ZK_BATCH_DEVICE_PTRS) return afail(h, ZK_ERR_INVALID_ARG, "unknown flag");
+    if (n > ZK_AN_MAX_IDS) return afail(h, ZK_ERR_INVALID_ARG, "more than ZK_AN_MAX_IDS ids");
+    if (n && (!ids || !heads)) return afail(h, ZK_ERR_INVALID_ARG, "null argument");
+    if ((cap_spans && !spans) || (cap_services && !services)) return afail(h, ZK_ERR_INVALID_ARG, "null output");
+    if (cap_rows && (!rows || !rows->trace_id || !rows->span_id || !rows->ts || !rows->value || !rows->ipv4 || !rows->service_id || !rows->bits))
+        return afail(h, ZK_ERR_INVALID_ARG, "null output column");
+    if (sp_device(sp) != h->device) return afail(h, ZK_ERR_INVALID_ARG, "the two handles are on different devices");
+    totals[0] = totals[1] = totals[2] = 0;
+    if (n == 0) return ZK_OK;
+    memset(heads, 0, (size_t)n * sizeof(zk_an_trace));
+    h->qtimed = false;  // (zk_an_query_ms answers for this call only once k_an_adjust has run)
+    if (h->segs.empty()) return adjt_plain(h, sp, ids, n, flags, heads, spans, cap_spans, services, cap_services, totals);
+    zk_status st;
+    // the span store's part: zk_sp_traces' passes, its sizing call; the merged spans stay in its staging
+    h->adj_traces_host.resize((size_t)n * sizeof(zk_sp_trace));
+    zk_sp_trace* th = (zk_sp_trace*)h->adj_traces_host.data();
+    uint64_t t_out[2] = {0, 0};
+    st = zk_sp_traces(sp, ids, n, flags, th, nullptr, 0, nullptr, 0, t_out);
+    if (st != ZK_OK && st != ZK_ERR_CAPACITY) return afail(h, st, zk_sp_last_error(sp));
+    bool any = false;
+    for (uint32_t i = 0; i < n; ++i) any = any || (th[i].state & ZK_SP_TR_FOUND);
+    if (!any) return ZK_OK;
+    SpStagedTraces sv;
+    sp_staged_traces(sp, &sv);
+    if (!sv.heads || sv.total == 0) return afail(h, ZK_ERR_HIP, "the span store's staging is not there");
+    AN_HIP(h, hipSetDevice(h->device));
+    // this handle's part: the rows of the asked traces into its staging
+    uint32_t parts = 1;
+    h->adj_counts_host.resize(n);
+    uint32_t* counts = h->adj_counts_host.data();
+    if ((st = find_count(h, ids, n, flags, counts, &parts)) != ZK_OK) return st;
+    h->base_host.resize(n);
+    uint64_t rows_total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        h->base_host[i] = rows_total;
+        rows_total += counts[i];
+    }
+    // the overflowed traces are answered here; the others go on the two work lists, the wave-sized ones first
+    h->adj_list_host.clear();
+    uint32_t big_spans = kAdjWave, big_rows = kAdjWave, n_wave = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (uint32_t i = 0; i < n; ++i) {
+            if (!(th[i].state & ZK_SP_TR_FOUND)) continue;
+            const bool over = (th[i].state & ZK_SP_TR_OVERFLOW) || th[i].spans > kAdjMaxSpans || counts[i] > kAdjMaxRows;
+            if (over) {
+                if (pass) continue;
+                zk_an_trace& hd = heads[i];
+                hd.trace_id = th[i].trace_id;
+                hd.fragments = th[i].fragments;
+                hd.state = ZK_SP_TR_FOUND | ZK_AN_ADJ_OVERFLOW;
+                if (counts[i]) {
+                    hd.state |= ZK_AN_ADJ_ANNOTATED;
+                } else {  // not annotated: zk_sp_traces' head of a trace above its bound
+                    hd.start = th[i].start;
+                    hd.end = th[i].end;
+                    hd.state |= ZK_SP_TR_OVERFLOW | (th[i].state & ZK_SP_TR_TIMED);
+                }
+                continue;
+            }
+            const bool small = counts[i] <= (uint32_t)kAdjWave && th[i].spans <= (uint32_t)kAdjWave;
+            if (small != (pass == 0)) continue;
+            h->adj_list_host.push_back(i);
+            if (small) ++n_wave;
+            if (!small) {
+                while (big_spans < th[i].spans) big_spans <<= 1;
+                while (big_rows < counts[i]) big_rows <<= 1;
+            }
+        }
+    }
+    const uint32_t n_group = (uint32_t)h->adj_list_host.size() - n_wave;
+    if (h->adj_list_host.empty()) return ZK_OK;
+    // the stagings: a trace emits at most A + 2 S rows, at its row base plus twice its span base
+    const uint64_t e_n = rows_total + 2 * sv.total;
+    const size_t r8 = Block::col8(e_n), r4 = Block::col4(e_n);
+    if (!h->adjt && (st = alloc(h, &h->adjt, kAdjtBytes, "the adjusted traces' heads and work lists")) != ZK_OK) return st;
+    if ((st = grow(h, &h->rows, &h->rows_bytes, Block::cols_bytes(rows_total), "the gathered rows (44 B each)")) != ZK_OK) return st;
+    if ((st = grow(h, &h->adjt_spans, &h->adjt_spans_bytes, (size_t)sv.total * sizeof(zk_an_span), "the adjusted traces' spans (56 B per fragment)")) != ZK_OK)
+        return st;
+    if ((st = grow(h, &h->adjt_svc, &h->adjt_svc_bytes, (size_t)sv.total * 4, "the adjusted traces' services (4 B per fragment)")) != ZK_OK) return st;
+    if ((st = grow(h, &h->adjt_rows, &h->adjt_rows_bytes, 3 * r8 + 3 * r4, "the adjusted traces' rows (36 B each)")) != ZK_OK) return st;
+    uint8_t* qb = (uint8_t*)h->q;
+    uint8_t* ab = (uint8_t*)h->adjt;
+    const AnCols dev = Block::view(h->rows, rows_total, false);
+    AN_HIP(h, hipMemcpyAsync(qb + kQBaseAt, h->base_host.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    if (rows_total) {
+        AN_HIP(h, hipMemsetAsync(qb + kQCursorAt, 0, (size_t)n * 4, h->stream));
+        AN_HIP(h, launch_checked("k_an_find_write", k_an_find_write, dim3(n, (uint32_t)h->segs.size(), parts), dim3(kAnWG), 0, h->stream,
+                                 (const AnCols*)(qb + kQSegsAt), (const unsigned long long*)(qb + kQIdsAt),
+                                 (const uint32_t*)(qb + kQCountsAt), (uint32_t*)(qb + kQCursorAt),
+                                 (const unsigned long long*)(qb + kQBaseAt), dev));
+    }
+    AN_HIP(h, hipMemcpyAsync(ab + kAdjtListAt, h->adj_list_host.data(), h->adj_list_host.size() * 4, hipMemcpyHostToDevice, h->stream));
+    AN_HIP(h, hipMemsetAsync(ab, 0, (size_t)n * sizeof(zk_an_trace), h->stream));
+    AdjEmitIn in;
+    in.rows = dev;
+    in.list = (const uint32_t*)(ab + kAdjtListAt);
+    in.ids = (const unsigned long long*)(qb + kQIdsAt);
+    in.counts = (const uint32_t*)(qb + kQCountsAt);
+    in.base = (const unsigned long long*)(qb + kQBaseAt);
+    in.t_heads = sv.heads;
+    in.t_spans = sv.spans;
+    in.t_svc = sv.services;
+    in.t_base = sv.base;
+    in.t_total = sv.total;
+    in.cap_spans = in.cap_rows = (uint32_t)kAdjWave;
+    in.heads = nullptr;
+    in.o_svc = nullptr;
+    in.o_first = in.o_last = nullptr;
+    in.e_heads = (zk_an_trace*)ab;
+    in.e_spans = (zk_an_span*)h->adjt_spans;
+    in.e_svc = (uint32_t*)h->adjt_svc;
+    uint8_t* rb = (uint8_t*)h->adjt_rows;
+    in.e_span = (unsigned long long*)rb;
+    in.e_ts = (long long*)(rb + r8);
+    in.e_val = (unsigned long long*)(rb + 2 * r8);
+    in.e_ip = (uint32_t*)(rb + 3 * r8);
+    in.e_rsvc = (uint32_t*)(rb + 3 * r8 + r4);
+    in.e_bits = (uint32_t*)(rb + 3 * r8 + 2 * r4);
+    in.e_n = e_n;
+    in.h_sr = zk_hash_string("sr", 2);
+    in.h_ss = zk_hash_string("ss", 2);
+    AN_HIP(h, launch_checked("k_an_adjust (emitting, a wave per trace)", k_an_adjust<kAdjWave, AdjEmitIn>, dim3(n_wave), dim3(kAdjWave),
+                             adj_lds(kAdjWave, kAdjWave), h->stream, in));
+    in.list += n_wave;
+    in.cap_spans = big_spans;
+    in.cap_rows = big_rows;
+    AN_HIP(h, launch_checked("k_an_adjust (emitting, a workgroup per trace)", k_an_adjust<kAnWG, AdjEmitIn>, dim3(n_group), dim3(kAnWG),
+                             adj_lds(big_spans, big_rows), h->stream, in));
+    // only the heads cross before the totals are known
+    h->adjt_heads_host.resize((size_t)n * sizeof(zk_an_trace));
+    const zk_an_trace* got = (const zk_an_trace*)h->adjt_heads_host.data();
+    AN_HIP(h, hipMemcpyAsync(h->adjt_heads_host.data(), ab, (size_t)n * sizeof(zk_an_trace), hipMemcpyDeviceToHost, h->stream));
+    if (h->timing) AN_HIP(h, hipEventRecord(h->qev[1], h->stream));
+    AN_HIP(h, hipStreamSynchronize(h->stream));
+    h->qtimed = h->timing;
+    for (uint32_t i : h->adj_list_host) {
+        if (!(got[i].state & ZK_SP_TR_FOUND)) return afail(h, ZK_ERR_HIP, "a listed trace was not adjusted");
+        if (got[i].spans > th[i].spans || got[i].services > th[i].services || got[i].rows > (uint64_t)counts[i] + 2ull * th[i].spans)
+            return afail(h, ZK_ERR_HIP, "an adjusted trace is larger than its share of the staging");
+        heads[i] = got[i];
+        totals[0] += got[i].spans;
+        totals[1] += got[i].services;
+        totals[2] += got[i].rows;
+    }
+    if (totals[0] > cap_spans || totals[1] > cap_services || totals[2] > cap_rows)
+        return afail(h, ZK_ERR_CAPACITY, "an output holds fewer entries than the asked traces have");
+    // one copy per output, then each trace's share packed behind the ones before it
+    h->adjt_spans_host.resize((size_t)sv.total * sizeof(zk_an_span));
+    h->adjt_svc_host.resize((size_t)sv.total * 4);
+    AN_HIP(h, hipMemcpyAsync(h->adjt_spans_host.data(), h->adjt_spans, h->adjt_spans_host.size(), hipMemcpyDeviceToHost, h->stream));
+    AN_HIP(h, hipMemcpyAsync(h->adjt_svc_host.data(), h->adjt_svc, h->adjt_svc_host.size(), hipMemcpyDeviceToHost, h->stream));
+    if (totals[2]) {
+        h->adjt_rows_host.resize(3 * r8 + 3 * r4);
+        AN_HIP(h, hipMemcpyAsync(h->adjt_rows_host.data(), h->adjt_rows, 3 * r8 + 3 * r4, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (h->timing) AN_HIP(h, hipEventRecord(h->qev[1], h->stream));
+    AN_HIP(h, hipStreamSynchronize(h->stream));
+    const zk_an_span* s_spans = (const zk_an_span*)h->adjt_spans_host.data();
+    const uint32_t* s_svc = (const uint32_t*)h->adjt_svc_host.data();
+    const uint8_t* hr = h->adjt_rows_host.data();
+    uint64_t at_s = 0, at_v = 0, at_r = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const zk_an_trace& hd = heads[i];
+        const uint64_t from = sv.base_host[i], rfrom = h->base_host[i] + 2 * sv.base_host[i];
+        if (hd.spans) memcpy(spans + at_s, s_spans + from, (size_t)hd.spans * sizeof(zk_an_span));
+        if (hd.services) memcpy(services + at_v, s_svc + from, (size_t)hd.services * 4);
+        if (hd.rows) {
+            std::fill(rows->trace_id + at_r, rows->trace_id + at_r + hd.rows, hd.trace_id);
+            memcpy(rows->span_id + at_r, (const uint64_t*)hr + rfrom, (size_t)hd.rows * 8);
+            memcpy(rows->ts + at_r, (const int64_t*)(hr + r8) + rfrom, (size_t)hd.rows * 8);
+            memcpy(rows->value + at_r, (const uint64_t*)(hr + 2 * r8) + rfrom, (size_t)hd.rows * 8);
+            memcpy(rows->ipv4 + at_r, (const uint32_t*)(hr + 3 * r8) + rfrom, (size_t)hd.rows * 4);
+            memcpy(rows->service_id + at_r, (const uint32_t*)(hr + 3 * r8 + r4) + rfrom, (size_t)hd.rows * 4);
+            memcpy(rows->bits + at_r, (const uint32_t*)(hr + 3 * r8 + 2 * r4) + rfrom, (size_t)hd.rows * 4);
+        }
+        at_s += hd.spans;
+        at_v += hd.services;
+        at_r += hd.rows;
     }
     return ZK_OK;
     ZK_GUARD_END

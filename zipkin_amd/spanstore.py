@@ -653,11 +653,48 @@ class TraceSpanStore:
             raise ValueError("adjust needs annotations=, a TraceAnnotationStore")
         return adjust
 
-    def getTracesByIds(self, ids, adjust: Sequence[str] = (), annotations=None) -> List[Trace]:
+    def _adjust_on_device(self, adjust, annotations, on_device: bool = False) -> None:
+        """The rules of adjust_on_device=True: annotations= and "TIME_SKEW" as the only adjuster besides
+        "NOTHING", once, and not on_device=True beside it; anything else is a ValueError."""
+        adjust = self._adjusters(adjust, annotations)
+        if on_device:
+            raise ValueError("adjust_on_device=True replaces on_device=True: give one of them")
+        if [name for name in adjust if name != "NOTHING"] != ["TIME_SKEW"] or annotations is None:
+            raise ValueError('adjust_on_device=True needs annotations= and adjust=("TIME_SKEW",), applied once')
+
+    def _combos_adjusted_on_device(self, ids, annotations, decoder=None, lists=True, timelines=True) -> List[TraceCombo]:
+        """getTraceCombosByIds(adjust=("TIME_SKEW",), annotations=) from annotations.adjusted_traces(): the
+        adjusted traces with their annotations, summaries, timelines and depths from one answer per chunk; a
+        trace above the device's bounds goes the host's way. The cyclic collector is paused while the tuples
+        are built, as in _combos_on_device. lists, timelines: _combos_of's."""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64))
+        out: List[TraceCombo] = []
+        paused = gc.isenabled()
+        gc.disable()
+        try:
+            for a in range(0, len(ids), _abi.ZK_AN_MAX_IDS):
+                self._combos_of(out, *annotations.adjusted_traces(self, ids[a:a + _abi.ZK_AN_MAX_IDS]), annotations=annotations,
+                                decoder=decoder, lists=lists, timelines=timelines)
+        finally:
+            if paused:
+                gc.enable()
+        return out
+
+    def _combos_on_host(self, ids, adjust, annotations, decoder=None) -> List[TraceCombo]:
+        """The host path of getTraceCombosByIds with an annotation store."""
+        return [TraceCombo.of(t, TraceTimeline.of(t, decoder, self.services)) for t in self.getTracesByIds(ids, adjust, annotations)]
+
+    def getTracesByIds(self, ids, adjust: Sequence[str] = (), annotations=None, adjust_on_device: bool = False) -> List[Trace]:
         """One Trace per asked id that was found, in the order asked. annotations: a TraceAnnotationStore;
         every Trace then carries its annotations (Trace's annotations=). adjust: a sequence of "NOTHING" /
         "TIME_SKEW", folded over each trace in order as QueryService folds its adjusters; it needs
-        annotations=. A trace that has no rows in the annotation store is returned unadjusted."""
+        annotations=. A trace that has no rows in the annotation store is returned unadjusted.
+        adjust_on_device: the adjuster runs on the device (zk_an_adjusted_traces; the rules of
+        getTraceSummariesByIds' adjust_on_device). The answer is the host path's, with ONE difference:
+        Trace.rows is None, as with Trace.of_merged."""
+        if adjust_on_device:
+            self._adjust_on_device(adjust, annotations)
+            return [c.trace for c in self._combos_adjusted_on_device(ids, annotations, timelines=False)]
         adjust = self._adjusters(adjust, annotations)
         found = self.getSpansByTraceIds(ids)
         if annotations is None:
@@ -669,12 +706,17 @@ class TraceSpanStore:
             out.append(apply_adjusters(t, adjust) if a else t)
         return out
 
-    def getTraceTimelinesByIds(self, ids, adjust: Sequence[str] = (), annotations=None, decoder=None) -> List[TraceTimeline]:
+    def getTraceTimelinesByIds(self, ids, adjust: Sequence[str] = (), annotations=None, decoder=None,
+                               adjust_on_device: bool = False) -> List[TraceTimeline]:
         """QueryService.getTraceTimelinesByIds: the timeline of every asked trace that was found, in the
         order asked, after the adjusters. annotations=, a TraceAnnotationStore, is required. decoder: turns
-        the values into text (TraceTimeline.of); service names come from the store's services dictionary."""
+        the values into text (TraceTimeline.of); service names come from the store's services dictionary.
+        adjust_on_device: as for getTracesByIds; the answer is the same."""
         if annotations is None:
             raise ValueError("timelines need annotations=, a TraceAnnotationStore")
+        if adjust_on_device:
+            self._adjust_on_device(adjust, annotations)
+            return [c.timeline for c in self._combos_adjusted_on_device(ids, annotations, decoder, lists=False)]
         lines = (TraceTimeline.of(t, decoder, self.services) for t in self.getTracesByIds(ids, adjust, annotations))
         return [t for t in lines if t is not None]
 
@@ -751,8 +793,13 @@ class TraceSpanStore:
                 gc.enable()
         return out
 
-    def _combos_of(self, out: List[TraceCombo], heads, spans, services) -> None:
-        """The TraceCombos of one traces() answer, appended to out."""
+    def _combos_of(self, out: List[TraceCombo], heads, spans, services, rows=None, annotations=None, decoder=None,
+                   lists: bool = True, timelines: bool = True) -> None:
+        """The TraceCombos of one traces() answer, appended to out. With rows (and annotations, the store they
+        came from): of one TraceAnnotationStore.adjusted_traces() answer, whose heads and spans carry the same
+        field names; every span is then an AnnotatedSpan with its list, and the timeline is filled. A caller
+        that hands on only the timelines, or only the traces, saves the other's tuples (one per row each):
+        lists=False leaves the spans' lists empty, timelines=False the timeline None."""
         namer = Trace((), self.services, self.span_names)
         svc = services.tolist() if self.services is None else [namer._service(i) for i in services.tolist()]
         names = spans["name"].tolist()
@@ -770,7 +817,12 @@ class TraceSpanStore:
         svc_end = np.cumsum(k)
         mine = [tuple(svc[a:b]) for a, b in zip((svc_end - k).tolist(), svc_end.tolist())]
         c = heads["spans"].astype(np.int64)
-        merged = list(map(Span, np.repeat(heads["trace_id"], c).tolist(), sid, parent, names, first, last, mine))
+        merged = list(map(Span if rows is None else AnnotatedSpan, np.repeat(heads["trace_id"], c).tolist(), sid, parent, names, first,
+                          last, mine))
+        lines, line_at, over = None, None, _abi.ZK_SP_TR_OVERFLOW
+        if rows is not None:
+            over |= _abi.ZK_AN_ADJ_OVERFLOW
+            lines, line_at = self._annotate_merged(merged, heads, spans, rows, parent, names, decoder, lists, timelines)
         # one SpanTimestamp per (span, service) pair of a timed span, in the pairs' order
         pair_span = np.repeat(np.arange(len(spans)), k)
         keep = timed[pair_span]
@@ -779,9 +831,12 @@ class TraceSpanStore:
                           spans["first"][pair_span].tolist(), spans["last"][pair_span].tolist()))
         stamp_at = np.concatenate(([0], np.cumsum(np.where(timed, k, 0)))).tolist()
         at = 0
-        for tid, start, end, root, _, n_spans, _, state in heads.tolist():
-            if state & _abi.ZK_SP_TR_OVERFLOW:  # a trace too long for the device merge: the host path
-                out += self.getTraceCombosByIds([tid])
+        for q, (tid, start, end, root, _, n_spans, _, state, *_) in enumerate(heads.tolist()):
+            if state & over:  # a trace too long for the device merge: the host path
+                if rows is None:
+                    out += self.getTraceCombosByIds([tid])
+                else:
+                    out += self._combos_on_host([tid], ("TIME_SKEW",), annotations, decoder)  # (whole: one trace)
                 continue
             if not state & _abi.ZK_SP_TR_FOUND:
                 continue
@@ -790,8 +845,54 @@ class TraceSpanStore:
             summary = None
             if state & _abi.ZK_SP_TR_TIMED:
                 summary = TraceSummary(tid, start, end, _to_int(_wrap64(end - start)), stamps[stamp_at[at]:stamp_at[to]], [])
-            out.append(TraceCombo(Trace.of_merged(merged[at:to], root, depths), summary, None, depths))
+            trace, timeline = Trace.of_merged(merged[at:to], root, depths), None
+            if rows is not None:
+                trace.annotations = {s.id: s.annotations for s in trace.spans}
+                if timelines:
+                    timeline = TraceTimeline(tid, root, lines[line_at[q]:line_at[q + 1]], [])
+            out.append(TraceCombo(trace, summary, timeline, depths))
             at = to
+
+    def _annotate_merged(self, merged, heads, spans, rows, parent, names, decoder, lists=True, timelines=True):
+        """Every AnnotatedSpan of `merged` gets its list from `rows` (an adjusted_traces() answer: per span, in
+        the spans' order, the span's annotations in list order). Returns the chunk's TimelineAnnotations, every
+        trace's sorted by ts, and where each asked id's begin. The emitted order is TraceTimeline.of's order
+        before its sort, so one stable sort over (asked index, ts) gives all timelines at once."""
+        bits = rows.bits
+        kind = bits & _abi.ZK_AN_KIND_MASK
+        hosted = (bits & _abi.ZK_AN_HAS_HOST) != 0
+        port = bits >> _abi.ZK_AN_PORT_SHIFT
+        k = spans["rows"].astype(np.int64)
+        if lists:
+            ends = list(map(Endpoint, rows.ipv4.tolist(), port.tolist(), rows.service_id.tolist()))
+            anns = list(map(Annotation, rows.ts.tolist(), rows.value.tolist(), kind.tolist(),
+                            [e if h else None for e, h in zip(ends, hosted.tolist())]))
+            row_end = np.cumsum(k)
+            for s, a, b in zip(merged, (row_end - k).tolist(), row_end.tolist()):
+                s.annotations = anns[a:b]
+        else:
+            for s in merged:
+                s.annotations = []
+        if not timelines:
+            return None, None
+        # the timelines: a stable sort by (asked index, ts)
+        per_trace = heads["rows"].astype(np.int64)
+        order = np.lexsort((rows.ts, np.repeat(np.arange(len(heads)), per_trace)))
+        of_span = np.repeat(np.arange(len(spans)), k)[order]
+        kind_o, hosted_o = kind[order], hosted[order]
+        value = rows.value[order].tolist()
+        if decoder is not None:
+            value = [KIND_NAMES[c] if c else decoder.string(v) for v, c in zip(value, kind_o.tolist())]
+        svc = np.where(hosted_o, rows.service_id[order], 0).tolist()
+        if self.services is not None:
+            if svc and max(svc) >= len(self.services):
+                raise ValueError("a service id beyond the services dictionary")
+            svc = [self.services[i] if h else "Unknown" for i, h in zip(svc, hosted_o.tolist())]
+        span_of = of_span.tolist()
+        lines = list(map(TimelineAnnotation, rows.ts[order].tolist(), value, np.where(hosted_o, rows.ipv4[order], 0).tolist(),
+                         np.where(hosted_o, port[order], 0).tolist(), svc, spans["span_id"][of_span].tolist(),
+                         [parent[i] for i in span_of], [names[i] for i in span_of]))
+        return lines, np.concatenate(([0], np.cumsum(per_trace))).tolist()
 
     def _host_only(self, on_device: bool, adjust, annotations) -> bool:
         """Whether a call goes the host's way: always with an annotation store (the adjusters and the
@@ -801,18 +902,24 @@ class TraceSpanStore:
             raise ValueError("TIME_SKEW is adjusted on the host: on_device=True cannot be combined with it")
         return annotations is not None or not on_device
 
-    def getTraceCombosByIds(self, ids, on_device: bool = False, adjust: Sequence[str] = (), annotations=None) -> List[TraceCombo]:
+    def getTraceCombosByIds(self, ids, on_device: bool = False, adjust: Sequence[str] = (), annotations=None,
+                            adjust_on_device: bool = False) -> List[TraceCombo]:
         """QueryService.getTraceCombosByIds: one TraceCombo (the trace, its summary, its timeline, its span
         depths) per asked id that was found, in the order asked; summary is None for a trace without a timed
         fragment. on_device: spans, summary and depths are merged on the device (zk_sp_traces) and no
         fragment crosses to the host; the answer is the same. adjust, annotations: as for getTracesByIds;
-        with an annotation store the host path is used and timeline is filled, without one it is None."""
+        with an annotation store the host path is used and timeline is filled, without one it is None.
+        adjust_on_device: with an annotation store, the adjuster, the spans' lists and the depths come from
+        the device too (zk_an_adjusted_traces; the rules of getTraceSummariesByIds' adjust_on_device). The
+        answer is the host path's, with ONE difference: Trace.rows is None, as with Trace.of_merged."""
+        if adjust_on_device:
+            self._adjust_on_device(adjust, annotations, on_device)
+            return self._combos_adjusted_on_device(ids, annotations)
         if not self._host_only(on_device, adjust, annotations):
             return self._combos_on_device(ids)
-        traces = self.getTracesByIds(ids, adjust, annotations)
         if annotations is None:
-            return [TraceCombo.of(t) for t in traces]
-        return [TraceCombo.of(t, TraceTimeline.of(t, None, self.services)) for t in traces]
+            return [TraceCombo.of(t) for t in self.getTracesByIds(ids, adjust, annotations)]
+        return self._combos_on_host(ids, adjust, annotations)
 
     def _summaries_adjusted_on_device(self, ids, annotations) -> List[TraceSummary]:
         """getTraceSummariesByIds(adjust=("TIME_SKEW",), annotations=) from annotations.adjusted_summaries():
@@ -857,11 +964,7 @@ class TraceSpanStore:
         annotations= and "TIME_SKEW" as the only adjuster besides "NOTHING", once; anything else is a
         ValueError."""
         if adjust_on_device:
-            adjust = self._adjusters(adjust, annotations)
-            if on_device:
-                raise ValueError("adjust_on_device=True replaces on_device=True: give one of them")
-            if [name for name in adjust if name != "NOTHING"] != ["TIME_SKEW"] or annotations is None:
-                raise ValueError('adjust_on_device=True needs annotations= and adjust=("TIME_SKEW",), applied once')
+            self._adjust_on_device(adjust, annotations, on_device)
             return self._summaries_adjusted_on_device(np.ascontiguousarray(np.asarray(ids, dtype=np.uint64)), annotations)
         if not self._host_only(on_device, adjust, annotations):
             return self._summaries_on_device(ids)
