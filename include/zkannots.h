@@ -7,7 +7,7 @@
  * timestamp, the kind of its value and its host. This handle keeps one 44-B ROW per time annotation of an
  * accepted span, findable by trace id, and hands the rows of the asked traces back; the adjuster and the
  * timeline are built on the host over them (zipkin_amd/annotstore.py, spanstore.py). Binary annotations are
- * not kept.
+ * kept by a store of their own over this one's core: zkbinannots.h.
  *
  * A row, seven columns, 44 bytes:
  *   trace_id    u64

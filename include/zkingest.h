@@ -169,6 +169,47 @@ typedef struct zk_ingest_annotation_rows {
 zk_status zk_ingest_spans_annotated(zk_ingest* ing, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
                                     uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
                                     zk_ingest_items* items, zk_ingest_annotation_rows* an);
+/* caller buffers for the rows of the binary-annotation store (zkbinannots.h): seven parallel columns (HOST
+ * memory for zk_ingest_spans_annotated_binary, DEVICE memory for zk_ingest_dev_spans_annotated_binary), laid
+ * out as zk_bn_cols, then their capacity and count */
+typedef struct zk_ingest_binary_rows {
+    uint64_t* trace_id;
+    uint64_t* span_id;
+    uint64_t* key;         /* zk_hash_string(key); the bytes are kept: zk_ingest_string */
+    uint64_t* value;       /* zk_hash_string(value bytes), without the index's `| 1`; the bytes are kept */
+    uint32_t* ipv4;        /* the host's ipv4 (Endpoint field 1, the i32's bits); 0 without a host */
+    uint32_t* service_id;  /* the host's service id; 0 without a host */
+    uint32_t* bits;        /* ZK_BN_* of zkbinannots.h: type, HAS_HOST, the port (Endpoint field 2) in bits 16..31 */
+    uint64_t  cap;         /* rows the arrays hold */
+    uint64_t  n;           /* out (decoder): rows */
+} zk_ingest_binary_rows;
+
+/* zk_ingest_spans_annotated (records, rejection, `items`, ZK_INGEST_SPAN_NAMES and the time rows of `an`
+ * exactly as that call's for the same arguments) that also writes the binary-annotation store's rows to the
+ * HOST columns of `bn`: one row per binary annotation of every ACCEPTED span (with or without time
+ * annotations).
+ *   - Order: record order and, within a record, list order (all field-8 lists appended); the same for any
+ *     thread count.
+ *   - Wire forms of a BinaryAnnotation: field 1 string key, field 2 string value, field 3 i32 type, field 4
+ *     struct host, the host read as for a time row (ipv4, port, name). The last occurrence of a scalar
+ *     wins; a known id with another wire type is skipped by its type; within one binary annotation a later
+ *     host struct keeps the earlier ipv4, port and name unless it carries its own; an absent or empty name
+ *     is "Unknown service name". An absent key or value hashes as "". The type: an absent field 3 gives 0,
+ *     a value outside 0..6 gives 7 (ZK_BN_TYPE_OTHER). Binary annotations are not validated.
+ *   - A binary row's host enters the service dictionary after the record's own service, the record's items
+ *     and the record's time rows, in row order. A row without a host has service_id = ipv4 = 0, no HAS_HOST
+ *     bit and port 0.
+ *   - The key's and the value's bytes are captured: zk_ingest_string(hash) answers for both, with their
+ *     length (a value may hold NUL and bytes that are no UTF-8). One string is kept per distinct value:
+ *     nothing bounds the host memory of high-cardinality values here.
+ *   - bn->cap too small: ZK_ERR_CAPACITY; the records, all time rows that fit `an` and the first cap binary
+ *     rows are written and bn->n = cap. The capacities of an and bn are judged independently.
+ *   - an and bn and their columns must not be NULL (ZK_ERR_INVALID_ARG).
+ * The device decoder emits the same rows into device columns: zk_ingest_dev_spans_annotated_binary. */
+zk_status zk_ingest_spans_annotated_binary(zk_ingest* ing, const uint8_t* buf, const uint64_t* offsets, uint64_t n,
+                                           uint32_t codec, uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
+                                           uint64_t* n_rejected, zk_ingest_items* items, zk_ingest_annotation_rows* an,
+                                           zk_ingest_binary_rows* bn);
 /* the value hash of the annotation index: zk_hash_string(s, len) | 1, so it is never 0 (0 asks for any
    value, and marks a time-annotation entry) */
 uint64_t  zk_index_value_hash(const char* s, uint64_t len);
@@ -316,8 +357,34 @@ zk_status   zk_ingest_dev_spans_multi_annotated(zk_ingest_dev* ing, uint32_t nb,
                                                 uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
                                                 uint64_t* n_rejected, zk_ingest_items* items,
                                                 zk_ingest_annotation_rows* an);
+/* zk_ingest_dev_spans_annotated / zk_ingest_dev_spans_multi_annotated that also write the binary-annotation
+ * store's rows (zkbinannots.h) to the seven DEVICE columns of `bn` (laid out as zk_bn_cols), which
+ * zk_bn_observe (ZK_BATCH_DEVICE_PTRS) takes without a copy: zk_ingest_spans_annotated_binary on the device.
+ * Records, rejection, dictionaries, `items`, ZK_INGEST_SPAN_NAMES and the time rows of `an` are the annotated
+ * call's for the same arguments. an, bn or any of their columns NULL: ZK_ERR_INVALID_ARG before any device is
+ * touched. an->n = bn->n = 0 on entry.
+ *   - Rows, wire forms, order, the capacity prefix (an and bn judged independently), errors and the
+ *     dictionary rule are the host decoder's and the annotated call's, word for word; service_id is THIS
+ *     decoder's id (compare through names).
+ *   - Strings: without ZK_INGEST_NO_ROW_STRINGS every key and value goes through the captured-string set as
+ *     row values do, and zk_ingest_dev_string(hash) answers for every key and value the call wrote, with its
+ *     length. With the flag the rows are identical and the set is untouched. One string is kept per distinct
+ *     value on the host side: high-cardinality values are what the flag is for.
+ *   - Bounded stores: a row at or past bn->cap is dropped, never written elsewhere.
+ * ONE rows pass serves both lists: the count kernel decompresses a fragment once and walks field 6 and then
+ * field 8 over the same bytes; the write kernel walks both again over the slice's scratch. A fragment is
+ * walked when it is accepted, with or without time annotations. */
+zk_status   zk_ingest_dev_spans_annotated_binary(zk_ingest_dev* ing, const uint8_t* buf, const uint64_t* offsets, uint64_t n,
+                                                 uint32_t codec, uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
+                                                 uint64_t* n_rejected, zk_ingest_items* items /* may be NULL */,
+                                                 zk_ingest_annotation_rows* an, zk_ingest_binary_rows* bn);
+zk_status   zk_ingest_dev_spans_multi_annotated_binary(zk_ingest_dev* ing, uint32_t nb, const uint8_t* const* bufs,
+                                                       const uint64_t* const* offsets, const uint64_t* ns, uint32_t codec,
+                                                       uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
+                                                       uint64_t* n_rejected, zk_ingest_items* items,
+                                                       zk_ingest_annotation_rows* an, zk_ingest_binary_rows* bn);
 /* the last rows pass of this decoder: the device time between its first and last launch (ms), and the
-   slices it ran in (0 / 0 before the first annotated call) */
+   slices it ran in (0 / 0 before the first annotated call); the combined pass of an annotated_binary call */
 zk_status   zk_ingest_dev_rows_stats(const zk_ingest_dev* ing, double* pass_ms, uint64_t* slices);
 /* the string behind a key / value hash an items batch of this decoder has seen, or behind the value of a
    row an annotated call wrote without ZK_INGEST_NO_ROW_STRINGS (two-phase) */

@@ -13,6 +13,8 @@ from .nameindex import IndexedTraceId, TraceNameIndex, merge_trace_ids  # noqa: 
 from .annindex import AnnotationItems, DeviceAnnotationItems, TraceAnnotationIndex, get_trace_ids, trace_ids_intersect  # noqa: F401
 from .retention import IndexRetention, SpanRetention  # noqa: F401
 from .annotstore import ADJ_ANNOTATED, ADJ_OVERFLOW, ADJUSTED_HEAD, Annotation, AnnotationRows, DeviceAnnotationRows, Endpoint, TraceAnnotationStore  # noqa: F401
+from .binannotstore import (BinaryAnnotation, BinaryAnnotationRows, DeviceBinaryAnnotationRows,  # noqa: F401
+                            TraceBinaryAnnotationStore)
 from .spanstore import (SUMMARY_HEAD, TRACE_HEAD, TRACE_SPAN, AnnotatedSpan, Span, SpanTimestamp, TimelineAnnotation,  # noqa: F401
                         Timespan, TimeSkewAdjuster, Trace, TraceCombo, TraceSpanStore, TraceSummary, TraceTimeline)
 from .windows import WindowedAggregateJob, WindowPartition  # noqa: F401
@@ -55,6 +57,10 @@ __all__ = [
     "TRACE_SPAN",
     "TraceCombo",
     "TraceAnnotationStore",
+    "TraceBinaryAnnotationStore",
+    "BinaryAnnotationRows",
+    "DeviceBinaryAnnotationRows",
+    "BinaryAnnotation",
     "ADJUSTED_HEAD",
     "ADJUSTED_TRACE_HEAD",
     "ADJUSTED_TRACE_SPAN",

@@ -478,6 +478,41 @@ class zk_an_cols(C.Structure):
     ]
 
 
+ZK_BN_BUCKETS, ZK_BN_MAX_SEGMENTS, ZK_BN_MAX_IDS, ZK_BN_ROW_BYTES = ZK_AN_BUCKETS, ZK_AN_MAX_SEGMENTS, ZK_AN_MAX_IDS, ZK_AN_ROW_BYTES
+ZK_BN_TYPE_MASK = 7
+(ZK_BN_TYPE_BOOL, ZK_BN_TYPE_BYTES, ZK_BN_TYPE_I16, ZK_BN_TYPE_I32, ZK_BN_TYPE_I64, ZK_BN_TYPE_DOUBLE, ZK_BN_TYPE_STRING,
+ ZK_BN_TYPE_OTHER) = range(8)
+ZK_BN_HAS_HOST = 8
+ZK_BN_PORT_SHIFT = 16
+
+
+class zk_bn_cols(C.Structure):
+    """zk_an_cols with `key` in the place of `ts` (zkbinannots.h)."""
+    _fields_ = [
+        ("trace_id", C.c_void_p),
+        ("span_id", C.c_void_p),
+        ("key", C.c_void_p),
+        ("value", C.c_void_p),
+        ("ipv4", C.c_void_p),
+        ("service_id", C.c_void_p),
+        ("bits", C.c_void_p),
+    ]
+
+
+class zk_ingest_binary_rows(C.Structure):
+    _fields_ = [
+        ("trace_id", C.c_void_p),
+        ("span_id", C.c_void_p),
+        ("key", C.c_void_p),
+        ("value", C.c_void_p),
+        ("ipv4", C.c_void_p),
+        ("service_id", C.c_void_p),
+        ("bits", C.c_void_p),
+        ("cap", C.c_uint64),
+        ("n", C.c_uint64),
+    ]
+
+
 class zk_an_trace(C.Structure):
     _fields_ = [
         ("trace_id", C.c_uint64),
@@ -655,6 +690,12 @@ _SIGNATURES = [
          C.POINTER(zk_ingest_items), C.POINTER(zk_ingest_annotation_rows)],
     ),
     ("zk_index_value_hash", C.c_uint64, [C.c_char_p, C.c_uint64]),
+    (
+        "zk_ingest_spans_annotated_binary",
+        C.c_int,
+        [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(zk_span_cols), _U64P, _U64P,
+         C.POINTER(zk_ingest_items), C.POINTER(zk_ingest_annotation_rows), C.POINTER(zk_ingest_binary_rows)],
+    ),
     ("zk_ingest_num_services", C.c_int, [_P, _U32P]),
     ("zk_ingest_service_id", C.c_int, [_P, C.c_char_p, C.c_uint64, _U32P]),
     ("zk_ingest_service_name", C.c_int, [_P, C.c_uint32, C.c_char_p, C.c_uint64, _U64P]),
@@ -688,6 +729,13 @@ _SIGNATURES = [
     ("zk_ingest_dev_spans_multi_annotated", C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _U64P,
                                                       _U64P, C.POINTER(zk_ingest_items),
                                                       C.POINTER(zk_ingest_annotation_rows)]),
+    ("zk_ingest_dev_spans_annotated_binary", C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _U64P, _U64P,
+                                                       C.POINTER(zk_ingest_items), C.POINTER(zk_ingest_annotation_rows),
+                                                       C.POINTER(zk_ingest_binary_rows)]),
+    ("zk_ingest_dev_spans_multi_annotated_binary", C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _U64P,
+                                                             _U64P, C.POINTER(zk_ingest_items),
+                                                             C.POINTER(zk_ingest_annotation_rows),
+                                                             C.POINTER(zk_ingest_binary_rows)]),
     ("zk_ingest_dev_rows_stats", C.c_int, [_P, C.POINTER(C.c_double), _U64P]),
     ("zk_ingest_dev_string", C.c_int, [_P, C.c_uint64, C.c_char_p, C.c_uint64, _U64P]),
     ("zk_ingest_dev_num_services", C.c_int, [_P, C.POINTER(C.c_uint32)]),
@@ -809,6 +857,16 @@ _SIGNATURES = [
     ("zk_an_gather", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _U32P, C.POINTER(zk_an_cols), C.c_uint64, _U64P]),
     ("zk_an_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_an_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zk_bn_create", C.c_int, [C.POINTER(zk_an_config), C.POINTER(_P)]),
+    ("zk_bn_destroy", C.c_int, [_P]),
+    ("zk_bn_last_error", C.c_char_p, [_P]),
+    ("zk_bn_observe", C.c_int, [_P, C.POINTER(zk_bn_cols), C.c_uint64, C.c_uint32]),
+    ("zk_bn_reset", C.c_int, [_P]),
+    ("zk_bn_compact", C.c_int, [_P]),
+    ("zk_bn_info", C.c_int, [_P, _U64P, _U64P, _U64P]),
+    ("zk_bn_gather", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _U32P, C.POINTER(zk_bn_cols), C.c_uint64, _U64P]),
+    ("zk_bn_observe_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zk_bn_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_an_expire", C.c_int, [_P, C.c_int64, _P, _P, C.c_uint32, _U64P]),
     ("zk_an_expire_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zk_an_adjusted_summaries", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, C.POINTER(zk_sp_span_ts), C.c_uint64, _U64P]),

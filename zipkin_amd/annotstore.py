@@ -195,7 +195,7 @@ class TraceAnnotationStore:
             self.info()
 
     def observe_stored(self, decoder, buf, offsets, n: int, *, snappy: bool = True, strict: bool = True, spans=None,
-                       row_strings: bool = True):
+                       row_strings: bool = True, binary=None):
         """Decode one batch of STORED fragments already in HBM (buf uint8, offsets int64[n + 1]: torch tensors
         on the device) with `decoder` (an ingest.DeviceSpanDecoder) and observe its annotation rows in one
         step: the twin of TraceAnnotationIndex.observe_stored. No row column is copied to the host. With
@@ -205,12 +205,23 @@ class TraceAnnotationStore:
         (info, gather, compact, expire, observe_stored; observe(sync=True) ends in info), the record columns
         until the span store's next info() or the next observe_stored(spans=) on it: longer than the
         device-pointer rule of zk_an_observe / zk_sp_observe requires, never shorter. row_strings=False leaves the
-        values' strings uncaptured (the adjuster and the summaries need no text; a timeline does)."""
+        values' strings uncaptured (the adjuster and the summaries need no text; a timeline does).
+        With binary= (a binannotstore.TraceBinaryAnnotationStore on the same device) the same call's rows pass
+        also emits the batch's binary-annotation rows (zk_ingest_dev_spans_annotated_binary) and they are
+        observed there, held until that store's next synchronising call; row_strings covers their keys and
+        values too."""
         import torch
 
         torch.cuda.current_stream(self.device).synchronize()  # (the caller's tensors may still be in flight)
-        cols, rejected, rows = decoder.decode_device(buf, offsets, n, snappy=snappy, strict=strict, annotated=True,
-                                                     row_strings=row_strings)
+        if binary is not None:
+            cols, rejected, rows, brows = decoder.decode_device(buf, offsets, n, snappy=snappy, strict=strict, annotated=True,
+                                                                row_strings=row_strings, binary=True)
+            if len(brows):
+                binary.observe(brows, sync=False)
+            binary._held = brows
+        else:
+            cols, rejected, rows = decoder.decode_device(buf, offsets, n, snappy=snappy, strict=strict, annotated=True,
+                                                         row_strings=row_strings)
         if len(rows):
             self.observe(rows, sync=False)
         self._held = rows

@@ -38,7 +38,7 @@ SOURCES = [
     "zk_an.hip",
 ]
 HEADERS = ["zk_internal.h", "zk_cluster.h", "zk_tracegen.h", "zk_sketch_internal.h", "zk_rt_internal.h", "zk_block.h", "zk_launch.h", "zk_comm.h", "zk_rl_internal.h", "zk_lh_internal.h", "zk_lh_snapshot.h", "zk_td_select.h", "zk_ix_select.h", "zk_hist.h", "zk_expire.h", "zk_seg_index.h", "zk_sp_staged.h"]
-PUBLIC_HEADERS = ["zkagg.h", "zksketch.h", "zkstore.h", "zkingest.h", "zkcomm.h", "zkwindow.h", "zkduration.h", "zkindex.h", "zkannindex.h", "zkspans.h", "zkannots.h"]
+PUBLIC_HEADERS = ["zkagg.h", "zksketch.h", "zkstore.h", "zkingest.h", "zkcomm.h", "zkwindow.h", "zkduration.h", "zkindex.h", "zkannindex.h", "zkspans.h", "zkannots.h", "zkbinannots.h"]
 LIB = PKG / "libzkagg.so"
 ARCH = os.environ.get("ZK_OFFLOAD_ARCH", "gfx950")
 

@@ -32,6 +32,7 @@
 // asked id's count or the output's size, and the expiry's probes stay inside their table (at most `slots`
 // steps), its mark words inside the segment's and its rewrite inside the new segment's slices.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <string.h>
 
 #include <algorithm>
@@ -45,6 +46,7 @@
 #include "zk_sp_staged.h"
 #include "zk_tracegen.h"
 #include "zkannots.h"
+#include "zkbinannots.h"
 #include "zkingest.h"
 
 namespace zk {
@@ -1217,6 +1219,48 @@ zk_status zk_an_query_ms(zk_an* h, double* ms) {
     return ZK_OK;
     ZK_GUARD_END
 }
+
+// ---- the binary-annotation store (zkbinannots.h): a typed facade over the core above --------------------
+// A zk_bn IS a zk_an behind another name: zk_bn_cols is zk_an_cols with `key` where `ts` is, the canonical
+// order reads the key as the signed 64-bit value the core sorts ts by, and the TYPE lies where the KIND does.
+// No kernel and no store code of its own; the types keep a zk_bn out of zk_an_expire / zk_an_adjusted_*.
+static_assert(sizeof(zk_bn_cols) == sizeof(zk_an_cols), "zk_bn_cols is zk_an_cols");
+static_assert(offsetof(zk_bn_cols, trace_id) == offsetof(zk_an_cols, trace_id) && offsetof(zk_bn_cols, span_id) == offsetof(zk_an_cols, span_id) &&
+                  offsetof(zk_bn_cols, key) == offsetof(zk_an_cols, ts) && offsetof(zk_bn_cols, value) == offsetof(zk_an_cols, value) &&
+                  offsetof(zk_bn_cols, ipv4) == offsetof(zk_an_cols, ipv4) && offsetof(zk_bn_cols, service_id) == offsetof(zk_an_cols, service_id) &&
+                  offsetof(zk_bn_cols, bits) == offsetof(zk_an_cols, bits),
+              "zk_bn_cols: key in the place of ts");
+static_assert(sizeof(uint64_t*) == sizeof(int64_t*), "a key column is read as a ts column");
+static_assert(ZK_BN_TYPE_MASK == ZK_AN_KIND_MASK && ZK_BN_HAS_HOST == ZK_AN_HAS_HOST && ZK_BN_PORT_SHIFT == ZK_AN_PORT_SHIFT,
+              "the bits word of a binary row is laid out as the core sorts it");
+
+static zk_an* bn_core(zk_bn* b) { return reinterpret_cast<zk_an*>(b); }
+
+zk_status zk_bn_create(const zk_an_config* cfg, zk_bn** out) {
+    if (!cfg || !out) return ZK_ERR_INVALID_ARG;
+    zk_an_config c = *cfg;
+    c.expire_chunk = 0;  // (ignored: no expiry)
+    zk_an* h = nullptr;
+    const zk_status st = zk_an_create(&c, &h);
+    *out = reinterpret_cast<zk_bn*>(h);
+    return st;
+}
+zk_status zk_bn_destroy(zk_bn* b) { return zk_an_destroy(bn_core(b)); }
+const char* zk_bn_last_error(const zk_bn* b) { return zk_an_last_error(reinterpret_cast<const zk_an*>(b)); }
+zk_status zk_bn_observe(zk_bn* b, const zk_bn_cols* in, uint64_t n, uint32_t flags) {
+    return zk_an_observe(bn_core(b), reinterpret_cast<const zk_an_cols*>(in), n, flags);
+}
+zk_status zk_bn_reset(zk_bn* b) { return zk_an_reset(bn_core(b)); }
+zk_status zk_bn_compact(zk_bn* b) { return zk_an_compact(bn_core(b)); }
+zk_status zk_bn_info(zk_bn* b, uint64_t* entries, uint64_t* segments, uint64_t* bytes) {
+    return zk_an_info(bn_core(b), entries, segments, bytes);
+}
+zk_status zk_bn_gather(zk_bn* b, const uint64_t* ids, uint32_t n, uint32_t flags, uint32_t* counts, zk_bn_cols* out, uint64_t cap,
+                       uint64_t* n_out) {
+    return zk_an_gather(bn_core(b), ids, n, flags, counts, reinterpret_cast<zk_an_cols*>(out), cap, n_out);
+}
+zk_status zk_bn_observe_ms(zk_bn* b, double out[3]) { return zk_an_observe_ms(bn_core(b), out); }
+zk_status zk_bn_query_ms(zk_bn* b, double* ms) { return zk_an_query_ms(bn_core(b), ms); }
 
 }  // extern "C"
 

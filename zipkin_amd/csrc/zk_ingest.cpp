@@ -207,6 +207,7 @@ struct BinAnn {
     uint32_t key_len = 0;
     const char* value = nullptr;  // (read for the annotation index only)
     uint32_t value_len = 0;
+    int32_t type = 0;  // field 3, the AnnotationType ordinal (read for the binary rows only); absent: 0
     Host host;
 };
 struct SpanT {
@@ -268,6 +269,8 @@ void read_binary_annotation(Rd& r, BinAnn* b) {
             r.str(&b->key, &b->key_len);
         else if (id == 2 && t == T_STRING)
             r.str(&b->value, &b->value_len);
+        else if (id == 3 && t == T_I32)
+            b->type = r.i32();
         else if (id == 4 && t == T_STRUCT)
             read_endpoint(r, &b->host);
         else
@@ -388,6 +391,7 @@ struct Decoded {
     int32_t span_name;  // ZK_INGEST_SPAN_NAMES: index into DecodeRange::span_names, -1: no name (id 0)
     uint32_t ix0 = 0, ix_n = 0;  // zk_ingest_spans_indexed: the record's entries in DecodeRange::ix
     uint32_t an0 = 0, an_n = 0;  // zk_ingest_spans_annotated: the record's rows in DecodeRange::rows
+    uint32_t bn0 = 0, bn_n = 0;  // zk_ingest_spans_annotated_binary: the record's rows in DecodeRange::brows
 };
 // an entry of the annotation index before its service id is known
 struct IxItem {
@@ -401,12 +405,19 @@ struct AnRow {
     int64_t ts;
     uint32_t ipv4, bits;
 };
+// a row of the binary-annotation store (zkbinannots.h) before its service id is known
+struct BnRow {
+    Item key;    // the host's name (-1: no host), the key's string and its hash
+    Item value;  // the value's string and its hash
+    uint32_t ipv4, bits;
+};
 struct DecodeRange {
     uint64_t lo = 0, hi = 0;
     std::vector<Decoded> recs;
     std::vector<Item> kv, ann;
     std::vector<IxItem> ix;
     std::vector<AnRow> rows;
+    std::vector<BnRow> brows;
     std::vector<std::string> names, strs;
     std::unordered_map<std::string, int32_t> name_ix;
     std::unordered_map<uint64_t, uint32_t> str_ix;
@@ -464,7 +475,7 @@ bool is_client_name(const Host& h) {
 
 // want_ix: 0 no index entries, 1 with the shouldIndex rule, 2 without it
 void decode_range(const uint8_t* buf, const uint64_t* offsets, uint32_t codec, bool strict, bool want_kv,
-                  bool want_ann, bool want_names, int want_ix, bool want_rows, DecodeRange* d) {
+                  bool want_ann, bool want_names, int want_ix, bool want_rows, bool want_brows, DecodeRange* d) {
     std::vector<uint8_t> scratch;
     SpanT s;
     std::vector<const Ann*> distinct;
@@ -608,6 +619,17 @@ void decode_range(const uint8_t* buf, const uint64_t* offsets, uint32_t codec, b
                                         a.host.present ? (uint32_t)a.host.ipv4 : 0u, bits});
             }
         rec.an_n = (uint32_t)d->rows.size() - rec.an0;
+        // ---- the binary-annotation store's rows: one per binary annotation, in the lists' order ----
+        rec.bn0 = (uint32_t)d->brows.size();
+        if (want_brows)
+            for (const BinAnn& b : s.banns) {
+                uint32_t bits = (b.type >= 0 && b.type <= 6) ? (uint32_t)b.type : 7u;
+                if (b.host.present) bits |= 8u | ((uint32_t)(uint16_t)b.host.port << 16);
+                const Item key = d->item_of(-1, b.key, b.key_len), val = d->item_of(-1, b.value, b.value_len);
+                d->brows.push_back(BnRow{Item{b.host.present ? d->name(b.host) : -1, key.str, key.hash}, val,
+                                         b.host.present ? (uint32_t)b.host.ipv4 : 0u, bits});
+            }
+        rec.bn_n = (uint32_t)d->brows.size() - rec.bn0;
         rec.kv_n = (uint32_t)d->kv.size() - rec.kv0;
         rec.ann_n = (uint32_t)d->ann.size() - rec.ann0;
         rec.ix_n = (uint32_t)d->ix.size() - rec.ix0;
@@ -778,16 +800,19 @@ const char* zk_ingest_last_error(const zk_ingest* g) { return g ? g->err.c_str()
 
 uint64_t zk_index_value_hash(const char* s, uint64_t len) { return zk_hash_string(s, len) | 1ull; }
 
-// zk_ingest_spans (ix == nullptr), zk_ingest_spans_indexed (items == nullptr) and zk_ingest_spans_annotated (an)
+// zk_ingest_spans (ix == nullptr), zk_ingest_spans_indexed (items == nullptr), zk_ingest_spans_annotated (an)
+// and zk_ingest_spans_annotated_binary (an and bn)
 static zk_status ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
                               uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
-                              zk_ingest_items* items, zk_ingest_index_items* ix, zk_ingest_annotation_rows* an = nullptr) {
+                              zk_ingest_items* items, zk_ingest_index_items* ix, zk_ingest_annotation_rows* an = nullptr,
+                              zk_ingest_binary_rows* bn = nullptr) {
     ZK_GUARD_BEGIN
     if (!g || !n_out || !n_rejected) return ZK_ERR_INVALID_ARG;
     *n_out = *n_rejected = 0;
     if (items) items->kv_n = items->ann_n = 0;
     if (ix) ix->n = 0;
     if (an) an->n = 0;
+    if (bn) bn->n = 0;
     if (n == 0) return ZK_OK;
     if (!buf || !offsets || !out || !out->trace_id || !out->span_id || !out->parent_id || !out->first_ts ||
         !out->last_ts || !out->service_id || !out->flags)
@@ -815,7 +840,7 @@ static zk_status ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* 
         d.lo = n * t / T;
         d.hi = n * (t + 1) / T;
         try {
-            decode_range(buf, offsets, codec, strict, want_kv, want_ann, want_names, want_ix, an != nullptr, &d);
+            decode_range(buf, offsets, codec, strict, want_kv, want_ann, want_names, want_ix, an != nullptr, bn != nullptr, &d);
         } catch (...) {
             d.err_index = d.lo;
             d.err_status = ZK_ERR_CAPACITY;
@@ -918,6 +943,23 @@ static zk_status ingest_spans(zk_ingest* g, const uint8_t* buf, const uint64_t* 
                 keep(it.value);
                 ++an->n;
             }
+            for (uint32_t q = r.bn0; q < r.bn0 + r.bn_n; ++q) {
+                if (bn->n >= bn->cap) {
+                    item_overflow = true;
+                    continue;
+                }
+                const BnRow& it = d.brows[q];
+                bn->trace_id[bn->n] = r.tid;
+                bn->span_id[bn->n] = r.sid;
+                bn->key[bn->n] = it.key.hash;
+                bn->value[bn->n] = it.value.hash;
+                bn->ipv4[bn->n] = it.ipv4;
+                bn->service_id[bn->n] = it.key.name >= 0 ? id_of(it.key.name) : 0u;
+                bn->bits[bn->n] = it.bits;
+                keep(it.key);
+                keep(it.value);
+                ++bn->n;
+            }
         }
         *n_rejected += d.rejected;
         if (d.err_index != UINT64_MAX) {  // the first error of the batch (ranges are in input order)
@@ -953,6 +995,16 @@ zk_status zk_ingest_spans_annotated(zk_ingest* g, const uint8_t* buf, const uint
     if (!an || !an->trace_id || !an->span_id || !an->ts || !an->value || !an->ipv4 || !an->service_id || !an->bits)
         return ZK_ERR_INVALID_ARG;
     return ingest_spans(g, buf, offsets, n, codec, flags, out, n_out, n_rejected, items, nullptr, an);
+}
+
+zk_status zk_ingest_spans_annotated_binary(zk_ingest* g, const uint8_t* buf, const uint64_t* offsets, uint64_t n, uint32_t codec,
+                                           uint32_t flags, const zk_span_cols* out, uint64_t* n_out, uint64_t* n_rejected,
+                                           zk_ingest_items* items, zk_ingest_annotation_rows* an, zk_ingest_binary_rows* bn) {
+    if (!an || !an->trace_id || !an->span_id || !an->ts || !an->value || !an->ipv4 || !an->service_id || !an->bits)
+        return ZK_ERR_INVALID_ARG;
+    if (!bn || !bn->trace_id || !bn->span_id || !bn->key || !bn->value || !bn->ipv4 || !bn->service_id || !bn->bits)
+        return ZK_ERR_INVALID_ARG;
+    return ingest_spans(g, buf, offsets, n, codec, flags, out, n_out, n_rejected, items, nullptr, an, bn);
 }
 
 zk_status zk_ingest_num_services(const zk_ingest* g, uint32_t* n) {

@@ -45,6 +45,7 @@
 #include "zk_guard.h"
 #include "zk_launch.h"
 #include "zkannots.h"
+#include "zkbinannots.h"
 #include "zkingest.h"
 
 namespace zk {
@@ -2521,12 +2522,24 @@ __device__ __forceinline__ bool ix_live(const IngArgs& a, const IxArgs& x, uint6
     *p = x.dropped ? (uint64_t)a.pos[i] : i;
     return (x.r_flags[*p] & ZK_F_HAS_ANNOTATIONS) != 0;
 }
+// kAll: every accepted fragment (a span without time annotations may carry binary ones); else ix_live
+template <bool kAll>
+__device__ __forceinline__ bool ix_live_t(const IngArgs& a, const IxArgs& x, uint64_t i, uint64_t* p) {
+    if constexpr (kAll) {
+        if (a.status[i] != kStOk) return false;
+        *p = x.dropped ? (uint64_t)a.pos[i] : i;
+        return true;
+    } else {
+        return ix_live(a, x, i, p);
+    }
+}
 
+template <bool kAll>
 __global__ __launch_bounds__(kIngWG) void k_ing_index_raw(IngArgs a, IxArgs x) {
     const uint64_t i = (uint64_t)blockIdx.x * kIngWG + threadIdx.x;
     uint32_t raw = 0;
     uint64_t p;
-    if (i < a.n && a.snappy && ix_live(a, x, i, &p)) {
+    if (i < a.n && a.snappy && ix_live_t<kAll>(a, x, i, &p)) {
         const uint64_t b = a.offsets[i], e = a.ends[i];
         uint32_t h[5];
         uint64_t v;
@@ -2762,6 +2775,18 @@ struct RwArgs {
     uint32_t* o_svc;
     uint32_t* o_bits;
     uint32_t strings;       // capture the value strings (no ZK_INGEST_NO_ROW_STRINGS)
+    // kBinary only (zk_ingest_dev_spans_annotated_binary): the binary rows' plan and columns. Their running
+    // bases across slices are IxArgs::ctl[5] / [6], ping-pong by parity as [1] / [2] are for the time rows.
+    uint64_t* b_cnt;        // [n] binary rows of fragment i
+    uint64_t* b_eoff;       // [n] exclusive scan of b_cnt within the slice
+    uint64_t* b_tid;        // the caller's seven binary-row columns
+    uint64_t* b_sid;
+    uint64_t* b_key;
+    uint64_t* b_val;
+    uint32_t* b_ipv4;
+    uint32_t* b_svc;
+    uint32_t* b_bits;
+    uint64_t b_cap;
 };
 
 // read_endpoint with the two fields the rows keep: field 1 (i32 -> ipv4) and field 2 (i16 -> port), by
@@ -2867,11 +2892,95 @@ __device__ uint32_t rows_walk(const IngArgs& a, const IxArgs& x, const RwArgs& w
     return m;
 }
 
+// The binary rows of one Span at [src, src + len): the walk of rows_walk over the field-8 lists (as
+// ix_next_bann reads a binary annotation), with field 3 (i32 -> the type) and the row-reading endpoint
+// reader for field 4. Count: lists unknown hosts and captures key and value bytes (the lane's last known
+// hash is kept per kind). Write: row k at `at + k` when that is below w.b_cap. Returns their number.
+template <bool kWrite>
+__device__ uint32_t bin_rows_walk(const IngArgs& a, const IxArgs& x, const RwArgs& w, const uint8_t* src, uint64_t len,
+                                  uint64_t at, uint64_t tid, uint64_t sid) {
+    typedef const uint8_t* P;
+    GItemIter<P> it{DRdT<P>{src, src + len, true}, 0, 8};
+    uint32_t m = 0;
+    uint64_t known_k = 0, known_v = 0;
+    while (it.next_elem()) {
+        P k = nullptr, v = nullptr, hn = nullptr;
+        uint32_t kl = 0, vl = 0, hl = 0, ip = 0, port = 0;
+        int32_t ty = 0;
+        bool host = false;
+        for (;;) {
+            uint8_t t;
+            int16_t id;
+            if (!it.r.field(&t, &id)) break;
+            if (id == 1 && t == T_STRING)
+                it.r.str(&k, &kl);
+            else if (id == 2 && t == T_STRING)
+                it.r.str(&v, &vl);
+            else if (id == 3 && t == T_I32)
+                ty = it.r.i32();
+            else if (id == 4 && t == T_STRUCT) {
+                host = true;
+                read_endpoint_row(it.r, &hn, &hl, &ip, &port);
+            } else
+                skip_flat(it.r, t);
+        }
+        if (!it.r.ok) break;  // (the decoder read these bytes: never taken)
+        uint32_t id = 0;
+        if (host) {
+            if (!hn || hl == 0) {
+                hn = a.unknown;
+                hl = kUnknownLen;
+            }
+            uint64_t h;
+            id = kNoId;
+            const bool found = resolve16_id(a, hn, hl, &h, &id);
+            if constexpr (kWrite) {
+                if (!found) atomicAdd(&x.ctl[3], 1ull);
+            } else if (!found) {
+                const unsigned long long q = atomicAdd(&a.icnt[3], 1ull);
+                if (q < a.x_cap) {  // (past it the host sees the count, grows the list and counts the slice again)
+                    a.x_hash[q] = h;
+                    a.x_ptr[q] = (uint64_t)(uintptr_t)hn;
+                    a.x_len[q] = hl;
+                    a.x_keep[q] = 1u;
+                    a.x_status[q] = kStOk;
+                    a.x_list[q] = (uint32_t)q;
+                }
+            }
+        }
+        const bool kk = k != nullptr && kl > 0, vv = v != nullptr && vl > 0;
+        if constexpr (kWrite) {
+            const uint64_t q = at + m;
+            if (q < w.b_cap) {
+                w.b_tid[q] = tid;
+                w.b_sid[q] = sid;
+                w.b_key[q] = d_hash(k, kk ? kl : 0u);
+                w.b_val[q] = d_hash(v, vv ? vl : 0u);
+                w.b_ipv4[q] = host ? ip : 0u;
+                w.b_svc[q] = host ? id : 0u;
+                w.b_bits[q] = ((uint32_t)ty <= 6u ? (uint32_t)ty : ZK_BN_TYPE_OTHER) |
+                              (host ? (ZK_BN_HAS_HOST | (port << ZK_BN_PORT_SHIFT)) : 0u);
+            }
+        } else if (w.strings) {
+            // (a full set fails the probe and counts in icnt[4]: the host grows it and counts the slice again)
+            const uint64_t hk = d_hash(k, kk ? kl : 0u);
+            if (hk != known_k && capture_string(a, hk, kk ? k : a.unknown, kk ? kl : 0u, kk ? k : a.unknown)) known_k = hk;
+            const uint64_t hv = d_hash(v, vv ? vl : 0u);
+            if (hv != known_v && capture_string(a, hv, vv ? v : a.unknown, vv ? vl : 0u, vv ? v : a.unknown)) known_v = hv;
+        }
+        ++m;
+    }
+    return m;
+}
+
+// kBinary = false: zk_ingest_dev_spans_annotated's kernels. kBinary = true: every ACCEPTED fragment is live, and
+// the field-8 walk runs behind the field-6 walk over the Span this lane has just decompressed.
+template <bool kBinary>
 __global__ __launch_bounds__(kIngWG) void k_ing_rows_count(IngArgs a, IxArgs x, RwArgs w) {
     const uint64_t i = x.lo + (uint64_t)blockIdx.x * kIngWG + threadIdx.x;
-    uint64_t p, len, n = 0;
+    uint64_t p, len, n = 0, nb = 0;
     uint32_t core = 0;
-    if (i < x.hi && ix_live(a, x, i, &p)) {
+    if (i < x.hi && ix_live_t<kBinary>(a, x, i, &p)) {
         const uint8_t* src = ix_span(a, x, i, &len);
         bool ok = true;
         if (a.snappy) {
@@ -2881,23 +2990,40 @@ __global__ __launch_bounds__(kIngWG) void k_ing_rows_count(IngArgs a, IxArgs x, 
             if (!ok) atomicAdd(&x.ctl[3], 1ull);  // (the decoder read these bytes: never taken)
         }
         if (ok) n = rows_walk<false>(a, x, w, src, len, 0, 0, 0, &core);
+        if constexpr (kBinary) {
+            if (ok) nb = bin_rows_walk<false>(a, x, w, src, len, 0, 0, 0);
+        }
     }
-    if (i < x.hi) x.cnt[i] = n;
-    // the core kinds of the wave, one atomic per wave, and only while the word lacks one of them
+    if (i < x.hi) {
+        x.cnt[i] = n;
+        if constexpr (kBinary) w.b_cnt[i] = nb;
+    }
+    // the core kinds of the wave, one atomic per wave, and only while the word lacks one of them (every lane
+    // of the wave reaches the reduction: no lane has returned above)
     for (int d = 32; d > 0; d >>= 1) core |= (uint32_t)__shfl_xor((int)core, d);
     if (__lane_id() == 0 && core && (x.ctl[4] & core) != core) atomicOr(&x.ctl[4], (unsigned long long)core);
 }
 
+template <bool kBinary>
 __global__ __launch_bounds__(kIngWG) void k_ing_rows_write(IngArgs a, IxArgs x, RwArgs w) {
     const uint64_t i = x.lo + (uint64_t)blockIdx.x * kIngWG + threadIdx.x;
     if (i >= x.hi) return;
     const uint64_t base = x.ctl[1 + x.parity], n = x.cnt[i], at = base + x.eoff[i];
     if (i == x.hi - 1) x.ctl[1 + (x.parity ^ 1u)] = at + n;  // the rows before the next slice
-    if (n == 0) return;
+    uint64_t nb = 0, bat = 0;
+    if constexpr (kBinary) {
+        nb = w.b_cnt[i];
+        bat = x.ctl[5 + x.parity] + w.b_eoff[i];
+        if (i == x.hi - 1) x.ctl[5 + (x.parity ^ 1u)] = bat + nb;  // the binary rows before the next slice
+    }
+    if (n == 0 && nb == 0) return;  // (a fragment with binary rows and no time rows is still walked)
     uint64_t p, len;
-    if (!ix_live(a, x, i, &p)) return;
+    if (!ix_live_t<kBinary>(a, x, i, &p)) return;
     const uint8_t* src = ix_span(a, x, i, &len);
-    rows_walk<true>(a, x, w, src, len, at, x.r_tid[p], w.r_sid[p], nullptr);
+    if (n) rows_walk<true>(a, x, w, src, len, at, x.r_tid[p], w.r_sid[p], nullptr);
+    if constexpr (kBinary) {
+        if (nb) bin_rows_walk<true>(a, x, w, src, len, bat, x.r_tid[p], w.r_sid[p]);
+    }
 }
 
 }  // namespace
@@ -2963,6 +3089,8 @@ struct zk_ingest_dev : zk_ing_dict {  // (the base: the service dictionary)
     hipEvent_t rw_ev[2] = {nullptr, nullptr};  // around the last pass
     bool rw_timed = false;
     uint64_t rw_slices = 0;                // slices of the last pass
+    uint8_t* bn_w = nullptr;               // the combined pass's second per-fragment count and offset (2 x 8 B)
+    uint64_t bn_w_cap = 0;                 // fragments it holds
     std::string err;
 };
 
@@ -3089,6 +3217,7 @@ zk_status zk_ingest_dev_destroy(zk_ingest_dev* g) {
     hipFree(g->istage);
     hipFree(g->multi);
     hipFree(g->ix_ctl);
+    hipFree(g->bn_w);
     for (hipEvent_t e : g->ix_ev)
         if (e) hipEventDestroy(e);
     for (hipEvent_t e : g->rw_ev)
@@ -3810,13 +3939,16 @@ hipError_t size_ix_ctl(zk_ingest_dev* g, uint64_t slices) {
 // fragment larger than all of it. a.scratch / a.scratch_cap and x.ctl are set for the pass; *need: the
 // scan's temporary bytes (g->cub holds them).
 zk_status lay_out_slices(zk_ingest_dev* g, IngArgs& a, IxArgs& x, hipStream_t s, const char* what,
-                         std::vector<uint64_t>* bounds_out, size_t* need_out) {
+                         std::vector<uint64_t>* bounds_out, size_t* need_out, bool all_accepted = false) {
     const uint64_t n = a.n, n1 = n + 1;
     const dim3 blk(kIngWG);
     ING_HIP(g, hipMemsetAsync(x.ctl, 0, 8 * 8, s));
     ING_HIP(g, hipMemsetAsync(a.icnt + 3, 0, 4 * 8, s));
     ING_HIP(g, hipMemsetAsync(x.raw + n, 0, 8, s));
-    ING_HIP(g, launch_checked("k_ing_index_raw", k_ing_index_raw, dim3((unsigned)((n + kIngWG - 1) / kIngWG)), blk, 0, s, a, x));
+    if (all_accepted)  // (the combined rows pass: a span without time annotations may carry binary ones)
+        ING_HIP(g, launch_checked("k_ing_index_raw", k_ing_index_raw<true>, dim3((unsigned)((n + kIngWG - 1) / kIngWG)), blk, 0, s, a, x));
+    else
+        ING_HIP(g, launch_checked("k_ing_index_raw", k_ing_index_raw<false>, dim3((unsigned)((n + kIngWG - 1) / kIngWG)), blk, 0, s, a, x));
     size_t need = 0;
     ING_HIP(g, hipcub::DeviceScan::ExclusiveSum(nullptr, need, x.raw, x.raw_off, (int)n1, s));
     if (need > g->cub_cap) {
@@ -4002,8 +4134,11 @@ zk_status finish_indexed(zk_ingest_dev* g, zk_status st, const IngBatchState& bs
 // accepted fragments into the seven device columns of an, in the host decoder's order. The stream is idle
 // when this starts and when it returns. Per slice: count (which also lists new hosts and captures new
 // value strings), the new strings to the host map, the new hosts through D3 / D4, scan, write.
+// With bn (zk_ingest_dev_spans_annotated_binary) the kBinary = true kernels run instead: every accepted fragment is
+// live, the count kernel counts both lists over one decompression, a second scan places the binary rows, and
+// the write kernel fills both sets of columns.
 zk_status rows_pass(zk_ingest_dev* g, const IngBatchState& bs, uint32_t flags, const zk_span_cols* out,
-                    zk_ingest_annotation_rows* an) {
+                    zk_ingest_annotation_rows* an, zk_ingest_binary_rows* bn = nullptr) {
     IngArgs a = bs.a;
     hipStream_t s = g->stream;
     ING_HIP(g, hipSetDevice(g->device));
@@ -4035,6 +4170,26 @@ zk_status rows_pass(zk_ingest_dev* g, const IngBatchState& bs, uint32_t flags, c
     w.o_svc = an->service_id;
     w.o_bits = an->bits;
     w.strings = strings ? 1u : 0u;
+    if (bn) {
+        const uint64_t n1 = a.n + 1;
+        if (n1 > g->bn_w_cap) {
+            hipFree(g->bn_w);
+            g->bn_w = nullptr;
+            g->bn_w_cap = 0;
+            ING_HIP(g, hipMalloc(&g->bn_w, 2 * align256(8 * n1)));
+            g->bn_w_cap = n1;
+        }
+        w.b_cnt = (uint64_t*)g->bn_w;
+        w.b_eoff = (uint64_t*)(g->bn_w + align256(8 * g->bn_w_cap));
+        w.b_tid = bn->trace_id;
+        w.b_sid = bn->span_id;
+        w.b_key = bn->key;
+        w.b_val = bn->value;
+        w.b_ipv4 = bn->ipv4;
+        w.b_svc = bn->service_id;
+        w.b_bits = bn->bits;
+        w.b_cap = bn->cap;
+    }
     a.scratch = g->scratch;
     a.scratch_cap = g->scratch_cap;
     a.unknown = g->arena;
@@ -4043,7 +4198,7 @@ zk_status rows_pass(zk_ingest_dev* g, const IngBatchState& bs, uint32_t flags, c
     std::vector<uint64_t> bounds;
     size_t need = 0;
     {
-        const zk_status st = lay_out_slices(g, a, x, s, "rows pass", &bounds, &need);
+        const zk_status st = lay_out_slices(g, a, x, s, "rows pass", &bounds, &need, bn != nullptr);
         if (st != ZK_OK) return st;
     }
     unsigned long long* const hc = g->h_counts;
@@ -4066,7 +4221,10 @@ zk_status rows_pass(zk_ingest_dev* g, const IngBatchState& bs, uint32_t flags, c
         }
         bind_items(g, a, ax);
         ING_HIP(g, hipMemsetAsync(a.icnt + 2, 0, 3 * 8, s));  // captured strings, extra names, a full set
-        ING_HIP(g, launch_checked("k_ing_rows_count", k_ing_rows_count, grid, blk, 0, s, a, x, w));
+        if (bn)
+            ING_HIP(g, launch_checked("k_ing_rows_count", k_ing_rows_count<true>, grid, blk, 0, s, a, x, w));
+        else
+            ING_HIP(g, launch_checked("k_ing_rows_count", k_ing_rows_count<false>, grid, blk, 0, s, a, x, w));
         ING_HIP(g, hipMemcpyAsync(hc, a.icnt + 2, 3 * 8, hipMemcpyDeviceToHost, s));
         ING_HIP(g, hipStreamSynchronize(s));
         const uint64_t fresh = hc[0], extra = hc[1], set_full = hc[2];
@@ -4089,13 +4247,19 @@ zk_status rows_pass(zk_ingest_dev* g, const IngBatchState& bs, uint32_t flags, c
             if (st != ZK_OK) return leave(st, g->err);
         }
         ING_HIP(g, hipcub::DeviceScan::ExclusiveSum(g->cub, need, x.cnt + x.lo, x.eoff + x.lo, (int)m, s));
-        ING_HIP(g, launch_checked("k_ing_rows_write", k_ing_rows_write, grid, blk, 0, s, a, x, w));
+        if (bn) {
+            ING_HIP(g, hipcub::DeviceScan::ExclusiveSum(g->cub, need, w.b_cnt + x.lo, w.b_eoff + x.lo, (int)m, s));
+            ING_HIP(g, launch_checked("k_ing_rows_write", k_ing_rows_write<true>, grid, blk, 0, s, a, x, w));
+        } else {
+            ING_HIP(g, launch_checked("k_ing_rows_write", k_ing_rows_write<false>, grid, blk, 0, s, a, x, w));
+        }
         parity ^= 1u;
         ++k;
     }
     ING_HIP(g, hipEventRecord(g->rw_ev[1], s));
     ING_HIP(g, hipMemcpyAsync(hc, x.ctl + 1 + parity, 8, hipMemcpyDeviceToHost, s));
     ING_HIP(g, hipMemcpyAsync(hc + 1, x.ctl + 3, 2 * 8, hipMemcpyDeviceToHost, s));
+    ING_HIP(g, hipMemcpyAsync(hc + 3, x.ctl + 5 + parity, 8, hipMemcpyDeviceToHost, s));
     ING_HIP(g, hipStreamSynchronize(s));
     g->rw_timed = true;
     g->rw_slices = bounds.size() - 1;
@@ -4108,8 +4272,12 @@ zk_status rows_pass(zk_ingest_dev* g, const IngBatchState& bs, uint32_t flags, c
             if (hc[2] >> c & 1ull) g->strings.emplace(zk_hash_string(kCore[c], 2), kCore[c]);
     }
     an->n = std::min<uint64_t>(total, an->cap);
+    const uint64_t btotal = bn ? hc[3] : 0;
+    if (bn) bn->n = std::min<uint64_t>(btotal, bn->cap);
     if (total > an->cap)
         return dfail(g, ZK_ERR_CAPACITY, "annotation row buffers too small: " + std::to_string(total) + " rows");
+    if (bn && btotal > bn->cap)
+        return dfail(g, ZK_ERR_CAPACITY, "binary annotation row buffers too small: " + std::to_string(btotal) + " rows");
     return ZK_OK;
 }
 
@@ -4118,11 +4286,15 @@ bool an_valid(const zk_ingest_annotation_rows* an) {
 }
 
 // after the decode of an annotated call: as finish_indexed, with the rows pass
+bool bn_valid(const zk_ingest_binary_rows* bn) {
+    return bn && bn->trace_id && bn->span_id && bn->key && bn->value && bn->ipv4 && bn->service_id && bn->bits;
+}
+
 zk_status finish_annotated(zk_ingest_dev* g, zk_status st, const IngBatchState& bs, uint32_t flags, const zk_span_cols* out,
-                           zk_ingest_annotation_rows* an) {
+                           zk_ingest_annotation_rows* an, zk_ingest_binary_rows* bn = nullptr) {
     if (!bs.done || (st != ZK_OK && st != ZK_ERR_CAPACITY)) return st;
     const std::string item_err = g->err;
-    const zk_status sr = rows_pass(g, bs, flags, out, an);
+    const zk_status sr = rows_pass(g, bs, flags, out, an, bn);
     if (sr != ZK_OK) return sr;
     if (st != ZK_OK) g->err = item_err;
     return st;
@@ -4219,6 +4391,35 @@ zk_status zk_ingest_dev_spans_multi_annotated(zk_ingest_dev* g, uint32_t nb, con
     IngBatchState bs;
     const zk_status st = ingest_multi(g, nb, bufs, offsets, ns, codec, flags, out, n_out, n_rejected, items, &bs);
     return finish_annotated(g, st, bs, flags, out, an);
+    ZK_GUARD_END
+}
+
+zk_status zk_ingest_dev_spans_annotated_binary(zk_ingest_dev* g, const uint8_t* buf, const uint64_t* offsets, uint64_t n,
+                                               uint32_t codec, uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
+                                               uint64_t* n_rejected, zk_ingest_items* items, zk_ingest_annotation_rows* an,
+                                               zk_ingest_binary_rows* bn) {
+    ZK_GUARD_BEGIN
+    if (!g || !an_valid(an) || !bn_valid(bn)) return ZK_ERR_INVALID_ARG;  // (before any device is touched)
+    an->n = 0;
+    bn->n = 0;
+    IngBatchState bs;
+    const zk_status st = ingest_batch(g, buf, offsets, n, codec, flags, out, n_out, n_rejected, items, nullptr, &bs);
+    return finish_annotated(g, st, bs, flags, out, an, bn);
+    ZK_GUARD_END
+}
+
+zk_status zk_ingest_dev_spans_multi_annotated_binary(zk_ingest_dev* g, uint32_t nb, const uint8_t* const* bufs,
+                                                     const uint64_t* const* offsets, const uint64_t* ns, uint32_t codec,
+                                                     uint32_t flags, const zk_span_cols* out, uint64_t* n_out,
+                                                     uint64_t* n_rejected, zk_ingest_items* items,
+                                                     zk_ingest_annotation_rows* an, zk_ingest_binary_rows* bn) {
+    ZK_GUARD_BEGIN
+    if (!g || !an_valid(an) || !bn_valid(bn)) return ZK_ERR_INVALID_ARG;
+    an->n = 0;
+    bn->n = 0;
+    IngBatchState bs;
+    const zk_status st = ingest_multi(g, nb, bufs, offsets, ns, codec, flags, out, n_out, n_rejected, items, &bs);
+    return finish_annotated(g, st, bs, flags, out, an, bn);
     ZK_GUARD_END
 }
 

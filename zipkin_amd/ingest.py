@@ -131,13 +131,20 @@ class SpanDecoder:
         return cols.take(slice(0, nout.value)), int(nrej.value), items
 
     def decode_annotated(self, blobs, *, snappy: bool = True, strict: bool = True, span_names: bool = False,
-                         row_cap: int | None = None, one_thread: bool = False):
+                         row_cap: int | None = None, one_thread: bool = False, binary: bool = False,
+                         binary_cap: int | None = None):
         """decode() that also returns the annotation store's rows (zk_ingest_spans_annotated):
         (SpanColumns, rejected, annotstore.AnnotationRows), one row per time annotation of every accepted
         span, in record order and the annotation list's order. row_cap: the rows to allow for (default 8
         per fragment, at least 16); a batch with more raises ZK_ERR_CAPACITY, and the exception's `rows`
-        then holds the first row_cap rows. A batch that may hold more says so with row_cap."""
+        then holds the first row_cap rows. A batch that may hold more says so with row_cap.
+        binary=True (zk_ingest_spans_annotated_binary) appends the binary-annotation store's rows, a
+        binannotstore.BinaryAnnotationRows with one row per binary annotation of every accepted span:
+        (cols, rejected, rows, brows). binary_cap: the binary rows to allow for (default 8 per fragment, at
+        least 16); the two capacities are judged independently, and the exception of a short one carries
+        `rows` and `brows`, each the prefix that fitted."""
         from .annotstore import AnnotationRows
+        from .binannotstore import BinaryAnnotationRows
 
         buf, offsets, n = _pack(blobs)
         cols = SpanColumns.empty(n)
@@ -149,14 +156,28 @@ class SpanDecoder:
         flags = (_abi.ZK_INGEST_STRICT if strict else 0) | (_abi.ZK_INGEST_ONE_THREAD if one_thread else 0)
         flags |= _abi.ZK_INGEST_SPAN_NAMES if span_names else 0
         ab = cols.abi()
-        st = self._L.zk_ingest_spans_annotated(self._h, buf.ctypes.data, offsets.ctypes.data, n, codec, flags,
-                                               C.byref(ab), C.byref(nout), C.byref(nrej), None, C.byref(an))
+        brows = None
+        if binary:
+            bcap = int(binary_cap) if binary_cap is not None else max(16, 8 * n)
+            brows = BinaryAnnotationRows.empty(bcap)
+            bn = brows.ingest_abi(cap=bcap, n=0)
+            st = self._L.zk_ingest_spans_annotated_binary(self._h, buf.ctypes.data, offsets.ctypes.data, n, codec, flags,
+                                                          C.byref(ab), C.byref(nout), C.byref(nrej), None, C.byref(an),
+                                                          C.byref(bn))
+            brows = brows.take(slice(0, int(bn.n)))
+        else:
+            st = self._L.zk_ingest_spans_annotated(self._h, buf.ctypes.data, offsets.ctypes.data, n, codec, flags,
+                                                   C.byref(ab), C.byref(nout), C.byref(nrej), None, C.byref(an))
         rows = rows.take(slice(0, int(an.n)))
         if st == _abi.ZK_ERR_CAPACITY:
             e = _abi.ZkError(st, self._L.zk_ingest_last_error(self._h).decode() or _abi.status_str(st))
             e.rows = rows
+            e.brows = brows
+            e.cols = cols.take(slice(0, nout.value))
             raise e
         self._check(st)
+        if binary:
+            return cols.take(slice(0, nout.value)), int(nrej.value), rows, brows
         return cols.take(slice(0, nout.value)), int(nrej.value), rows
 
     @property
@@ -204,12 +225,17 @@ class SpanDecoder:
     def span_names(self) -> List[str]:
         return [self.span_name(i) for i in range(self.num_span_names)]
 
-    def string(self, h: int) -> str:
+    def bytes(self, h: int) -> bytes:
+        """The bytes behind a key / value hash, with their length (a binary annotation's value may hold NUL
+        and bytes that are no UTF-8)."""
         ln = C.c_uint64()
         self._check(self._L.zk_ingest_string(self._h, h, None, 0, C.byref(ln)))
         buf = C.create_string_buffer(max(1, ln.value))
         self._check(self._L.zk_ingest_string(self._h, h, buf, ln.value, C.byref(ln)))
-        return buf.raw[: ln.value].decode("utf-8", "surrogateescape")
+        return buf.raw[: ln.value]
+
+    def string(self, h: int) -> str:
+        return self.bytes(h).decode("utf-8", "surrogateescape")
 
 
 def snappy_uncompress(data: bytes) -> bytes:
@@ -226,7 +252,9 @@ def snappy_uncompress(data: bytes) -> bytes:
     return out[: n.value].tobytes()
 
 
-def _one_pass(indexed: bool, annotated: bool) -> None:
+def _one_pass(indexed: bool, annotated: bool, binary: bool = False) -> None:
+    if binary and not annotated:
+        raise ValueError("binary=True needs annotated=True: the binary rows come from the rows pass (no binary-only call)")
     if indexed and annotated:
         raise ValueError("annotated=True with indexed=True: no call runs the index pass and the rows pass together")
 
@@ -280,7 +308,8 @@ class DeviceSpanDecoder:
     def decode_device(self, buf, offsets, n: int, *, snappy: bool = True, strict: bool = True, out=None,
                       items: bool = False, item_cap: int | None = None, span_names: bool = False,
                       indexed: bool = False, client_rule: bool = True, index_cap: int | None = None,
-                      annotated: bool = False, row_cap: int | None = None, row_strings: bool = True):
+                      annotated: bool = False, row_cap: int | None = None, row_strings: bool = True,
+                      binary: bool = False, binary_cap: int | None = None):
         """-> (DeviceColumns with .n = records written, rejected), or with items=True
         (cols, rejected, (kv_service, kv_key), (ann_service, ann_value)): the span indexer's items as
         device tensors (int32 service ids of this decoder, int64 hashes = uint64 bit patterns), in no
@@ -299,12 +328,21 @@ class DeviceSpanDecoder:
         per fragment, at least 16; a batch with more is decoded again with 4x the room).
         row_strings=False (ZK_INGEST_NO_ROW_STRINGS) leaves the rows' value strings uncaptured: the
         rows are the same, string() does not learn them. annotated and indexed together are a
-        ValueError: no C call runs both passes."""
-        _one_pass(indexed, annotated)
+        ValueError: no C call runs both passes.
+        binary=True with annotated=True (zk_ingest_dev_spans_annotated_binary) appends, behind the rows, the
+        binary-annotation store's rows, a binannotstore.DeviceBinaryAnnotationRows in the host decoder's
+        order, from the same rows pass. binary_cap: the binary rows to allow for (default 8 per fragment, at
+        least 16; a batch with more is decoded again with 4x the room). row_strings covers keys and values
+        too. binary=True without annotated=True is a ValueError."""
+        _one_pass(indexed, annotated, binary)
         L, h = self._L, self._h
         bp, op = buf.data_ptr(), offsets.data_ptr()
 
-        def call(codec, flags, ab, nout, nrej, it, ix=None, an=None):
+        def call(codec, flags, ab, nout, nrej, it, ix=None, an=None, bn=None):
+            if bn is not None:
+                return L.zk_ingest_dev_spans_annotated_binary(h, bp, op, n, codec, flags, C.byref(ab), C.byref(nout),
+                                                              C.byref(nrej), None if it is None else C.byref(it),
+                                                              C.byref(an), C.byref(bn))
             if an is not None:
                 return L.zk_ingest_dev_spans_annotated(h, bp, op, n, codec, flags, C.byref(ab), C.byref(nout), C.byref(nrej),
                                                        None if it is None else C.byref(it), C.byref(an))
@@ -317,17 +355,19 @@ class DeviceSpanDecoder:
                                                C.byref(it))
 
         return self._run(call, n, snappy, strict, out, items, item_cap, span_names, indexed, client_rule, index_cap,
-                         annotated, row_cap, row_strings)
+                         annotated, row_cap, row_strings, binary, binary_cap)
 
     def decode_device_many(self, batches, *, snappy: bool = True, strict: bool = True, out=None,
                            items: bool = False, item_cap: int | None = None, span_names: bool = False,
                            indexed: bool = False, client_rule: bool = True, index_cap: int | None = None,
-                           annotated: bool = False, row_cap: int | None = None, row_strings: bool = True):
+                           annotated: bool = False, row_cap: int | None = None, row_strings: bool = True,
+                           binary: bool = False, binary_cap: int | None = None):
         """Several HBM-resident batches [(buf, offsets, n), ...] in ONE decode
         (zk_ingest_dev_spans_multi, zk_ingest_dev_spans_multi_indexed with indexed=True, or
         zk_ingest_dev_spans_multi_annotated with annotated=True): the results of decode_device over
-        the batches joined in order, for one set of launches and one host round trip."""
-        _one_pass(indexed, annotated)
+        the batches joined in order, for one set of launches and one host round trip. binary=True:
+        zk_ingest_dev_spans_multi_annotated_binary."""
+        _one_pass(indexed, annotated, binary)
         L, h = self._L, self._h
         nb = len(batches)
         n = sum(int(b[2]) for b in batches)
@@ -335,7 +375,11 @@ class DeviceSpanDecoder:
         offs = (C.c_void_p * max(1, nb))(*[b[1].data_ptr() if int(b[2]) else None for b in batches])
         ns = (C.c_uint64 * max(1, nb))(*[int(b[2]) for b in batches])
 
-        def call(codec, flags, ab, nout, nrej, it, ix=None, an=None):
+        def call(codec, flags, ab, nout, nrej, it, ix=None, an=None, bn=None):
+            if bn is not None:
+                return L.zk_ingest_dev_spans_multi_annotated_binary(h, nb, bufs, offs, ns, codec, flags, C.byref(ab), C.byref(nout),
+                                                                    C.byref(nrej), None if it is None else C.byref(it),
+                                                                    C.byref(an), C.byref(bn))
             if an is not None:
                 return L.zk_ingest_dev_spans_multi_annotated(h, nb, bufs, offs, ns, codec, flags, C.byref(ab), C.byref(nout),
                                                              C.byref(nrej), None if it is None else C.byref(it), C.byref(an))
@@ -346,10 +390,10 @@ class DeviceSpanDecoder:
                                                C.byref(nrej), None if it is None else C.byref(it))
 
         return self._run(call, n, snappy, strict, out, items, item_cap, span_names, indexed, client_rule, index_cap,
-                         annotated, row_cap, row_strings)
+                         annotated, row_cap, row_strings, binary, binary_cap)
 
     def _run(self, call, n, snappy, strict, out, items, item_cap, span_names=False, indexed=False, client_rule=True,
-             index_cap=None, annotated=False, row_cap=None, row_strings=True):
+             index_cap=None, annotated=False, row_cap=None, row_strings=True, binary=False, binary_cap=None):
         import torch
 
         from .columns import DeviceColumns
@@ -371,7 +415,8 @@ class DeviceSpanDecoder:
         cap = item_cap if item_cap is not None else 2 * n + 16
         icap = int(index_cap) if index_cap is not None else max(16, 8 * n)
         rcap = int(row_cap) if row_cap is not None else max(16, 8 * n)
-        it = ix = an = None
+        bcap = int(binary_cap) if binary_cap is not None else max(16, 8 * n)
+        it = ix = an = bn = None
         while True:
             if items:
                 ks = torch.empty(cap, dtype=torch.int32, device=dev)
@@ -388,14 +433,19 @@ class DeviceSpanDecoder:
                 # (fresh tensors per decode: a store that observed the last ones may still read them)
                 row = [torch.empty(max(1, rcap), dtype=torch.int64 if k < 4 else torch.int32, device=dev) for k in range(7)]
                 an = _abi.zk_ingest_annotation_rows(*[t.data_ptr() for t in row], rcap, 0)
-                st = call(codec, flags, ab, nout, nrej, it, None, an)
+                if binary:
+                    brow = [torch.empty(max(1, bcap), dtype=torch.int64 if k < 4 else torch.int32, device=dev) for k in range(7)]
+                    bn = _abi.zk_ingest_binary_rows(*[t.data_ptr() for t in brow], bcap, 0)
+                st = call(codec, flags, ab, nout, nrej, it, None, an, bn)
             else:
                 st = call(codec, flags, ab, nout, nrej, it)
             if st == _abi.ZK_ERR_CAPACITY:
                 grow_items = items and (it.kv_n == cap or it.ann_n == cap)
                 grow_index = indexed and ix.n == icap
                 grow_rows = annotated and an.n == rcap
-                if grow_items or grow_index or grow_rows:  # more items / entries / rows than guessed: the batch again
+                grow_brows = binary and bn.n == bcap
+                if grow_items or grow_index or grow_rows or grow_brows:  # more items / entries / rows than guessed: the batch again
+                    bcap = max(16, bcap * 4) if grow_brows else bcap
                     cap = cap * 4 if grow_items else cap
                     icap = max(16, icap * 4) if grow_index else icap
                     rcap = max(16, rcap * 4) if grow_rows else rcap
@@ -414,6 +464,10 @@ class DeviceSpanDecoder:
             from .annotstore import DeviceAnnotationRows
 
             res += (DeviceAnnotationRows(*[t[: an.n] for t in row]),)
+        if binary:
+            from .binannotstore import DeviceBinaryAnnotationRows
+
+            res += (DeviceBinaryAnnotationRows(*[t[: bn.n] for t in brow]),)
         return res
 
     def index_stats(self) -> dict:
@@ -444,11 +498,21 @@ class DeviceSpanDecoder:
         memo[h] = v
         return v
 
+    def bytes(self, h: int) -> bytes:
+        """The bytes behind a hash, with their length: string() without the decoding (a binary annotation's
+        value may hold NUL and bytes that are no UTF-8)."""
+        h = int(h) & 0xFFFFFFFFFFFFFFFF
+        ln = C.c_uint64()
+        self._check(self._L.zk_ingest_dev_string(self._h, h, None, 0, C.byref(ln)))
+        buf = C.create_string_buffer(max(1, ln.value))
+        self._check(self._L.zk_ingest_dev_string(self._h, h, buf, ln.value, C.byref(ln)))
+        return buf.raw[: ln.value]
+
     def decode(self, blobs: Sequence[bytes], *, snappy: bool = True, strict: bool = True, items: bool = False,
                span_names: bool = False, indexed: bool = False, client_rule: bool = True,
                index_cap: int | None = None, annotated: bool = False, row_cap: int | None = None,
-               row_strings: bool = True):
-        _one_pass(indexed, annotated)
+               row_strings: bool = True, binary: bool = False, binary_cap: int | None = None):
+        _one_pass(indexed, annotated, binary)
         import torch
 
         dev = f"cuda:{self.device}"
@@ -460,7 +524,8 @@ class DeviceSpanDecoder:
         off = torch.from_numpy(offsets).to(dev)
         return self.decode_device(buf, off, len(blobs), snappy=snappy, strict=strict, items=items,
                                   span_names=span_names, indexed=indexed, client_rule=client_rule, index_cap=index_cap,
-                                  annotated=annotated, row_cap=row_cap, row_strings=row_strings)
+                                  annotated=annotated, row_cap=row_cap, row_strings=row_strings, binary=binary,
+                                  binary_cap=binary_cap)
 
     @property
     def num_services(self) -> int:

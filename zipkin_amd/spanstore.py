@@ -26,6 +26,7 @@ import numpy as np
 from . import _abi
 from .annotstore import (KIND_CR, KIND_CS, KIND_NAMES, KIND_SR, KIND_SS, LOOPBACK_IPV4, Annotation, AnnotationRow, Endpoint,
                          annotation_key)
+from .binannotstore import BinaryAnnotation, BinaryAnnotationRow, binary_annotation_key
 from .columns import COLUMNS, ENTRY_COLUMNS, SUMMARY_HEAD, DeviceColumns  # noqa: F401  (zk_sp_summary's head and entries)
 
 INT64_MIN, INT64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -110,10 +111,18 @@ class Trace:
     a list in canonical order, `annotations` maps span id -> that list, and the first and last of a span
     that has annotation rows are the minimum and maximum ts of those rows; a span without rows keeps its
     record times. Services, parent and name stay the records' rules. Without it `annotations` is None and
-    nothing changes."""
+    nothing changes.
+
+    binary: the trace's binary-annotation rows (binannotstore.BinaryAnnotationRow, any order), attached by
+    span id after the trace is built (attach_binary): `binary_annotations` then maps span id -> the span's
+    BinaryAnnotations in canonical order, for every span of the trace; rows of a span id the trace has no
+    span of are ignored. Without it `binary_annotations` is None and getBinaryAnnotations() is []."""
+
+    binary_annotations: Optional[Dict[int, List[BinaryAnnotation]]] = None
 
     def __init__(self, rows: Sequence[Row], services: Optional[Sequence[str]] = None,
-                 span_names: Optional[Sequence[str]] = None, annotations: Optional[Sequence[AnnotationRow]] = None):
+                 span_names: Optional[Sequence[str]] = None, annotations: Optional[Sequence[AnnotationRow]] = None,
+                 binary: Optional[Sequence[BinaryAnnotationRow]] = None):
         self.rows: List[Row] = sorted((tuple(int(v) for v in r) for r in rows), key=canonical_key)
         self._services = None if services is None else list(services)
         self._span_names = None if span_names is None else list(span_names)
@@ -125,6 +134,29 @@ class Trace:
             for r in sorted((tuple(int(v) for v in r) for r in annotations), key=annotation_key):
                 by_span.setdefault(r[1], []).append(Annotation.of_row(r))
             self._annotate({s.id: by_span.get(s.id, []) for s in self.spans})
+        if binary is not None:
+            self.attach_binary(binary)
+
+    def attach_binary(self, rows: Sequence[BinaryAnnotationRow]) -> "Trace":
+        """Attach the trace's binary-annotation rows by span id: every span of the trace as it stands gets its
+        rows in canonical order ([] without any); rows of other span ids are ignored. Returns self."""
+        by_span: Dict[int, List[BinaryAnnotation]] = {s.id: [] for s in self.spans}
+        for r in sorted((tuple(int(v) for v in r) for r in rows), key=binary_annotation_key):
+            if r[1] in by_span:
+                by_span[r[1]].append(BinaryAnnotation.of_row(r))
+        self.binary_annotations = by_span
+        return self
+
+    def getBinaryAnnotations(self) -> List[BinaryAnnotation]:
+        """Trace.getBinaryAnnotations (Trace.scala:161-165): the binary annotations of all spans, the spans
+        in the trace's span order, each span's in canonical order. [] without attached rows."""
+        given = self.binary_annotations or {}
+        return [b for s in self.spans for b in given.get(s.id, ())]
+
+    def getBinaryAnnotationsByKey(self, key) -> List[BinaryAnnotation]:
+        """Trace.getBinaryAnnotationsByKey (Trace.scala:167-171): those whose key is `key` (the key's hash, as
+        the rows carry it), in getBinaryAnnotations' order."""
+        return [b for b in self.getBinaryAnnotations() if b.key == key]
 
     def _annotate(self, anns: Dict[int, List[Annotation]]) -> None:
         """Every span of anns (the others are dropped) as an AnnotatedSpan with its list, the times of a
@@ -150,6 +182,8 @@ class Trace:
         t._services, t._span_names, t._given = self._services, self._span_names, None
         t.spans = list(self.spans)
         t._annotate(anns)
+        if self.binary_annotations is not None:  # (a pruned span's binary annotations leave with it)
+            t.binary_annotations = {s.id: self.binary_annotations.get(s.id, []) for s in t.spans}
         return t
 
     @classmethod
@@ -427,9 +461,28 @@ class TimelineAnnotation(NamedTuple):
     span_name: Union[int, str, None]
 
 
+def resolve_binary(binaries: Sequence[BinaryAnnotation], decoder=None, services: Optional[Sequence[str]] = None) -> list:
+    """BinaryAnnotations for a reader: with a decoder (.string and .bytes by hash) the key becomes text and
+    the value its bytes; with the services dictionary a host's service id becomes its name."""
+    if decoder is None and services is None:
+        return list(binaries)
+    out = []
+    for b in binaries:
+        key, value, host = b.key, b.value, b.host
+        if decoder is not None:
+            key, value = decoder.string(key), decoder.bytes(value)
+        if host is not None and services is not None:
+            if host.service_id >= len(services):
+                raise ValueError("a service id beyond the services dictionary")
+            host = Endpoint(host.ipv4, host.port, services[host.service_id])
+        out.append(BinaryAnnotation(key, value, b.type, host, b.span_id))
+    return out
+
+
 class TraceTimeline(NamedTuple):
     """The reference's TraceTimeline(traceId, rootSpanId, annotations, binaryAnnotations).
-    binary_annotations is always []: the annotation store keeps none (a stated departure)."""
+    binary_annotations is trace.getBinaryAnnotations(): [] unless the trace carries binary-annotation rows
+    (binary=, a TraceBinaryAnnotationStore, on the by-id calls)."""
     trace_id: int
     root_span_id: int
     annotations: List[TimelineAnnotation]
@@ -440,7 +493,9 @@ class TraceTimeline(NamedTuple):
         """TraceTimeline.apply: None for a trace without spans; else all annotations of all spans (the spans
         in span order, each span's list in its order), sorted by ts with a STABLE sort, which is the stated
         order of equal timestamps. decoder: anything with .string(hash) (a SpanDecoder) turns values into
-        text (a core annotation's is its kind's). services: the service dictionary, by id, as it stands."""
+        text (a core annotation's is its kind's). services: the service dictionary, by id, as it stands.
+        binary_annotations: the trace's (getBinaryAnnotations); with the decoder the keys become text and the
+        values bytes (decoder.bytes), with the dictionary a host's service becomes its name."""
         if not trace.spans:
             return None
         given = trace.annotations or {}
@@ -460,7 +515,7 @@ class TraceTimeline(NamedTuple):
                         svc = services[svc]
                 out.append(TimelineAnnotation(a.ts, value, ipv4, port, svc, s.id, s.parent, s.name))
         out.sort(key=lambda t: t.ts)
-        return TraceTimeline(trace.id, trace.getRootMostSpan().id, out, [])
+        return TraceTimeline(trace.id, trace.getRootMostSpan().id, out, resolve_binary(trace.getBinaryAnnotations(), decoder, services))
 
 
 class TraceCombo(NamedTuple):
@@ -684,14 +739,36 @@ class TraceSpanStore:
         """The host path of getTraceCombosByIds with an annotation store."""
         return [TraceCombo.of(t, TraceTimeline.of(t, decoder, self.services)) for t in self.getTracesByIds(ids, adjust, annotations)]
 
-    def getTracesByIds(self, ids, adjust: Sequence[str] = (), annotations=None, adjust_on_device: bool = False) -> List[Trace]:
+    def _attach_binary(self, traces: Sequence[Trace], binary) -> None:
+        """Every trace gets its rows of `binary`, a TraceBinaryAnnotationStore, by span id, after it is built
+        (and adjusted): one lookup for all of them."""
+        traces = [t for t in traces if t.id is not None]
+        if not traces:
+            return
+        for t, rows in zip(traces, binary.getBinaryAnnotationsByTraceIds([t.id for t in traces])):
+            t.attach_binary(rows)
+
+    def _combos_with_binary(self, combos: List[TraceCombo], binary, decoder=None) -> List[TraceCombo]:
+        """The combos with their traces' binary annotations attached and their timelines' fourth field filled."""
+        self._attach_binary([c.trace for c in combos], binary)
+        return [c if c.timeline is None else c._replace(timeline=c.timeline._replace(
+            binary_annotations=resolve_binary(c.trace.getBinaryAnnotations(), decoder, self.services))) for c in combos]
+
+    def getTracesByIds(self, ids, adjust: Sequence[str] = (), annotations=None, adjust_on_device: bool = False,
+                       binary=None) -> List[Trace]:
         """One Trace per asked id that was found, in the order asked. annotations: a TraceAnnotationStore;
         every Trace then carries its annotations (Trace's annotations=). adjust: a sequence of "NOTHING" /
         "TIME_SKEW", folded over each trace in order as QueryService folds its adjusters; it needs
         annotations=. A trace that has no rows in the annotation store is returned unadjusted.
         adjust_on_device: the adjuster runs on the device (zk_an_adjusted_traces; the rules of
         getTraceSummariesByIds' adjust_on_device). The answer is the host path's, with ONE difference:
-        Trace.rows is None, as with Trace.of_merged."""
+        Trace.rows is None, as with Trace.of_merged.
+        binary: a TraceBinaryAnnotationStore; every Trace then carries its binary annotations
+        (Trace.attach_binary, after the adjusters: a pruned span's leave with it). It needs no annotations=."""
+        if binary is not None:
+            out = self.getTracesByIds(ids, adjust, annotations, adjust_on_device)
+            self._attach_binary(out, binary)
+            return out
         if adjust_on_device:
             self._adjust_on_device(adjust, annotations)
             return [c.trace for c in self._combos_adjusted_on_device(ids, annotations, timelines=False)]
@@ -707,13 +784,19 @@ class TraceSpanStore:
         return out
 
     def getTraceTimelinesByIds(self, ids, adjust: Sequence[str] = (), annotations=None, decoder=None,
-                               adjust_on_device: bool = False) -> List[TraceTimeline]:
+                               adjust_on_device: bool = False, binary=None) -> List[TraceTimeline]:
         """QueryService.getTraceTimelinesByIds: the timeline of every asked trace that was found, in the
         order asked, after the adjusters. annotations=, a TraceAnnotationStore, is required. decoder: turns
         the values into text (TraceTimeline.of); service names come from the store's services dictionary.
-        adjust_on_device: as for getTracesByIds; the answer is the same."""
+        adjust_on_device: as for getTracesByIds; the answer is the same. binary: a TraceBinaryAnnotationStore;
+        the timelines' binary_annotations are then the traces' (keys as text and values as bytes with the
+        decoder, host services as names with the dictionary); without it they are []."""
         if annotations is None:
             raise ValueError("timelines need annotations=, a TraceAnnotationStore")
+        if binary is not None:
+            combos = self.getTraceCombosByIds(ids, adjust=adjust, annotations=annotations, adjust_on_device=adjust_on_device,
+                                              binary=binary, decoder=decoder)
+            return [c.timeline for c in combos if c.timeline is not None]
         if adjust_on_device:
             self._adjust_on_device(adjust, annotations)
             return [c.timeline for c in self._combos_adjusted_on_device(ids, annotations, decoder, lists=False)]
@@ -903,7 +986,7 @@ class TraceSpanStore:
         return annotations is not None or not on_device
 
     def getTraceCombosByIds(self, ids, on_device: bool = False, adjust: Sequence[str] = (), annotations=None,
-                            adjust_on_device: bool = False) -> List[TraceCombo]:
+                            adjust_on_device: bool = False, binary=None, decoder=None) -> List[TraceCombo]:
         """QueryService.getTraceCombosByIds: one TraceCombo (the trace, its summary, its timeline, its span
         depths) per asked id that was found, in the order asked; summary is None for a trace without a timed
         fragment. on_device: spans, summary and depths are merged on the device (zk_sp_traces) and no
@@ -911,15 +994,21 @@ class TraceSpanStore:
         with an annotation store the host path is used and timeline is filled, without one it is None.
         adjust_on_device: with an annotation store, the adjuster, the spans' lists and the depths come from
         the device too (zk_an_adjusted_traces; the rules of getTraceSummariesByIds' adjust_on_device). The
-        answer is the host path's, with ONE difference: Trace.rows is None, as with Trace.of_merged."""
+        answer is the host path's, with ONE difference: Trace.rows is None, as with Trace.of_merged.
+        binary: a TraceBinaryAnnotationStore; on every path the traces then carry their binary annotations
+        and a timeline's binary_annotations is filled (resolved through decoder= and the services
+        dictionary). decoder: turns a timeline's values into text, as in getTraceTimelinesByIds."""
+        if binary is not None:
+            return self._combos_with_binary(self.getTraceCombosByIds(ids, on_device, adjust, annotations, adjust_on_device,
+                                                                     decoder=decoder), binary, decoder)
         if adjust_on_device:
             self._adjust_on_device(adjust, annotations, on_device)
-            return self._combos_adjusted_on_device(ids, annotations)
+            return self._combos_adjusted_on_device(ids, annotations, decoder)
         if not self._host_only(on_device, adjust, annotations):
             return self._combos_on_device(ids)
         if annotations is None:
             return [TraceCombo.of(t) for t in self.getTracesByIds(ids, adjust, annotations)]
-        return self._combos_on_host(ids, adjust, annotations)
+        return self._combos_on_host(ids, adjust, annotations, decoder)
 
     def _summaries_adjusted_on_device(self, ids, annotations) -> List[TraceSummary]:
         """getTraceSummariesByIds(adjust=("TIME_SKEW",), annotations=) from annotations.adjusted_summaries():
